@@ -2,12 +2,13 @@
 """Headline benchmark: frames/sec of integration() + raycasting() on the synthetic 640x480 depth
 stream into a 512^3 / 4.8 m TSDF (BASELINE.json metric; configs[1] at N=1).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one frame of the hot path: allocation scan + integration sweep + raycast.  The depth
 frames are generated before the timed region and are resident in HBM; poses are 64-byte kernel
-arguments.  N > 1 shards the image rows of ONE stream across ranks with one RCCL all-gather of the
+arguments.  Exactly K steps are timed (`ms_per_step` = wall time of the timed region / K); `--sustain` adds a
+second timed region on request.  N > 1 shards the image rows of ONE stream across ranks with one RCCL all-gather of the
 new-block key lists per frame (supereight_amd/multi_gpu.py): total work is fixed -> "strong".
 
 Rank 0 prints ONE JSON line.  Besides the contract fields it carries
@@ -59,7 +60,7 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-frames", type=int, default=20, help="timed frames of the CPU baseline sample")
     ap.add_argument("--cpu-reps", type=int, default=4, help="repetitions of the CPU baseline sample (the fastest is reported, all are listed)")
-    ap.add_argument("--sustain", type=int, default=200, help="N = 1: after the K contract steps keep going until this many frames have been timed in total (0 = off)")
+    ap.add_argument("--sustain", type=int, default=0, help="N = 1: after the K contract steps keep going, in a second timed region, until this many frames have been timed in total (0 = off)")
     ap.add_argument("--no-streaming", action="store_true", help="N = 1: the eager two-queue schedule instead of the one-queue streaming schedule (se_hip_set_streaming)")
     ap.add_argument("--sharded-streaming", action="store_true",
                     help="N > 1: the one-queue schedule for the row-sharded replicas too (all-gather and commit behind the fused launch on the main stream); "
@@ -74,6 +75,8 @@ def parse():
     ap.add_argument("--config4-steps", type=int, default=20)
     ap.add_argument("--no-replicas", action="store_true", help="N > 1: skip the replicas-only leg (independent streams per GPU, the throughput upper bound of SURVEY 8e)")
     ap.add_argument("--detail", type=str, default="", help="write a detailed JSON report to this path")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (raycast images, map bricks) to DIR/<name>.npy; see dump_outputs()")
     return ap.parse_args()
 
 
@@ -89,6 +92,51 @@ def algorithmic_bytes(stats: dict, frames: int, W: int, H: int, voxel_bytes: int
     a_alloc = W * H * 4 + stats["probes"] / n * 4
     a_ray = W * H * 24 + (stats["gets"] * voxel_bytes + (8 * stats["interps"] + 32 * stats["grads"]) * vb) / n
     return {"integrate": a_int, "alloc_scan": a_alloc, "raycast": a_ray}
+
+
+DUMP_MAX_BYTES = 60_000_000   # --dump-outputs: all arrays together (under 64 MB with the .npy headers)
+DUMP_SEED = 0                 # the fixed sample of bricks / nodes when the whole map does not fit
+
+
+def _sample(n: int, m: int) -> np.ndarray:
+    """indices of a fixed, seeded sample of m out of n rows (all rows when n <= m), ascending"""
+    if n <= m:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, m, replace=False))
+
+
+def dump_outputs(out_dir: str, p) -> dict:
+    """What a caller of integration() + raycasting() receives after the last timed frame, as float32 / float64 .npy files:
+      vertex, normal            (H, W, 3) float32 raycast images (normal.x == -2: no hit)
+      block_coords              (nb, 3) brick coordinates of every allocated block, key order (float64, exact)
+      block_active              (nb,) VoxelBlock::active_ flags
+      block_index               (m,) rows of block_coords whose voxel planes follow (a fixed seeded sample when the map is large)
+      block_x, block_y          (m, 512) voxel planes of those blocks (SDF: x = tsdf, y = weight; OFusion: x = log-odds, y = time stamp)
+      node_side                 (nn,) edge of every octree node, key order
+      node_x, node_y            (nn', 8) node values of a fixed seeded sample (node_index)
+    Inputs are generated from fixed seeds, so two builds run with the same arguments can be compared file for file."""
+    v, n = p.vertex_normal()
+    coords, x, y, act = p.blocks()
+    _, side, nx, ny = p.nodes()
+    arrays = {"vertex": v, "normal": n, "block_coords": coords.astype(np.float64), "block_active": act.astype(np.float32),
+              "node_side": side.astype(np.float64)}
+    fixed = sum(a.nbytes for a in arrays.values()) + 8 * (len(coords) + len(side))     # + the two index arrays at most
+    room = DUMP_MAX_BYTES - fixed
+    if room <= 0:
+        raise SystemExit(f"--dump-outputs: images and key lists alone are {fixed} bytes (> {DUMP_MAX_BYTES})")
+    # bricks get 7/8 of what is left, nodes the rest (a brick row pair is 4 KiB, a node row pair 64 B)
+    bi = _sample(len(coords), (room * 7 // 8) // (2 * 512 * 4))
+    ni = _sample(len(side), (room // 8) // (2 * 8 * 4))
+    arrays.update({"block_index": bi.astype(np.float64), "block_x": x[bi], "block_y": y[bi],
+                   "node_index": ni.astype(np.float64), "node_x": nx[ni], "node_y": ny[ni]})
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "files": sorted(arrays), "bytes": int(total), "blocks": len(coords), "blocks_dumped": len(bi),
+            "nodes": len(side), "nodes_dumped": len(ni)}
 
 
 def make_stream(args, n_frames: int = 0):
@@ -434,8 +482,8 @@ def main():
     W, H, N, dim, mu = args.width, args.height, args.res, args.dim, args.mu
     warm = max(args.warmup, 4)   # frames 0..3 are the reference's own warm-up (forced integration, no raycast before frame 3)
     K = args.steps
-    # N = 1: the K contract steps are followed, in a second timed region, by as many frames as it takes to have
-    # `--sustain` frames timed in total (K = 20 is 1.6 ms of GPU time: too short to be a stable figure on its own)
+    # N = 1, on request: the K contract steps are followed, in a second timed region, by as many frames as it takes to have
+    # `--sustain` frames timed in total (off by default: --steps alone sets the number of timed frames)
     extra = max(0, args.sustain - K) if (world == 1 and args.sustain > 0) else 0
     F = warm + K + extra
 
@@ -517,6 +565,11 @@ def main():
     sp.p.enable_timing(False)
     nblocks, nnodes = sp.p.counts()
     mem = sp.p.memory_info()
+    dumped = None
+    if args.dump_outputs:
+        sp.gather_images()       # collective: every rank of a row-sharded run takes part, rank 0 writes
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, sp.p)
     sp.close()
     if scratch is not None:
         scratch.close()
@@ -547,6 +600,8 @@ def main():
         }
         if sustained:
             result["sustained"] = sustained
+        if dumped:
+            result["dumped_outputs"] = dumped
 
     # ---- roofline of the dominant kernel (rank 0, its own share of the image)
     if timings is not None and world > 1:

@@ -4,7 +4,7 @@
 
 The reference cannot be built in this image (Eigen3 / Sophus absent), so these are ORACLE outputs,
 not reference outputs: they pin the oracle against accidental change and give the GPU tests a
-fixture that needs neither the oracle nor /root/reference at run time.  Per field type: 5 frames of
+fixture that needs neither the oracle nor the reference at run time.  Per field type: 5 frames of
 the synthetic stream, 80x60 depth into a 128^3 / 2.4 m volume -- and (r03) 8 frames of the ICL-like stress stream
 (every 12th frame of its camera path: 24 deg and ~15 cm between consecutive inputs, scene clipped by the volume, sensor noise,
 negative fy), whose raycasts leave the volume (stats.oob > 0, stored) without touching the reads the reference leaves undefined

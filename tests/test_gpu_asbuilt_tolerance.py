@@ -2,7 +2,7 @@
 
 The parity gate of this repository is bit-exactness against oracle/ compiled with -ffp-contract=off and with the
 Eigen / Sophus arithmetic defined in source order (tests/test_gpu_parity.py).  The reference itself is compiled by
-GCC -O3 -march=native (FMA contraction on, /root/reference CMakeLists.txt:6) against real Sophus, whose SE3f(Matrix4f)
+GCC -O3 -march=native (FMA contraction on, the reference's CMakeLists.txt:6) against real Sophus, whose SE3f(Matrix4f)
 round-trips the rotation through a unit quaternion (DenseSLAMSystem.cpp:237).  This test runs the SAME frames through the
 HIP path and through the oracle's noise-floor variant (oracle/Makefile FPC=fast + so_set_sophus_quat(1)), prints the
 distance distribution and asserts the acceptance tolerances of SURVEY.md 8(d):

@@ -1,22 +1,16 @@
-"""Build-container pin of include/se_mc_table.h: case by case the same triangles, in the same order and orientation, as
-the reference's triTable (se_core/include/se/algorithms/edge_tables.h:66).  /root/reference does not exist on the GPU
-box, so the test skips there (it is not a gpu test)."""
+"""Pin of include/se_mc_table.h: case by case the same triangles, in the same order and orientation, as the reference's
+triTable (se_core/include/se/algorithms/edge_tables.h:66).  The reference's 256 x 16 literals are stored as a data fixture,
+tests/golden/mc_tri_table_i8.npy (-1 = no further edge), so the check needs no reference checkout."""
 import os
-import re
 
 import numpy as np
-import pytest
 
 from tests.test_mesh_export import load_table
 
-REF = "/root/reference/se_core/include/se/algorithms/edge_tables.h"
+GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "mc_tri_table_i8.npy")
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference checkout not present (GPU box)")
 def test_triangle_table_equals_the_reference_literals():
-    src = open(REF).read()
-    body = src[src.index("int triTable[256][16]"):]
-    rows = re.findall(r"\{([^{}]*)\}", body)[:256]
-    ref = np.array([[int(v) for v in r.split(",") if v.strip()] for r in rows], np.int64)
+    ref = np.load(GOLDEN).astype(np.int64)
     assert ref.shape == (256, 16)
     assert (load_table() == ref).all()
