@@ -186,6 +186,12 @@ class DenseSLAMSystem {
     out.coords.resize((size_t)nb * 3); out.x.resize((size_t)nb * 512); out.y.resize((size_t)nb * 512); out.active.resize(nb);
     if (nb) ok(se_hip_download_blocks(h_, out.coords.data(), out.x.data(), out.y.data(), out.active.data()));
   }
+  /* Not in the reference's class (an addition of this mirror): VolumeTemplate::get / operator[] / interp / grad for n points in metres
+   * (host_points_m[n][3]) answered on the device map without getMap() -- se_hip_query_points_host, definitions in se_hip.h.  host_out
+   * holds host arrays; a null member is not computed. */
+  bool queryMap(const float* host_points_m, size_t n, se_hip_query_out& host_out) {
+    return ok(se_hip_query_points_host(h_, host_points_m, (int64_t)n, &host_out));
+  }
   /* vertex_ / normal_ of the last raycasting(): width*height packed xyz */
   bool getVertexNormal(std::vector<float>& vertex, std::vector<float>& normal) {
     const size_t n = (size_t)computation_size_.x() * computation_size_.y() * 3;

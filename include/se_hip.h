@@ -299,6 +299,39 @@ int se_hip_download_blocks(se_hip_pipeline* p, int32_t* coords, float* x, float*
 /* internal nodes sorted by key: code[n] (key = code|level), side[n], x[n][8], y[n][8] (value_[8]) */
 int se_hip_download_nodes(se_hip_pipeline* p, uint64_t* code, uint32_t* side, float* x, float* y);
 
+/* ---- batched point queries against the resident map: the reference's map read interface VolumeTemplate
+ *      (se_denseslam/include/se/continuous/volume_template.hpp:77-102) for N points in metres at once, without getMap().
+ * Voxel coordinates of a point p: q = s * p per axis, s = (float)size / dim (a float division; no FMA anywhere), v = (int)q (truncation).
+ *   fine[n][2]   (x, y)  VolumeTemplate::get(p) = Octree::get_fine(v): voxel v, or initValue() if its block is not allocated.
+ *   coarse[n][2] (x, y)  VolumeTemplate::operator[](p) = Octree::get(v) (octree.hpp:335-355): voxel v if its block exists, else value_[childid]
+ *                        of the deepest existing node on the path from the root (OFusion's multi-resolution free space).
+ *   interp[n]            VolumeTemplate::interp(p, x) = Octree::interp(q) (octree.hpp:541-563), bit for bit.
+ *   grad[n][3]           VolumeTemplate::grad(p, x) = Octree::grad(q) (octree.hpp:652-737), scaled by 0.5 * dim / size as there, bit for bit.
+ *   status[n] (uint8)    bit 0: v lies in [0, size)^3; bit 1: the block holding v is allocated; bit 2: all eight voxels interp reads
+ *                        (corners max(floor(q), 0) + {0, 1} per axis) lie in allocated blocks -- the interpolated value comes from observed
+ *                        blocks only.
+ * y is returned as float, as se_hip_download_blocks does: the weight for SDF, the last-update time for OFusion.
+ * Defined beyond the reference, whose unchecked tree walk is undefined there:
+ *   - v outside [0, size)^3: fine = coarse = initValue(), status bit 0 clear; interp / grad are still Octree::interp / Octree::grad with
+ *     missing blocks (outside the volume none exists): empty().x / initValue().x corners as the reference's gather rules say.
+ *   - a non-finite point, or |q| >= 2^20 on any axis: status = 0, fine = coarse = initValue(), interp = empty().x, grad = (0, 0, 0); no map
+ *     memory is read.
+ * A null output pointer means "not wanted"; at least one must be set.  Both entries answer for the map after everything enqueued before them
+ * (a scan that ran on the side stream included), refuse n < 0, a null points pointer with n > 0 or no output with SE_HIP_E_INVALID (n == 0 is a
+ * no-op), and report a sticky SE_HIP_E_CAPACITY like the other read-back calls.  No launch counter (SE_HIP_K_*) counts them.
+ *   se_hip_query_points       device arrays (points [n][3] float, outputs as above); enqueued on the handle's stream, asynchronous like the
+ *                             stage calls -- the outputs are complete once the stream has reached that point (se_hip_sync).
+ *   se_hip_query_points_host  host arrays; staged through a device buffer the handle keeps (and grows); synchronises before it returns. */
+typedef struct se_hip_query_out {
+  float* fine;      /* [n][2] */
+  float* coarse;    /* [n][2] */
+  float* interp;    /* [n]    */
+  float* grad;      /* [n][3] */
+  uint8_t* status;  /* [n]    */
+} se_hip_query_out;
+int se_hip_query_points(se_hip_pipeline* p, const float* device_points_m, int64_t n, const se_hip_query_out* device_out);
+int se_hip_query_points_host(se_hip_pipeline* p, const float* host_points_m, int64_t n, const se_hip_query_out* host_out);
+
 /* ---- "next" row f-4: Octree::save (se_core/include/se/octree.hpp:898-914, io/se_serialise.hpp:54-86),
  *      written straight from the device map in the reference's byte layout:
  *        int32 size, float dim, uint64 n_nodes, n_nodes x {uint64 code, int32 side, value_[8]},

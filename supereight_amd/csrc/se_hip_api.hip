@@ -22,6 +22,7 @@
 #include "se_kernels.h"
 #include "se_track_kernels.h"
 #include "se_mesh_kernels.h"
+#include "se_query_kernels.h"
 
 int flush_pending_raycast(se_hip_pipeline* p);   // (defined next to se_hip_frame)
 
@@ -143,6 +144,8 @@ struct se_hip_pipeline {
   size_t shard_cap = 0;                  // bricks per segment
   bool mc_table_ready = false;   // SE_MC_TRI uploaded to constant memory
   unsigned long long* mesh_ctr = nullptr;
+  unsigned char* query_buf = nullptr;   // se_hip_query_points_host: device staging of the points and the outputs, grown on demand
+  size_t query_cap = 0;
   bool filter_input = false;   // preprocessing(..., filterInput): tracking sees the bilateral-filtered depth
   bool occ_commit_due = false; // the next sweep kernel must publish the scan's occupancy bits
   OccLists occ_lists{nullptr, 0, 0};   // ... of these key lists (own list, or every rank's after se_hip_alloc_commit)
@@ -708,6 +711,7 @@ int se_hip_destroy(se_hip_pipeline* p) {
   if (p->sort_tmp) hipFree(p->sort_tmp);
   if (p->gate_host) hipHostFree(p->gate_host);
   if (p->mesh_ctr) hipFree(p->mesh_ctr);
+  if (p->query_buf) hipFree(p->query_buf);
   for (int i = 0; i < se_hip_pipeline::kIn; ++i) { if (p->in_host[i]) hipHostFree(p->in_host[i]); if (p->in_done[i]) hipEventDestroy(p->in_done[i]); }
   if (p->own_side && p->side) hipStreamDestroy(p->side);
   if (p->ev_sweep) hipEventDestroy(p->ev_sweep);
@@ -1904,6 +1908,66 @@ int se_hip_download_nodes(se_hip_pipeline* p, uint64_t* code, uint32_t* side, fl
     if (y) std::memcpy(y + i * 8, hy.data() + s * 8, 8 * sizeof(float));
   }
   return SE_HIP_OK;
+}
+
+
+// ------------------------------------------------------------------------------------ point queries
+namespace {
+int query_args(const float* points, int64_t n, const se_hip_query_out* out) {
+  if (n < 0) return fail(SE_HIP_E_INVALID, "se_hip_query_points: n < 0");
+  if (n > 0 && !points) return fail(SE_HIP_E_INVALID, "se_hip_query_points: null points");
+  if (!out || !(out->fine || out->coarse || out->interp || out->grad || out->status)) return fail(SE_HIP_E_INVALID, "se_hip_query_points: no output requested");
+  return SE_HIP_OK;
+}
+void launch_query(se_hip_pipeline* p, const float* points, int64_t n, const QueryOut& o) {
+  const DevMap& m = p->map;
+  const float s = (float)m.size / m.dim;                // VolumeTemplate: inverseVoxelSize = _size / _dim
+  const float grad_scale = 0.5f * m.dim / (float)m.size;  // octree.hpp:736
+  const int grid = grid_for((size_t)n, SE_WG_QUERY, 16384);
+  if (m.dense) hipLaunchKernelGGL((k_query_points<true>), dim3(grid), dim3(SE_WG_QUERY), 0, p->stream, m, points, (long long)n, o, s, grad_scale);
+  else hipLaunchKernelGGL((k_query_points<false>), dim3(grid), dim3(SE_WG_QUERY), 0, p->stream, m, points, (long long)n, o, s, grad_scale);
+}
+}  // namespace
+
+int se_hip_query_points(se_hip_pipeline* p, const float* device_points_m, int64_t n, const se_hip_query_out* device_out) {
+  if (int r = check(p)) return r;
+  if (int r = query_args(device_points_m, n, device_out)) return r;
+  if (int r = join_scan(p)) return r;
+  if (int r = check_overflow(p)) return r;
+  if (n == 0) return SE_HIP_OK;
+  const QueryOut o{device_out->fine, device_out->coarse, device_out->interp, device_out->grad, device_out->status};
+  launch_query(p, device_points_m, n, o);
+  HIP_TRY(hipGetLastError());
+  return SE_HIP_OK;
+}
+
+int se_hip_query_points_host(se_hip_pipeline* p, const float* host_points_m, int64_t n, const se_hip_query_out* host_out) {
+  if (int r = check(p)) return r;
+  if (int r = query_args(host_points_m, n, host_out)) return r;
+  if (int r = join_scan(p)) return r;
+  if (n == 0) return fetch_counters(p);
+  // staging: [points n x 3][fine n x 2][coarse n x 2][interp n][grad n x 3][status n], only the parts asked for (floats first: 4-byte aligned)
+  const size_t un = (size_t)n;
+  const size_t sz[5] = {host_out->fine ? 2 * un * 4 : 0, host_out->coarse ? 2 * un * 4 : 0, host_out->interp ? un * 4 : 0,
+                        host_out->grad ? 3 * un * 4 : 0, host_out->status ? un : 0};
+  size_t off[5], need = 3 * un * 4;
+  for (int k = 0; k < 5; ++k) { off[k] = need; need += sz[k]; }
+  if (need > p->query_cap) {
+    if (p->query_buf) { HIP_TRY(hipStreamSynchronize(p->stream)); hipFree(p->query_buf); p->query_buf = nullptr; p->query_cap = 0; }
+    HIP_TRY(hipMalloc((void**)&p->query_buf, need));
+    p->query_cap = need;
+  }
+  unsigned char* b = p->query_buf;
+  HIP_TRY(hipMemcpyAsync(b, host_points_m, 3 * un * 4, hipMemcpyHostToDevice, p->stream));
+  auto dev = [&](int k) { return sz[k] ? b + off[k] : nullptr; };
+  const QueryOut o{(float*)dev(0), (float*)dev(1), (float*)dev(2), (float*)dev(3), (uint8_t*)dev(4)};
+  launch_query(p, (const float*)b, n, o);
+  HIP_TRY(hipGetLastError());
+  void* dst[5] = {host_out->fine, host_out->coarse, host_out->interp, host_out->grad, host_out->status};
+  for (int k = 0; k < 5; ++k)
+    if (sz[k]) HIP_TRY(hipMemcpyAsync(dst[k], b + off[k], sz[k], hipMemcpyDeviceToHost, p->stream));
+  // (synchronises; a sticky overflow is reported as the other read-back calls report it)
+  return fetch_counters(p);
 }
 
 

@@ -1,0 +1,146 @@
+// Batched point queries against the resident map (se_hip_query_points, include/se_hip.h): for N points in metres, what the
+// reference's map read interface VolumeTemplate (se_denseslam/include/se/continuous/volume_template.hpp:77-102) answers --
+// get(p) = Octree::get_fine, operator[](p) = Octree::get (coarse node value where no block exists), interp(p, x) and grad(p, x).
+//
+// One thread per point, grid-stride loop over int64 n, wave64 workgroups.  interp / grad are the raycast's own inline
+// se_interp / se_grad (bit-exact with Octree::interp / Octree::grad); the coarse walk is the index pyramid read top-down.
+// Voxel coordinates: q = s * p per axis (s = (float)size / dim), v = (int)q (truncation, VolumeTemplate::get / operator[]).
+// A point with a non-finite q or |q| >= 2^20 on any axis gets the defaults (status 0, initValue() for fine and coarse,
+// empty().x for interp, 0 for grad) and touches no map memory; see se_hip.h for the full definition of every output.
+#pragma once
+#include "se_kernels.h"
+
+#define SE_WG_QUERY 64           // one wave per workgroup
+#define SE_QUERY_LIMIT 1048576.f // |s * p| below 2^20 on every axis, else the point is refused (status 0)
+
+// status bits of se_hip_query_out::status
+#define SE_Q_IN_VOLUME 1u        // v lies in [0, size)^3
+#define SE_Q_ALLOCATED 2u        // the block holding v is allocated
+#define SE_Q_OBSERVED 4u         // all eight voxels interp reads lie in allocated blocks
+
+struct QueryOut { float* fine; float* coarse; float* interp; float* grad; uint8_t* status; };
+
+// leaf-grid entry (slot + 1) of block (bx, by, bz), 0 if it lies outside the volume or is not allocated.  Both layouts keep
+// the entry in tab[] (a dense brick grid also holds bricks of blocks that were never allocated: initValue() everywhere).
+__device__ __forceinline__ uint32_t se_query_block(const DevMap& m, int bx, int by, int bz) {
+  const int nb = m.size >> 3;
+  if (!((unsigned)bx < (unsigned)nb && (unsigned)by < (unsigned)nb && (unsigned)bz < (unsigned)nb)) return 0u;
+  const uint32_t e = m.tab[leaf_index(m, bx, by, bz)];
+  return e == SE_PENDING ? 0u : e;
+}
+
+// Octree::grad (octree.hpp:652-737) for a stencil that leaves the volume: every one of the 32 voxels is looked up on its own, a voxel outside the
+// volume or in a block that is not allocated reads initValue().x (Octree::get(x, y, z, cached) -> get_fine).  Same clamps, same term order as
+// se_grad_generic.
+__device__ __forceinline__ f3 se_query_grad_checked(const DevMap& m, const FieldConst fc, f3 pos) {
+  const float flx = floorf(pos.x), fly = floorf(pos.y), flz = floorf(pos.z);
+  const int bx = cvt_i32(flx), by = cvt_i32(fly), bz = cvt_i32(flz);
+  const float fx = pos.x - flx, fy = pos.y - fly, fz = pos.z - flz;
+  const int hi = m.size - 1;
+  const int X[4] = {max(bx - 1, 0), max(bx, 0), min(bx + 1, hi), min(bx + 2, hi)};
+  const int Y[4] = {max(by - 1, 0), max(by, 0), min(by + 1, hi), min(by + 2, hi)};
+  const int Z[4] = {max(bz - 1, 0), max(bz, 0), min(bz + 1, hi), min(bz + 2, hi)};
+  float V[4][4][4];
+#pragma unroll
+  for (int zi = 0; zi < 4; ++zi)
+#pragma unroll
+    for (int yi = 0; yi < 4; ++yi)
+#pragma unroll
+      for (int xi = 0; xi < 4; ++xi) {
+        const int central = (xi == 1 || xi == 2) + (yi == 1 || yi == 2) + (zi == 1 || zi == 2);
+        if (central < 2) continue;
+        const int x = X[xi], y = Y[yi], z = Z[zi];
+        const uint32_t e = in_volume(m, x, y, z) ? se_query_block(m, x >> 3, y >> 3, z >> 3) : 0u;
+        V[zi][yi][xi] = e ? m.vx[se_voxel_index(e, x, y, z)] : fc.init_x;
+      }
+  f3 g;
+  g.x = (((V[1][1][2] - V[1][1][0]) * (1 - fx) + (V[1][1][3] - V[1][1][1]) * fx) * (1 - fy) +
+         ((V[1][2][2] - V[1][2][0]) * (1 - fx) + (V[1][2][3] - V[1][2][1]) * fx) * fy) * (1 - fz) +
+        (((V[2][1][2] - V[2][1][0]) * (1 - fx) + (V[2][1][3] - V[2][1][1]) * fx) * (1 - fy) +
+         ((V[2][2][2] - V[2][2][0]) * (1 - fx) + (V[2][2][3] - V[2][2][1]) * fx) * fy) * fz;
+  g.y = (((V[1][2][1] - V[1][0][1]) * (1 - fx) + (V[1][2][2] - V[1][0][2]) * fx) * (1 - fy) +
+         ((V[1][3][1] - V[1][1][1]) * (1 - fx) + (V[1][3][2] - V[1][1][2]) * fx) * fy) * (1 - fz) +
+        (((V[2][2][1] - V[2][0][1]) * (1 - fx) + (V[2][2][2] - V[2][0][2]) * fx) * (1 - fy) +
+         ((V[2][3][1] - V[2][1][1]) * (1 - fx) + (V[2][3][2] - V[2][1][2]) * fx) * fy) * fz;
+  g.z = (((V[2][1][1] - V[0][1][1]) * (1 - fx) + (V[2][1][2] - V[0][1][2]) * fx) * (1 - fy) +
+         ((V[2][2][1] - V[0][2][1]) * (1 - fx) + (V[2][2][2] - V[0][2][2]) * fx) * fy) * (1 - fz) +
+        (((V[3][1][1] - V[1][1][1]) * (1 - fx) + (V[3][1][2] - V[1][1][2]) * fx) * (1 - fy) +
+         ((V[3][2][1] - V[1][2][1]) * (1 - fx) + (V[3][2][2] - V[1][2][2]) * fx) * fy) * fz;
+  return g;  // the caller applies (0.5f * dim / size)
+}
+
+// One instantiation per brick layout.  The field type needs none: y is read through se_ld_y, whose byte / float plane test is uniform
+// across the wave, and initValue() / empty() come from the map (FieldConst).
+template <bool DENSE>
+__global__ __launch_bounds__(SE_WG_QUERY) void k_query_points(DevMap m, const float* __restrict__ pts, long long n, QueryOut o, float s, float grad_scale) {
+  const FieldConst fc = se_field_const(m);
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const f3 q = {s * pts[3 * i], s * pts[3 * i + 1], s * pts[3 * i + 2]};
+    float fine_x = fc.init_x, fine_y = fc.init_y, coarse_x = fc.init_x, coarse_y = fc.init_y, ip = fc.empty_x;
+    f3 g = {0.f, 0.f, 0.f};
+    uint32_t st = 0u;
+    // (a NaN fails every comparison)
+    if (fabsf(q.x) < SE_QUERY_LIMIT && fabsf(q.y) < SE_QUERY_LIMIT && fabsf(q.z) < SE_QUERY_LIMIT) {
+      const int x = cvt_i32(q.x), y = cvt_i32(q.y), z = cvt_i32(q.z);
+      if (in_volume(m, x, y, z)) {
+        st |= SE_Q_IN_VOLUME;
+        const uint32_t e = se_query_block(m, x >> 3, y >> 3, z >> 3);
+        if (e) {
+          st |= SE_Q_ALLOCATED;
+          const size_t vi = se_voxel_index(e, x, y, z);
+          fine_x = coarse_x = m.vx[vi];
+          fine_y = coarse_y = se_ld_y(m, vi);
+        } else if (o.coarse) {
+          // Octree::get (octree.hpp:335-355): descend from the root while the child on the path exists; the first missing child's
+          // value_[childid] in its parent is the answer.  Every allocated octant has all its ancestors, so the walk stops at the first
+          // level l whose octant is absent.  Unrolled over the constant bound so that m.off[] is indexed by constants only.
+          uint32_t nid = 0u;   // node 0 = the root
+          int lmiss = m.leaf_level;
+          bool down = true;
+#pragma unroll
+          for (int l = 1; l < SE_MAX_LEVELS; ++l) {
+            if (down && l < m.leaf_level) {
+              const int sh = m.max_level - l;
+              uint32_t c = m.tab[tab_index(m, l, x >> sh, y >> sh, z >> sh)];
+              c = c == SE_PENDING ? 0u : c;
+              if (c) nid = c - 1u;
+              else { lmiss = l; down = false; }
+            }
+          }
+          const int sh = m.max_level - lmiss;
+          const uint32_t child = ((uint32_t)(x >> sh) & 1u) | (((uint32_t)(y >> sh) & 1u) << 1) | (((uint32_t)(z >> sh) & 1u) << 2);
+          coarse_x = m.nx[(size_t)nid * 8 + child];
+          coarse_y = m.ny[(size_t)nid * 8 + child];
+        }
+      }
+      if (o.status) {
+        // the interpolation cell of se_interp / Octree::interp: corners lower .. lower + 1 per axis, lower = max(floor(q), 0)
+        const int lx = max(cvt_i32(floorf(q.x)), 0), ly = max(cvt_i32(floorf(q.y)), 0), lz = max(cvt_i32(floorf(q.z)), 0);
+        const bool cx = (lx & 7) == 7, cy = (ly & 7) == 7, cz = (lz & 7) == 7;
+        bool all = true;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const bool need = (!(k & 1) || cx) && (!(k & 2) || cy) && (!(k & 4) || cz);
+          if (need && all) all = se_query_block(m, (lx + (k & 1)) >> 3, (ly + ((k >> 1) & 1)) >> 3, (lz + (k >> 2)) >> 3) != 0u;
+        }
+        st |= all ? SE_Q_OBSERVED : 0u;
+      }
+      BlkCache c = {-1, -1, -1, 0u};
+      if (o.interp) ip = se_interp<DENSE>(m, fc, q, c);
+      if (o.grad) {
+        // se_grad (both forms) takes the stencil's voxels from the blocks of its two extreme clamped coordinates per axis, which holds while
+        // -1 <= floor(q) <= size - 1 on every axis (always, for the raycast).  Outside that band the checked form below reads each voxel by itself.
+        const int hi = m.size - 1;
+        const int bx = cvt_i32(floorf(q.x)), by = cvt_i32(floorf(q.y)), bz = cvt_i32(floorf(q.z));
+        const bool band = bx >= -1 && bx <= hi && by >= -1 && by <= hi && bz >= -1 && bz <= hi;
+        g = f3_scale(grad_scale, band ? se_grad<DENSE>(m, fc, q, c) : se_query_grad_checked(m, fc, q));
+      }
+    }
+    if (o.fine) { o.fine[2 * i] = fine_x; o.fine[2 * i + 1] = fine_y; }
+    if (o.coarse) { o.coarse[2 * i] = coarse_x; o.coarse[2 * i + 1] = coarse_y; }
+    if (o.interp) o.interp[i] = ip;
+    if (o.grad) { o.grad[3 * i] = g.x; o.grad[3 * i + 1] = g.y; o.grad[3 * i + 2] = g.z; }
+    if (o.status) o.status[i] = (uint8_t)st;
+  }
+}

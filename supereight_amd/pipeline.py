@@ -33,6 +33,11 @@ class SeHipError(RuntimeError):
     pass
 
 
+class _QueryOut(C.Structure):
+    """se_hip_query_out of include/se_hip.h: output addresses, 0 = not wanted."""
+    _fields_ = [("fine", C.c_void_p), ("coarse", C.c_void_p), ("interp", C.c_void_p), ("grad", C.c_void_p), ("status", C.c_void_p)]
+
+
 class _Config(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("volume_resolution", C.c_int32),
                 ("volume_dimension", C.c_float), ("field_type", C.c_int32), ("device", C.c_int32),
@@ -101,6 +106,8 @@ EXPORTS = {
     "se_hip_get_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),
     "se_hip_enable_stats": (C.c_int, [C.c_void_p, C.c_int32]),
     "se_hip_get_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32]),
+    "se_hip_query_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_QueryOut)]),
+    "se_hip_query_points_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_QueryOut)]),
 }
 
 
@@ -155,16 +162,25 @@ def _colmajor(m) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(m, dtype=np.float32).reshape(4, 4).T).reshape(16)
 
 
+def _torch_module(obj):
+    """torch, if `obj` is a torch tensor (without importing torch for callers that never use it)."""
+    import sys
+    torch = sys.modules.get("torch")
+    return torch if torch is not None and isinstance(obj, torch.Tensor) else None
+
+
 class DenseSLAMPipeline:
     # (class-level defaults: an object that adopts a handle made by se_hip_create_replicas does not run __init__)
     _k_last = _k_arr = _pyr_arr = None
     _k_addr = 0
+    _device = None
 
     def __init__(self, input_size, volume_resolution: int, volume_dimension: float, init_pose=None,
                  field_type: int = SDF, device: int = 0, max_blocks: int = 0, rows=None, streaming: bool = False):
         self.lib = load_library()
         self.W, self.H = int(input_size[0]), int(input_size[1])
         self.size, self.dim, self.field = int(volume_resolution), float(volume_dimension), field_type
+        self._device = int(device)
         rb, re_ = rows if rows is not None else (0, 0)
         cfg = _Config(self.W, self.H, self.size, self.dim, field_type, device, max_blocks, rb, re_)
         h = C.c_void_p()
@@ -526,6 +542,54 @@ class DenseSLAMPipeline:
         y = np.zeros((nn, 8), np.float32)
         self._check(self.lib.se_hip_download_nodes(self._h, code.ctypes.data, side.ctypes.data, x.ctypes.data, y.ctypes.data))
         return code, side, x, y
+
+    # (shape of each output per point, dtype)
+    _QUERY_OUTPUTS = (("fine", (2,), np.float32), ("coarse", (2,), np.float32), ("interp", (), np.float32), ("grad", (3,), np.float32),
+                      ("status", (), np.uint8))
+
+    def query(self, points, fine: bool = True, coarse: bool = False, interp: bool = True, grad: bool = True, status: bool = True) -> dict:
+        """Batched map queries (se_hip_query_points, include/se_hip.h): for each point in metres, the reference's VolumeTemplate::get
+        (fine: (x, y) of the voxel, initValue() where no block), operator[] (coarse: (x, y), the deepest existing node's value where no
+        block), interp(p, x), grad(p, x), and status bits (1 in the volume, 2 block allocated, 4 interp reads allocated blocks only).
+        Returns a dict of the outputs asked for.
+          - numpy float32 [N, 3]: through the host entry; numpy arrays out.
+          - a torch tensor on this handle's GPU (float32, contiguous, [N, 3]): through the device entry; outputs are torch tensors on the same
+            device.  The caller's current torch stream is synchronised first (the points must be complete when the handle's stream reads
+            them), and the handle is synchronised before the tensors are returned.
+        Anything else raises TypeError / ValueError before any library call."""
+        want = {"fine": fine, "coarse": coarse, "interp": interp, "grad": grad, "status": status}
+        if not any(want.values()):
+            raise ValueError("query: no output requested")
+        if type(points) is np.ndarray:
+            if points.dtype != np.float32:
+                raise TypeError(f"query: points must be float32, got {points.dtype}")
+            if points.ndim != 2 or points.shape[1] != 3:
+                raise ValueError(f"query: points must have shape [N, 3], got {list(points.shape)}")
+            pts = np.ascontiguousarray(points)
+            n = pts.shape[0]
+            res = {k: np.empty((n,) + shp, dt) for k, shp, dt in self._QUERY_OUTPUTS if want[k]}
+            out = _QueryOut(*(res[k].ctypes.data if k in res else None for k, _, _ in self._QUERY_OUTPUTS))
+            self._check(self.lib.se_hip_query_points_host(self._h, pts.ctypes.data if n else None, n, C.byref(out)))
+            return res
+        torch = _torch_module(points)
+        if torch is None:
+            raise TypeError(f"query: points must be a numpy float32 array or a torch tensor on the GPU, got {type(points).__name__}")
+        if points.dtype != torch.float32:
+            raise TypeError(f"query: points must be float32, got {points.dtype}")
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError(f"query: points must have shape [N, 3], got {list(points.shape)}")
+        if not points.is_contiguous():
+            raise ValueError("query: points must be contiguous")
+        if points.device.type != "cuda" or (self._device is not None and points.device.index != self._device):
+            raise ValueError(f"query: points must be on this handle's GPU (cuda:{self._device}), got {points.device}")
+        n = int(points.shape[0])
+        dt = {np.float32: torch.float32, np.uint8: torch.uint8}
+        res = {k: torch.empty((n,) + shp, dtype=dt[npdt], device=points.device) for k, shp, npdt in self._QUERY_OUTPUTS if want[k]}
+        out = _QueryOut(*(res[k].data_ptr() if k in res else None for k, _, _ in self._QUERY_OUTPUTS))
+        torch.cuda.current_stream(points.device).synchronize()
+        self._check(self.lib.se_hip_query_points(self._h, points.data_ptr() if n else None, n, C.byref(out)))
+        self.sync()
+        return res
 
     def save(self, filename: str):
         """Octree::save of the reference (octree.hpp:898-914): same byte layout, entries sorted by key."""
