@@ -167,9 +167,6 @@ __device__ __forceinline__ uint32_t leaf_index(const DevMap& m, int bx, int by, 
   const int l = m.leaf_level;
   return m.leaf_off + (((((uint32_t)bz << l) | (uint32_t)by) << l) | (uint32_t)bx);
 }
-__device__ __forceinline__ uint32_t tab_index_packed(const DevMap& m, int l, uint32_t p) {
-  return m.off[l] + (((((p >> 20) & 1023u) << l) | ((p >> 10) & 1023u)) << l | (p & 1023u));
-}
 // Morton code of an octant position (<= 10 bits per axis), x lowest
 __device__ __forceinline__ uint32_t morton30(int x, int y, int z) {
   return (uint32_t)(se_expand21_d((unsigned long long)x) | (se_expand21_d((unsigned long long)y) << 1) | (se_expand21_d((unsigned long long)z) << 2));

@@ -21,9 +21,6 @@
 #define SE_TILE_W 8     // raycast: a wave covers a SE_TILE_W x SE_TILE_H pixel tile (product 64)
 #define SE_TILE_H 8
 #endif
-#ifndef SE_FUSED_RAY_PRIO
-#define SE_FUSED_RAY_PRIO 1   // k_raycast_scan at <= 512^3: raycast waves start at issue priority 1 instead of 0 (A/B: profiles/r04x_fused_ray_prio_ab.log)
-#endif
 #define SE_SPEC_OF 8  // OFusion march: samples fetched per memory round trip
 #ifndef SE_COST_BATCH
 #define SE_COST_BATCH 5   // raycast scheduling: cost of a tile = trips of its slowest ray + SE_COST_BATCH * its march batches (fitted against per-wave clocks in r02)
@@ -37,15 +34,9 @@
 // 1-3 k per frame at 1024^3.  The lanes of a wave that reach the same insertion point together (`mine` = this lane takes a slot; any divergent context:
 // the ballot sees the lanes that are active here) therefore share ONE atomic: the first of them adds their number, every lane takes base + its rank among
 // them (mbcnt).  Which lane gets which slot was never specified (pool order is the reference's race too, memory_pool.hpp:71); sets are unchanged.
-#ifndef SE_WAVE_AGG
-#define SE_WAVE_AGG 1      // 0: one atomic per lane (the r05 form; A/B: profiles/r06a)
-#endif
-#ifndef SE_DEFER_MARK
-#define SE_DEFER_MARK 1    // 0: beam-start marks in place even when the occupancy bits are deferred (the r05 form); 2: no marks at all (scan bisect; needs SE_HIP_BEAM=0 SE_HIP_OF_LEAP=0)
-#endif
+// r05 took one atomic per lane (A/B: profiles/r06a).
 template <typename T>
 __device__ __forceinline__ T se_wave_take(T* counter, bool mine) {
-  if (!SE_WAVE_AGG) return mine ? atomicAdd(counter, (T)1) : (T)0;
   const unsigned long long wm = __ballot(mine);
   if (!mine) return (T)0;
   const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(wm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)wm, 0u));
@@ -139,7 +130,7 @@ __device__ __forceinline__ bool se_insert_octant(const DevMap& m, int level, int
         m.bactive[slot] = 1;  // allocate_level: active(true), octree.hpp:841
         occ_set(m, level, x, y, z);
         { const uint32_t lin = block_linear(m, x, y, z); atomicOr(&m.lbits[lin >> 5], 1u << (lin & 31u)); }   // (never deferred: a reader that sees the bit early finds PENDING or a brick of initValue())
-        if (SE_DEFER_MARK == 0 || (SE_DEFER_MARK == 1 && !m.defer_mark)) se_mark_coarse(m, x, y, z);
+        if (!m.defer_mark) se_mark_coarse(m, x, y, z);
         atomicExch(e, slot + 1u);
       }
     }
@@ -468,7 +459,7 @@ __device__ __forceinline__ void se_occ_commit(const DevMap& m, const OccLists L,
       const int sh = m.max_level - level;
       int x = (int)(se_compact21(code) >> sh), y = (int)(se_compact21(code >> 1) >> sh), z = (int)(se_compact21(code >> 2) >> sh);
       if ((unsigned)x >= (1u << level) || (unsigned)y >= (1u << level) || (unsigned)z >= (1u << level)) continue;
-      if (SE_DEFER_MARK == 1 && level == m.leaf_level) se_mark_coarse(m, x, y, z);   // the beam-start bitmaps of a deferred insertion (se_insert_octant)
+      if (level == m.leaf_level) se_mark_coarse(m, x, y, z);   // the beam-start bitmaps of a deferred insertion (se_insert_octant)
       for (int l = level; l >= 1; --l) {
         const uint32_t c = occ_code(l, x, y, z);
         atomicOr(&m.occ[c >> 5], 1u << (c & 31u));
@@ -1130,19 +1121,6 @@ __device__ __forceinline__ FieldConst se_field_const(const DevMap& m) {
   return f;
 }
 
-// slot+1 of the block holding voxel (x,y,z); 0 if outside the volume or (pooled mode) not allocated.
-// Dense mode needs no memory access: every brick of the grid exists and unallocated ones hold initValue().
-template <bool DENSE>
-__device__ __forceinline__ uint32_t se_block_of(const DevMap& m, int x, int y, int z, BlkCache& c) {
-  if (!in_volume(m, x, y, z)) return 0u;
-  const int bx = x >> 3, by = y >> 3, bz = z >> 3;
-  if (DENSE) return block_linear(m, bx, by, bz) + 1u;
-  if (bx == c.bx && by == c.by && bz == c.bz) return c.e;
-  uint32_t e = m.tab[leaf_index(m, bx, by, bz)];
-  e = e == SE_PENDING ? 0u : e;   // (see se_block_entry)
-  c.bx = bx; c.by = by; c.bz = bz; c.e = e;
-  return e;
-}
 __device__ __forceinline__ size_t se_voxel_index(uint32_t e, int x, int y, int z) {
   return (size_t)(e - 1u) * SE_BRICK_STRIDE + (size_t)((x & 7) + ((y & 7) << 3) + ((z & 7) << 6));
 }
@@ -1227,47 +1205,6 @@ __device__ __forceinline__ AxisTerm se_axis_y(const DevMap& m, int y) { return {
 __device__ __forceinline__ AxisTerm se_axis_z(const DevMap& m, int z) { return {(uint32_t)(z >> 3) << (2 * m.leaf_level), (uint32_t)(z & 7) << 6}; }
 __device__ __forceinline__ size_t se_axis_index(AxisTerm a, AxisTerm b, AxisTerm c) {
   return (size_t)(a.blk + b.blk + c.blk) * SE_BRICK_STRIDE + (size_t)(a.loc + b.loc + c.loc);
-}
-
-// Dense grid: the address of every corner of an interpolation cell follows from the position alone, so
-// the SDF march can fetch the corners of a sample together with the sample itself.  Same cell
-// arithmetic as se_interp; the block of corner k is ((lx + (k & 1)) >> 3, ...), the block gather_points
-// picks in every cross case.
-struct InterpCell { float fx, fy, fz, missing; uint32_t ok; };
-__device__ __forceinline__ InterpCell se_interp_cell_dense(const DevMap& m, const FieldConst fc, f3 pos, size_t vi[8]) {
-  const float flx = floorf(pos.x), fly = floorf(pos.y), flz = floorf(pos.z);
-  const int bx = cvt_i32(flx), by = cvt_i32(fly), bz = cvt_i32(flz);
-  InterpCell cell;
-  cell.fx = pos.x - flx; cell.fy = pos.y - fly; cell.fz = pos.z - flz;
-  const int lx = max(bx, 0), ly = max(by, 0), lz = max(bz, 0);
-  const bool cx = (lx & 7) == 7, cy = (ly & 7) == 7, cz = (lz & 7) == 7;
-  cell.missing = (cx && cy && cz) ? fc.init_x : fc.empty_x;
-  cell.ok = 0u;
-  const int nb = m.size >> 3;
-  const int top = m.size - 1;
-  if (lx < top && ly < top && lz < top) {   // the whole cell inside the volume: per-axis terms (see se_axis_index)
-    const AxisTerm X[2] = {se_axis_x(lx), se_axis_x(lx + 1)}, Y[2] = {se_axis_y(m, ly), se_axis_y(m, ly + 1)}, Z[2] = {se_axis_z(m, lz), se_axis_z(m, lz + 1)};
-#pragma unroll
-    for (int k = 0; k < 8; ++k) vi[k] = se_axis_index(X[k & 1], Y[(k >> 1) & 1], Z[k >> 2]);
-    cell.ok = 0xFFu;
-    return cell;
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int x = lx + (k & 1), y = ly + ((k >> 1) & 1), z = lz + (k >> 2);
-    const bool ok = (unsigned)(x >> 3) < (unsigned)nb && (unsigned)(y >> 3) < (unsigned)nb && (unsigned)(z >> 3) < (unsigned)nb;
-    vi[k] = ok ? se_voxel_index(block_linear(m, x >> 3, y >> 3, z >> 3) + 1u, x, y, z) : 0;
-    cell.ok |= ok ? (1u << k) : 0u;
-  }
-  return cell;
-}
-__device__ __forceinline__ float se_interp_blend(const InterpCell& c, const float v[8]) {
-  float p[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) p[k] = ((c.ok >> k) & 1u) ? v[k] : c.missing;
-  const float fx = c.fx, fy = c.fy, fz = c.fz;
-  return (((p[0] * (1 - fx) + p[1] * fx) * (1 - fy) + (p[2] * (1 - fx) + p[3] * fx) * fy) * (1 - fz) +
-          ((p[4] * (1 - fx) + p[5] * fx) * (1 - fy) + (p[6] * (1 - fx) + p[7] * fx) * fy) * fz);
 }
 
 // Octree::grad (octree.hpp:652-737), same term order.  The 48 get() calls of the reference touch
@@ -1611,16 +1548,11 @@ __device__ __forceinline__ RaySpan se_first_leaf_lite(const DevMap& m, const Ray
   // at 2048^3 -- the load is needed one trip later, which a wave alone on its SIMD reaches long before the data; profiles/r06c_groups_ab.log)
   // (r06, measured: for the > 512^3 instantiations the compiler turns this select of two loads into ONE load of a selected address -- a FLAT load, which counts
   // on both memory counters, so every trip begins with s_waitcnt vmcnt(0) lgkmcnt(0).  Forcing two loads -- the LDS value pinned by an empty asm, or the global
-  // arm as a wavefront-scope atomic load (SE_SIB_SPLIT) -- was slower, not faster: k_raycast 68.4 -> 70.0 us at 1024^3, the last waves' search phase 36 -> 40 us,
+  // arm as a wavefront-scope atomic load -- was slower, not faster: k_raycast 68.4 -> 70.0 us at 1024^3, the last waves' search phase 36 -> 40 us,
   // because the pinned LDS read is waited for at once instead of at the top of the next trip; profiles/r06f_flatfix_ab.log)
-#ifndef SE_SIB_SPLIT
-#define SE_SIB_SPLIT 0
-#endif
   auto sib_of = [&](uint32_t P) -> uint32_t {
-    if (SE_SIB_SPLIT && !SHALLOW && !(P < staged_parents)) return (uint32_t)__hip_atomic_load(occ_bytes + P, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
     return (SHALLOW || P < staged_parents) ? (uint32_t)s_occ8[P] : (uint32_t)occ_bytes[P];
   };
-#define SE_SIB_OF(P) sib_of(P)
   uint32_t sib = s_occ8[1];   // the root's children: word 0 of the occupancy bits is always staged
   int guard = 0;
   const int max_trips = (!live || redo) ? 0 : 4096;
@@ -1648,7 +1580,7 @@ __device__ __forceinline__ RaySpan se_first_leaf_lite(const DevMap& m, const Ray
         sib = (uint32_t)(gp_bits >> ((parent & 7u) << 3)) & 0xFFu;
       } else {
         if (scale == a.min_scale + 1) { gp_code = parent; gp_bits = *(const unsigned long long*)(occ_bytes + ((size_t)parent << 3)); }
-        sib = SE_SIB_OF(parent);
+        sib = sib_of(parent);
       }
     } else {
       // advance_ray (ray_iterator.hpp:116-167)
@@ -1668,12 +1600,11 @@ __device__ __forceinline__ RaySpan se_first_leaf_lite(const DevMap& m, const Ray
           pos.x = __uint_as_float(__float_as_uint(pos.x) & keep);
           pos.y = __uint_as_float(__float_as_uint(pos.y) & keep);
           pos.z = __uint_as_float(__float_as_uint(pos.z) & keep);
-          sib = SE_SIB_OF(parent);
+          sib = sib_of(parent);
         }
       }
     }
   }
-#undef SE_SIB_OF
   if (jumped && t_min == t_start) redo = true;
   return {t_min * m.dim, tmax_m, guard};
 }
@@ -1701,14 +1632,8 @@ struct RayCounters { unsigned long long n_get, n_interp; unsigned n_batch; };
 //    that turns out to need them without having them pays one extra round trip (se_interp), results unchanged;
 //  * `(double)f_tt <= 0.1` is `f_tt < 0.1f` (0.1f is the smallest float above 0.1): no double-precision compare.
 #ifndef SE_MARCH_SKIP
-#define SE_MARCH_SKIP 4    // SDF march in unobserved space: positions asked of the leaf bitmap per round trip (se_march_skip); 0 = off.  Measured 0 / 4 / 8
+#define SE_MARCH_SKIP 4    // SDF march in unobserved space: positions asked of the leaf bitmap per round trip (se_march_skip).  Measured off / 4 / 8
                            // (profiles/r04p_march_skip_ab.log): 59.8 / 59.8 / 61.6 us per frame at 512^3, 193.8 / 188.4 / 189.5 at 1024^3, stress 69.7 / 68.6 / 71.3
-#endif
-#ifndef SE_POOLED_CELL
-#define SE_POOLED_CELL 1   // pooled SDF march: the interpolation cell of sample 0 fetched with the batch when it lies inside the sample's brick; 0 = off (A/B)
-#endif
-#ifndef SE_MARCH_PROBE
-#define SE_MARCH_PROBE 1   // dense maps > 512^3: leaf-bitmap probe in front of brick reads while the march is in unobserved space (se_cast_ray_sdf_lean)
 #endif
 template <bool O32> struct SeDense;
 template <> struct SeDense<true> {     // byte-offset terms, 32 bit
@@ -1812,7 +1737,6 @@ __device__ __forceinline__ f3 se_grad_lean(const DevMap& m, const FieldConst fc,
 // same frame is unchanged; the same out of line: 72 us and 32 B of scratch.  profiles/r05al_skip_long_ab.log, r05ap_skip_long2_ab.log)
 template <bool STATS>
 __device__ __forceinline__ bool se_march_skip(const DevMap& m, const RayArgs& a, f3 dir, float tfar, f3& position, float& t, RayCounters& rc) {
-#if SE_MARCH_SKIP > 0
   const f3 sd = f3_scale(a.largestep, dir);
   f3 q[SE_MARCH_SKIP];
   uint32_t lin[SE_MARCH_SKIP], w[SE_MARCH_SKIP];
@@ -1840,7 +1764,6 @@ __device__ __forceinline__ bool se_march_skip(const DevMap& m, const RayArgs& a,
       t += a.largestep;
     }
   }
-#endif
   return false;
 }
 // one get(): voxel coordinates, inside-the-volume flag and index of the sample at q (metres)
@@ -1881,7 +1804,7 @@ __device__ __forceinline__ void se_cast_ray_sdf_lean(const DevMap& m, const RayA
   bool unobs = false;      // the last consumed sample had weight 0 (unobserved space)
   for (int guard = 0; t < tfar && !done && guard < 65536; ++guard) {
     ++rc.n_batch;
-    if (SE_MARCH_SKIP > 0 && unobs) {   // (S == stepsize == largestep in this state)
+    if (unobs) {   // (S == stepsize == largestep in this state)
       if (se_march_skip<STATS>(m, a, dir, tfar, position, t, rc)) break;
       if (!(t < tfar)) break;
     }
@@ -1900,7 +1823,7 @@ __device__ __forceinline__ void se_cast_ray_sdf_lean(const DevMap& m, const RayA
     SeSample<O32> s0 = se_sample_lean<O32>(m, a, q0), s1 = se_sample_lean<O32>(m, a, q1);
     float x0, y0, x1, y1;
     bool probed = false;
-    if constexpr (SE_MARCH_PROBE && !O32) {
+    if constexpr (!O32) {
      if (unobs) {
       probed = true;
       // Volumes > 512^3: the march is latency-bound on cold brick lines, and 43 % of its samples lie in blocks that were
@@ -2011,7 +1934,7 @@ __device__ __forceinline__ void se_cast_ray_sdf_pooled(const DevMap& m, const Ra
   SePCache pc = {0xFFFFFFFFu, 0u};
   for (int guard = 0; t < tfar && !done && guard < 65536; ++guard) {
     ++rc.n_batch;
-    if (SE_MARCH_SKIP > 0 && unobs) {
+    if (unobs) {
       if (se_march_skip<STATS>(m, a, dir, tfar, position, t, rc)) break;
       if (!(t < tfar)) break;
     }
@@ -2027,7 +1950,7 @@ __device__ __forceinline__ void se_cast_ray_sdf_pooled(const DevMap& m, const Ra
     // same blend as se_interp_generic; one round trip instead of two for the sample that decides the step
     bool have0 = false;
     float cv0[8], cfx = 0.f, cfy = 0.f, cfz = 0.f;
-    if (SE_POOLED_CELL && band && s0.e) {
+    if (band && s0.e) {
       const f3 pv = f3_scale(a.inv_voxel, q0);
       const float flx = floorf(pv.x), fly = floorf(pv.y), flz = floorf(pv.z);
       const int lx = max(cvt_i32(flx), 0), ly = max(cvt_i32(fly), 0), lz = max(cvt_i32(flz), 0);
@@ -2089,9 +2012,6 @@ __device__ __forceinline__ void se_cast_ray_sdf_pooled(const DevMap& m, const Ra
 // clear; the samples up to one step short of the last clear check point are consumed by K additions and f_t = f_tt.  Conservative: a bit set concurrently
 // by the next frame's scan shortens the leap, and a block that appears behind the test holds initValue() in every voxel (the argument of
 // se_march_skip).  Returns the number of samples consumed; `t` is advanced exactly as the loop would have advanced it.
-#ifndef SE_OF_LEAP
-#define SE_OF_LEAP 1
-#endif
 // 0 if the dilated block grid is clear at q (no block within one block of it), non-zero if not or if q lies outside the volume
 __device__ __forceinline__ uint32_t se_leap_word(const RayArgs& a, f3 q) {
   const int F = a.leap_level;
@@ -2147,7 +2067,7 @@ __device__ __forceinline__ void se_cast_ray_of_pooled(const DevMap& m, const Ray
   SePCache pc = {0xFFFFFFFFu, 0u};
   for (int guard = 0; t < tfar && !done && guard < 65536; ++guard) {
     ++rc.n_batch;
-    if (SE_OF_LEAP && quiet && a.leap_bits && t >= leap_hold) {
+    if (quiet && a.leap_bits && t >= leap_hold) {
       if (se_of_leap(a, org, dir, tfar, t, leap_hold) > 0) { f_t = f_tt; if (!(t < tfar)) break; }
     }
     float tt[SE_SPEC_OF];
@@ -2159,7 +2079,7 @@ __device__ __forceinline__ void se_cast_ray_of_pooled(const DevMap& m, const Ray
     for (int i = 1; i < SE_SPEC_OF; ++i) tt[i] = tt[i - 1] + stepsize;
 #pragma unroll
     for (int i = 0; i < SE_SPEC_OF; ++i) { q[i] = f3_add(org, f3_scale_r(dir, tt[i])); sm[i] = se_sample_pooled<false>(m, a, q[i], pc, false); }
-    quiet = (SE_OF_LEAP && a.leap_bits ? se_leap_word(a, q[SE_SPEC_OF - 1]) : 1u) == 0u;   // (see se_cast_ray_of_lean)
+    quiet = (a.leap_bits ? se_leap_word(a, q[SE_SPEC_OF - 1]) : 1u) == 0u;   // (see se_cast_ray_of_lean)
 #pragma unroll
     for (int i = 0; i < SE_SPEC_OF; ++i) { const size_t vi = se_pooled_index(sm[i]); qx[i] = m.vx[vi]; qy[i] = m.vx[vi + 512]; }
     bool stop = false;
@@ -2214,7 +2134,7 @@ __device__ __forceinline__ void se_cast_ray_of_lean(const DevMap& m, const RayAr
   float leap_hold = 0.f;              // no leap test before t has reached this value (the check point the last test found blocked)
   for (int guard = 0; t < tfar && !done && guard < 65536; ++guard) {
     ++rc.n_batch;
-    if (SE_OF_LEAP && quiet && a.leap_bits && t >= leap_hold) {
+    if (quiet && a.leap_bits && t >= leap_hold) {
       if (se_of_leap(a, org, dir, tfar, t, leap_hold) > 0) { f_t = f_tt; if (!(t < tfar)) break; }
     }
     float tt[SE_SPEC_OF];
@@ -2228,7 +2148,7 @@ __device__ __forceinline__ void se_cast_ray_of_lean(const DevMap& m, const RayAr
     for (int i = 0; i < SE_SPEC_OF; ++i) { q[i] = f3_add(org, f3_scale_r(dir, tt[i])); sm[i] = se_sample_lean<O32>(m, a, q[i]); }
     // (the leap is only tried from block-free space: the batch's last sample asks the dilated grid along with the values -- a quiet batch inside
     // allocated, unobserved blocks would otherwise pay a test that cannot succeed, batch after batch: r05an)
-    const uint32_t lw = SE_OF_LEAP && a.leap_bits ? se_leap_word(a, q[SE_SPEC_OF - 1]) : 1u;
+    const uint32_t lw = a.leap_bits ? se_leap_word(a, q[SE_SPEC_OF - 1]) : 1u;
 #pragma unroll
     for (int i = 0; i < SE_SPEC_OF; ++i) { qx[i] = A::ldx(m, sm[i].vi); qy[i] = A::ldy(m, sm[i].vi); }
     quiet = lw == 0u;
@@ -2290,12 +2210,10 @@ __device__ __forceinline__ float se_beam_start(const DevMap& m, const RayArgs& a
   const int C = m.clevel;
   const int cx = se_cvt_flr(p.x * a.beam_inv_cell), cy = se_cvt_flr(p.y * a.beam_inv_cell), cz = se_cvt_flr(p.z * a.beam_inv_cell);
   // A sample outside the volume sees no blocks -- unless it lies in the one-cell shell around it, within a cell of whatever is allocated on that face:
-  // the shell takes the dilated bit of the boundary cell it touches (which covers every cell within one of the sample's own)
-#ifndef SE_BEAM_SHELL
-#define SE_BEAM_SHELL 1    // 0: samples outside the volume count as clear (the r05 form; A/B)
-#endif
+  // the shell takes the dilated bit of the boundary cell it touches (which covers every cell within one of the sample's own; ADVICE r05: r05 counted
+  // every sample outside the volume as clear)
   const int nC = 1 << C;
-  const bool in = SE_BEAM_SHELL ? ((uint32_t)(cx + 1) <= (uint32_t)nC && (uint32_t)(cy + 1) <= (uint32_t)nC && (uint32_t)(cz + 1) <= (uint32_t)nC) : ((uint32_t)(cx | cy | cz) < (uint32_t)nC);
+  const bool in = (uint32_t)(cx + 1) <= (uint32_t)nC && (uint32_t)(cy + 1) <= (uint32_t)nC && (uint32_t)(cz + 1) <= (uint32_t)nC;
   const uint32_t idx = in ? (((uint32_t)min(max(cz, 0), nC - 1) << (2 * C)) | ((uint32_t)min(max(cy, 0), nC - 1) << C) | (uint32_t)min(max(cx, 0), nC - 1)) : 0u;
   const uint32_t w = m.cbits[idx >> 5];
   const bool occupied = in && ((w >> (idx & 31u)) & 1u);
@@ -2312,7 +2230,7 @@ __device__ __forceinline__ float se_beam_start(const DevMap& m, const RayArgs& a
     const int F = se_flevel(m);
     const int fx = se_cvt_flr(pf.x * a.beam_inv_cellf), fy = se_cvt_flr(pf.y * a.beam_inv_cellf), fz = se_cvt_flr(pf.z * a.beam_inv_cellf);
     const int nF = 1 << F;
-    const bool inf = SE_BEAM_SHELL ? ((uint32_t)(fx + 1) <= (uint32_t)nF && (uint32_t)(fy + 1) <= (uint32_t)nF && (uint32_t)(fz + 1) <= (uint32_t)nF) : ((uint32_t)(fx | fy | fz) < (uint32_t)nF);   // (the shell: as above)
+    const bool inf = (uint32_t)(fx + 1) <= (uint32_t)nF && (uint32_t)(fy + 1) <= (uint32_t)nF && (uint32_t)(fz + 1) <= (uint32_t)nF;   // (the shell: as above)
     const uint32_t fidx = inf ? (((uint32_t)min(max(fz, 0), nF - 1) << (2 * F)) | ((uint32_t)min(max(fy, 0), nF - 1) << F) | (uint32_t)min(max(fx, 0), nF - 1)) : 0u;
     const uint32_t fw = m.fbits[fidx >> 5];
     const bool clear2 = !(inf && ((fw >> (fidx & 31u)) & 1u)) && ((tf + 0.5f * a.beam_dt2) * rad + 0.5f * a.beam_dt2 <= 0.9f * a.beam_cellf);
@@ -2514,7 +2432,7 @@ __global__ __launch_bounds__(SE_WG_RAY) SE_RAY_OCC void k_raycast_scan(DevMap m,
     // the raycast's waves are the launch's critical path: they start at issue priority 1, the scan's (priority 0) take the slots they leave.  Same box,
     // two repetitions (profiles/r04x_fused_ray_prio_ab.log): +1.1 % frames/s at 512^3, +2 % OFusion, 0 on the stress stream, -1 % at 1024^3 (there the scan,
     // 2x as long, ends the launch when it is held back) -> volumes whose every level is staged (<= 512^3) only
-    if (SE_FUSED_RAY_PRIO && SHALLOW) __builtin_amdgcn_s_setprio(1);
+    if (SHALLOW) __builtin_amdgcn_s_setprio(1);
     se_raycast_wg<OFUSION, false, DENSE, SHALLOW, O32>(m, a, vertex, normal, smem, bid);
     return;
   }

@@ -246,90 +246,15 @@ __host__ __device__ inline void se_sincos_f32(float xf, float* s, float* c) {
   *s = (float)sv; *c = (float)cv;
 }
 
-// updatePoseKernel's arithmetic (tracking.cpp:42-65, 304-318): makeJTJ + LLT solve.  Eigen::LLT is defined as the unblocked
-// Cholesky with left-to-right inner sums (oracle: solve6).
-__device__ inline bool se_solve6(const float* vals /*b[6], upper triangle[21]*/, float x[6]) {
-  float Cm[6][6], L[6][6];
-  int k = 6;
-#pragma unroll
-  for (int r = 0; r < 6; ++r)
-#pragma unroll
-    for (int c = r; c < 6; ++c) { Cm[r][c] = vals[k]; Cm[c][r] = vals[k]; ++k; }
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    float d = Cm[j][j];
-    if (j > 0) { float sn = 0; for (int q = 0; q < j; ++q) sn += L[j][q] * L[j][q]; d -= sn; }
-    if (!(d > 0.f)) { for (int i = 0; i < 6; ++i) x[i] = 0.f; return false; }
-    d = sqrtf(d);
-    L[j][j] = d;
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      float v = Cm[i][j];
-      if (j > 0) { float sp = 0; for (int q = 0; q < j; ++q) sp += L[i][q] * L[j][q]; v -= sp; }
-      L[i][j] = v / d;
-    }
-  }
-  float yv[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) { float v = vals[i]; for (int q = 0; q < i; ++q) v -= L[i][q] * yv[q]; yv[i] = v / L[i][i]; }
-#pragma unroll
-  for (int i = 5; i >= 0; --i) { float v = yv[i]; for (int q = i + 1; q < 6; ++q) v -= L[q][i] * x[q]; x[i] = v / L[i][i]; }
-  return true;
-}
-// Sophus::SE3f::exp (tracking.cpp:310), Sophus 1.0 closed form with epsilon 1e-5f (oracle: se3_exp); T = row-major 4x4
-__device__ inline void se_se3_exp(const float a[6], float T[16]) {
-  const float eps = 1e-5f;
-  const float ox = a[3], oy = a[4], oz = a[5];
-  const float theta_sq = (ox * ox + oy * oy) + oz * oz, theta = sqrtf(theta_sq), half_theta = 0.5f * theta;
-  float imag_factor, real_factor;
-  if (theta_sq < eps * eps) {
-    const float theta_po4 = theta_sq * theta_sq;
-    imag_factor = 0.5f - (1.0f / 48.0f) * theta_sq + (1.0f / 3840.0f) * theta_po4;
-    real_factor = 1.f - (1.0f / 8.0f) * theta_sq + (1.0f / 384.0f) * theta_po4;
-  } else {
-    float sh, ch;
-    se_sincos_f32(half_theta, &sh, &ch);
-    imag_factor = sh / theta;
-    real_factor = ch;
-  }
-  float qw = real_factor, qx = imag_factor * ox, qy = imag_factor * oy, qz = imag_factor * oz;
-  const float qn = sqrtf(((qw * qw + qx * qx) + qy * qy) + qz * qz);
-  qw /= qn; qx /= qn; qy /= qn; qz /= qn;
-  const float tx = 2.f * qx, ty = 2.f * qy, tz = 2.f * qz;
-  const float twx = tx * qw, twy = ty * qw, twz = tz * qw, txx = tx * qx, txy = ty * qx, txz = tz * qx, tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
-  const float R[3][3] = {{1.f - (tyy + tzz), txy - twz, txz + twy}, {txy + twz, 1.f - (txx + tzz), tyz - twx}, {txz - twy, tyz + twx, 1.f - (txx + tyy)}};
-  float V[3][3];
-  if (theta < eps) {
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) V[i][j] = R[i][j];
-  } else {
-    const float Om[3][3] = {{0, -oz, oy}, {oz, 0, -ox}, {-oy, ox, 0}};
-    float Om2[3][3];
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j) Om2[i][j] = (Om[i][0] * Om[0][j] + Om[i][1] * Om[1][j]) + Om[i][2] * Om[2][j];
-    float st, ct;
-    se_sincos_f32(theta, &st, &ct);
-    const float ca = (1.f - ct) / theta_sq, cb = (theta - st) / (theta_sq * theta);
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j) V[i][j] = ((i == j ? 1.f : 0.f) + ca * Om[i][j]) + cb * Om2[i][j];
-  }
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) T[i * 4 + j] = R[i][j];
-    T[i * 4 + 3] = (V[i][0] * a[0] + V[i][1] * a[1]) + V[i][2] * a[2];
-  }
-  T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
-}
-
-// ---- the same arithmetic spread over the lanes of ONE wave (r04).  The single-lane versions above cost ~1 000 dependent VALU instructions (3 us) in
-// the prologue of every ICP launch.  Here all 64 lanes of wave 0 run the code; what is the same for every lane is computed redundantly (free on a SIMD),
-// and the pieces that are independent of each other go to different lanes: the rows of the Cholesky factor (lane r owns row r: one column step = one
-// multiply-add chain, ONE division), the two sincos calls, the four quaternion divisions, the sixteen entries of the pose product.  Every float operation
-// has the operands and the order it has in se_solve6 / se_se3_exp (sums left to right, true divisions, the same sqrtf): the results are bit-identical,
-// which tests/test_gpu_tracking.py checks against the oracle frame by frame.  SE_ICP_WAVE_SOLVE 0 = the single-lane code (A/B).
-#ifndef SE_ICP_WAVE_SOLVE
-#define SE_ICP_WAVE_SOLVE 1
-#endif
+// ---- updatePoseKernel's arithmetic (tracking.cpp:42-65, 304-318): makeJTJ + LLT solve and SE3 exp, spread over the lanes of ONE wave (r04).  Run on
+// one lane, it cost ~1 000 dependent VALU instructions (3 us) in the prologue of every ICP launch.  Here all 64 lanes of wave 0 run the code; what is the
+// same for every lane is computed redundantly (free on a SIMD), and the pieces that are independent of each other go to different lanes: the rows of the
+// Cholesky factor (lane r owns row r: one column step = one multiply-add chain, ONE division), the two sincos calls, the four quaternion divisions, the
+// sixteen entries of the pose product.  Every float operation has the operands and the order it has in the oracle's solve6 / se3_exp
+// (oracle/se_oracle.cpp: sums left to right, true divisions, the same sqrtf): the results are bit-identical, which tests/test_gpu_tracking.py checks
+// against the oracle frame by frame.
 __device__ __forceinline__ float se_lane(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
-// vals: b[6], upper triangle[21] (LDS); x: the solution, in every lane.  (Eigen::LLT as in se_solve6.)
+// vals: b[6], upper triangle[21] (LDS); x: the solution, in every lane.  (Eigen::LLT is defined as the unblocked Cholesky with left-to-right inner sums.)
 __device__ __forceinline__ void se_solve6_wave(const float* vals, float x[6], int lane) {
   const int r = lane < 6 ? lane : 5;     // (lanes 6..63 mirror lane 5: defined arithmetic, never read)
   float Lr[6], diag = 1.f;
@@ -383,7 +308,7 @@ __device__ __forceinline__ void se_solve6_wave(const float* vals, float x[6], in
     x[i] = u / dg[i];
   }
 }
-// se_se3_exp over a wave: T (rows 0..2; row 3 is 0 0 0 1) in every lane
+// Sophus::SE3f::exp (tracking.cpp:310), Sophus 1.0 closed form with epsilon 1e-5f, over a wave: T = row-major 4x4 (rows 0..2; row 3 is 0 0 0 1) in every lane
 __device__ __forceinline__ void se_se3_exp_wave(const float a[6], float T[16], int lane) {
   const float eps = 1e-5f;
   const float ox = a[3], oy = a[4], oz = a[5];
@@ -465,7 +390,6 @@ __device__ __forceinline__ void se_icp_finalize(IcpShared& sh, const float* __re
     sh.strip[0][t] = row0;
   }
   __syncthreads();
-#if SE_ICP_WAVE_SOLVE
   if (t < 64) {      // wave 0, every lane
     float x[6], D[16];
     se_solve6_wave(&sh.strip[0][1], x, t);
@@ -488,22 +412,6 @@ __device__ __forceinline__ void se_icp_finalize(IcpShared& sh, const float* __re
       sh.conv = sqrtf(xn) < icp_threshold ? 1 : 0;
     }
   }
-#else
-  if (t == 0) {
-    float x[6], D[16], N[16];
-    se_solve6(&sh.strip[0][1], x);
-    se_se3_exp(x, D);
-    // updatePoseKernel: pose = delta * pose (4x4 product, inner sums left to right)
-    for (int r = 0; r < 4; ++r)
-      for (int c = 0; c < 4; ++c)
-        N[r * 4 + c] = ((D[r * 4 + 0] * P[0 * 4 + c] + D[r * 4 + 1] * P[1 * 4 + c]) + D[r * 4 + 2] * P[2 * 4 + c]) + D[r * 4 + 3] * P[3 * 4 + c];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) sh.pose[q] = N[q];
-    float xn = 0.f;
-    for (int q = 0; q < 6; ++q) xn += x[q] * x[q];
-    sh.conv = sqrtf(xn) < icp_threshold ? 1 : 0;
-  }
-#endif
   __syncthreads();
 }
 // state[(j + 1) & 1] as iteration j-1's update leaves it (or a plain copy when that iteration did not run)
