@@ -1724,6 +1724,66 @@ __device__ __forceinline__ f3 se_grad_lean(const DevMap& m, const FieldConst fc,
          ((V[3][2][1] - V[1][2][1]) * (1 - fx) + (V[3][2][2] - V[1][2][2]) * fx) * fy) * fz;
   return g;
 }
+
+// leaf-grid entry (slot + 1) of block (bx, by, bz), 0 if it lies outside the volume or is not allocated.  Both layouts keep
+// the entry in tab[] (a dense brick grid also holds bricks of blocks that were never allocated: initValue() everywhere).
+__device__ __forceinline__ uint32_t se_query_block(const DevMap& m, int bx, int by, int bz) {
+  const int nb = m.size >> 3;
+  if (!((unsigned)bx < (unsigned)nb && (unsigned)by < (unsigned)nb && (unsigned)bz < (unsigned)nb)) return 0u;
+  const uint32_t e = m.tab[leaf_index(m, bx, by, bz)];
+  return e == SE_PENDING ? 0u : e;
+}
+
+// Octree::grad (octree.hpp:652-737) for a stencil that leaves the volume: every one of the 32 voxels is looked up on its own, a voxel outside the
+// volume or in a block that is not allocated reads initValue().x (Octree::get(x, y, z, cached) -> get_fine).  Same clamps, same term order as
+// se_grad_generic.
+__device__ __forceinline__ f3 se_grad_checked(const DevMap& m, const FieldConst fc, f3 pos) {
+  const float flx = floorf(pos.x), fly = floorf(pos.y), flz = floorf(pos.z);
+  const int bx = cvt_i32(flx), by = cvt_i32(fly), bz = cvt_i32(flz);
+  const float fx = pos.x - flx, fy = pos.y - fly, fz = pos.z - flz;
+  const int hi = m.size - 1;
+  const int X[4] = {max(bx - 1, 0), max(bx, 0), min(bx + 1, hi), min(bx + 2, hi)};
+  const int Y[4] = {max(by - 1, 0), max(by, 0), min(by + 1, hi), min(by + 2, hi)};
+  const int Z[4] = {max(bz - 1, 0), max(bz, 0), min(bz + 1, hi), min(bz + 2, hi)};
+  float V[4][4][4];
+#pragma unroll
+  for (int zi = 0; zi < 4; ++zi)
+#pragma unroll
+    for (int yi = 0; yi < 4; ++yi)
+#pragma unroll
+      for (int xi = 0; xi < 4; ++xi) {
+        const int central = (xi == 1 || xi == 2) + (yi == 1 || yi == 2) + (zi == 1 || zi == 2);
+        if (central < 2) continue;
+        const int x = X[xi], y = Y[yi], z = Z[zi];
+        const uint32_t e = in_volume(m, x, y, z) ? se_query_block(m, x >> 3, y >> 3, z >> 3) : 0u;
+        V[zi][yi][xi] = e ? m.vx[se_voxel_index(e, x, y, z)] : fc.init_x;
+      }
+  f3 g;
+  g.x = (((V[1][1][2] - V[1][1][0]) * (1 - fx) + (V[1][1][3] - V[1][1][1]) * fx) * (1 - fy) +
+         ((V[1][2][2] - V[1][2][0]) * (1 - fx) + (V[1][2][3] - V[1][2][1]) * fx) * fy) * (1 - fz) +
+        (((V[2][1][2] - V[2][1][0]) * (1 - fx) + (V[2][1][3] - V[2][1][1]) * fx) * (1 - fy) +
+         ((V[2][2][2] - V[2][2][0]) * (1 - fx) + (V[2][2][3] - V[2][2][1]) * fx) * fy) * fz;
+  g.y = (((V[1][2][1] - V[1][0][1]) * (1 - fx) + (V[1][2][2] - V[1][0][2]) * fx) * (1 - fy) +
+         ((V[1][3][1] - V[1][1][1]) * (1 - fx) + (V[1][3][2] - V[1][1][2]) * fx) * fy) * (1 - fz) +
+        (((V[2][2][1] - V[2][0][1]) * (1 - fx) + (V[2][2][2] - V[2][0][2]) * fx) * (1 - fy) +
+         ((V[2][3][1] - V[2][1][1]) * (1 - fx) + (V[2][3][2] - V[2][1][2]) * fx) * fy) * fz;
+  g.z = (((V[2][1][1] - V[0][1][1]) * (1 - fx) + (V[2][1][2] - V[0][1][2]) * fx) * (1 - fy) +
+         ((V[2][2][1] - V[0][2][1]) * (1 - fx) + (V[2][2][2] - V[0][2][2]) * fx) * fy) * (1 - fz) +
+        (((V[3][1][1] - V[1][1][1]) * (1 - fx) + (V[3][1][2] - V[1][1][2]) * fx) * (1 - fy) +
+         ((V[3][2][1] - V[1][2][1]) * (1 - fx) + (V[3][2][2] - V[1][2][2]) * fx) * fy) * fz;
+  return g;  // the caller applies (0.5f * dim / size)
+}
+
+// The normal at a hit (raycastKernel / renderVolumeKernel: volume.grad(hit)).  A hit can lie up to a voxel beyond an upper face of the volume
+// (floor(q) = size: the reference's `lower` index max(base, 0) is not clamped there and reads initValue()), outside the band se_grad is exact in;
+// there every voxel of the stencil is read by itself.  (Seen from beyond the +x / +y / +z faces, tests/test_gpu_beam_shell.py.)
+template <bool DENSE, bool O32 = false>
+__device__ __forceinline__ f3 se_hit_grad(const DevMap& m, const FieldConst fc, f3 q, BlkCache& c) {
+  const int hi = m.size - 1;
+  const int bx = cvt_i32(floorf(q.x)), by = cvt_i32(floorf(q.y)), bz = cvt_i32(floorf(q.z));
+  if (!(bx >= -1 && bx <= hi && by >= -1 && by <= hi && bz >= -1 && bz <= hi)) return se_grad_checked(m, fc, q);
+  return DENSE ? se_grad_lean<O32>(m, fc, q, c) : se_grad<DENSE>(m, fc, q, c);
+}
 // Walking through unobserved space (r04).  While the last value had weight 0 the reference's march takes `largestep` after `largestep` until a get()
 // returns a weight again; 43 % of all samples of a frame are such steps, most of them in blocks that were never allocated, and each pair of them
 // was a dependent memory round trip.  The next SE_MARCH_SKIP positions -- formed by the same float additions the loop performs -- are asked of the
@@ -2210,10 +2270,11 @@ __device__ __forceinline__ float se_beam_start(const DevMap& m, const RayArgs& a
   const int C = m.clevel;
   const int cx = se_cvt_flr(p.x * a.beam_inv_cell), cy = se_cvt_flr(p.y * a.beam_inv_cell), cz = se_cvt_flr(p.z * a.beam_inv_cell);
   // A sample outside the volume sees no blocks -- unless it lies in the one-cell shell around it, within a cell of whatever is allocated on that face:
-  // the shell takes the dilated bit of the boundary cell it touches (which covers every cell within one of the sample's own; ADVICE r05: r05 counted
-  // every sample outside the volume as clear)
+  // the shell is cell -1 beyond a lower face and cell n beyond an upper one, on each axis, and the clamp below maps it to the boundary cell it touches,
+  // whose dilated bit covers every cell within one of the sample's own (r05 counted every sample outside the volume as clear; the shell
+  // beyond the upper faces was counted clear until tests/test_first_leaf_equivalence.py looked from there)
   const int nC = 1 << C;
-  const bool in = (uint32_t)(cx + 1) <= (uint32_t)nC && (uint32_t)(cy + 1) <= (uint32_t)nC && (uint32_t)(cz + 1) <= (uint32_t)nC;
+  const bool in = (uint32_t)(cx + 1) <= (uint32_t)(nC + 1) && (uint32_t)(cy + 1) <= (uint32_t)(nC + 1) && (uint32_t)(cz + 1) <= (uint32_t)(nC + 1);
   const uint32_t idx = in ? (((uint32_t)min(max(cz, 0), nC - 1) << (2 * C)) | ((uint32_t)min(max(cy, 0), nC - 1) << C) | (uint32_t)min(max(cx, 0), nC - 1)) : 0u;
   const uint32_t w = m.cbits[idx >> 5];
   const bool occupied = in && ((w >> (idx & 31u)) & 1u);
@@ -2230,7 +2291,7 @@ __device__ __forceinline__ float se_beam_start(const DevMap& m, const RayArgs& a
     const int F = se_flevel(m);
     const int fx = se_cvt_flr(pf.x * a.beam_inv_cellf), fy = se_cvt_flr(pf.y * a.beam_inv_cellf), fz = se_cvt_flr(pf.z * a.beam_inv_cellf);
     const int nF = 1 << F;
-    const bool inf = (uint32_t)(fx + 1) <= (uint32_t)nF && (uint32_t)(fy + 1) <= (uint32_t)nF && (uint32_t)(fz + 1) <= (uint32_t)nF;   // (the shell: as above)
+    const bool inf = (uint32_t)(fx + 1) <= (uint32_t)(nF + 1) && (uint32_t)(fy + 1) <= (uint32_t)(nF + 1) && (uint32_t)(fz + 1) <= (uint32_t)(nF + 1);   // (the shell: as above)
     const uint32_t fidx = inf ? (((uint32_t)min(max(fz, 0), nF - 1) << (2 * F)) | ((uint32_t)min(max(fy, 0), nF - 1) << F) | (uint32_t)min(max(fx, 0), nF - 1)) : 0u;
     const uint32_t fw = m.fbits[fidx >> 5];
     const bool clear2 = !(inf && ((fw >> (fidx & 31u)) & 1u)) && ((tf + 0.5f * a.beam_dt2) * rad + 0.5f * a.beam_dt2 <= 0.9f * a.beam_cellf);
@@ -2349,7 +2410,7 @@ __device__ __forceinline__ void se_raycast_wg(const DevMap& m, const RayArgs& a,
     if (hw > 0.f) {   // (hit.w() > 0.0)
       if (STATS) { ++n_hit; ++n_grad; }
       v[0] = hx; v[1] = hy; v[2] = hz;
-      const f3 g = DENSE ? se_grad_lean<O32>(m, fc, f3_scale(a.inv_voxel, {hx, hy, hz}), c) : se_grad<DENSE>(m, fc, f3_scale(a.inv_voxel, {hx, hy, hz}), c);
+      const f3 g = se_hit_grad<DENSE, O32>(m, fc, f3_scale(a.inv_voxel, {hx, hy, hz}), c);
       const f3 surfNorm = f3_scale(a.grad_scale, g);
       if (sqrtf(f3_sqnorm(surfNorm)) == 0) {
         n[0] = -2.f; n[1] = 0.f; n[2] = 0.f;  // INVALID (commons.h:71)
@@ -2545,7 +2606,7 @@ __global__ __launch_bounds__(SE_WG_RAY) void k_render_volume(DevMap m, RayArgs a
     if (sp.tcmin > 0.f) se_cast_ray<OFUSION, false, DENSE>(m, a, fc, org, dir, sp.tcmin, sp.tmax, c, hx, hy, hz, hw, rc);
     if (hw > 0) {
       test = {hx, hy, hz};
-      const f3 g = se_grad<DENSE>(m, fc, f3_scale(a.inv_voxel, test), c);
+      const f3 g = se_hit_grad<DENSE>(m, fc, f3_scale(a.inv_voxel, test), c);
       surfNorm = f3_scale(a.grad_scale, g);
       if (!OFUSION) surfNorm = f3_scale(-1.f, surfNorm);
     } else {

@@ -20,55 +20,6 @@
 
 struct QueryOut { float* fine; float* coarse; float* interp; float* grad; uint8_t* status; };
 
-// leaf-grid entry (slot + 1) of block (bx, by, bz), 0 if it lies outside the volume or is not allocated.  Both layouts keep
-// the entry in tab[] (a dense brick grid also holds bricks of blocks that were never allocated: initValue() everywhere).
-__device__ __forceinline__ uint32_t se_query_block(const DevMap& m, int bx, int by, int bz) {
-  const int nb = m.size >> 3;
-  if (!((unsigned)bx < (unsigned)nb && (unsigned)by < (unsigned)nb && (unsigned)bz < (unsigned)nb)) return 0u;
-  const uint32_t e = m.tab[leaf_index(m, bx, by, bz)];
-  return e == SE_PENDING ? 0u : e;
-}
-
-// Octree::grad (octree.hpp:652-737) for a stencil that leaves the volume: every one of the 32 voxels is looked up on its own, a voxel outside the
-// volume or in a block that is not allocated reads initValue().x (Octree::get(x, y, z, cached) -> get_fine).  Same clamps, same term order as
-// se_grad_generic.
-__device__ __forceinline__ f3 se_query_grad_checked(const DevMap& m, const FieldConst fc, f3 pos) {
-  const float flx = floorf(pos.x), fly = floorf(pos.y), flz = floorf(pos.z);
-  const int bx = cvt_i32(flx), by = cvt_i32(fly), bz = cvt_i32(flz);
-  const float fx = pos.x - flx, fy = pos.y - fly, fz = pos.z - flz;
-  const int hi = m.size - 1;
-  const int X[4] = {max(bx - 1, 0), max(bx, 0), min(bx + 1, hi), min(bx + 2, hi)};
-  const int Y[4] = {max(by - 1, 0), max(by, 0), min(by + 1, hi), min(by + 2, hi)};
-  const int Z[4] = {max(bz - 1, 0), max(bz, 0), min(bz + 1, hi), min(bz + 2, hi)};
-  float V[4][4][4];
-#pragma unroll
-  for (int zi = 0; zi < 4; ++zi)
-#pragma unroll
-    for (int yi = 0; yi < 4; ++yi)
-#pragma unroll
-      for (int xi = 0; xi < 4; ++xi) {
-        const int central = (xi == 1 || xi == 2) + (yi == 1 || yi == 2) + (zi == 1 || zi == 2);
-        if (central < 2) continue;
-        const int x = X[xi], y = Y[yi], z = Z[zi];
-        const uint32_t e = in_volume(m, x, y, z) ? se_query_block(m, x >> 3, y >> 3, z >> 3) : 0u;
-        V[zi][yi][xi] = e ? m.vx[se_voxel_index(e, x, y, z)] : fc.init_x;
-      }
-  f3 g;
-  g.x = (((V[1][1][2] - V[1][1][0]) * (1 - fx) + (V[1][1][3] - V[1][1][1]) * fx) * (1 - fy) +
-         ((V[1][2][2] - V[1][2][0]) * (1 - fx) + (V[1][2][3] - V[1][2][1]) * fx) * fy) * (1 - fz) +
-        (((V[2][1][2] - V[2][1][0]) * (1 - fx) + (V[2][1][3] - V[2][1][1]) * fx) * (1 - fy) +
-         ((V[2][2][2] - V[2][2][0]) * (1 - fx) + (V[2][2][3] - V[2][2][1]) * fx) * fy) * fz;
-  g.y = (((V[1][2][1] - V[1][0][1]) * (1 - fx) + (V[1][2][2] - V[1][0][2]) * fx) * (1 - fy) +
-         ((V[1][3][1] - V[1][1][1]) * (1 - fx) + (V[1][3][2] - V[1][1][2]) * fx) * fy) * (1 - fz) +
-        (((V[2][2][1] - V[2][0][1]) * (1 - fx) + (V[2][2][2] - V[2][0][2]) * fx) * (1 - fy) +
-         ((V[2][3][1] - V[2][1][1]) * (1 - fx) + (V[2][3][2] - V[2][1][2]) * fx) * fy) * fz;
-  g.z = (((V[2][1][1] - V[0][1][1]) * (1 - fx) + (V[2][1][2] - V[0][1][2]) * fx) * (1 - fy) +
-         ((V[2][2][1] - V[0][2][1]) * (1 - fx) + (V[2][2][2] - V[0][2][2]) * fx) * fy) * (1 - fz) +
-        (((V[3][1][1] - V[1][1][1]) * (1 - fx) + (V[3][1][2] - V[1][1][2]) * fx) * (1 - fy) +
-         ((V[3][2][1] - V[1][2][1]) * (1 - fx) + (V[3][2][2] - V[1][2][2]) * fx) * fy) * fz;
-  return g;  // the caller applies (0.5f * dim / size)
-}
-
 // One instantiation per brick layout.  The field type needs none: y is read through se_ld_y, whose byte / float plane test is uniform
 // across the wave, and initValue() / empty() come from the map (FieldConst).
 template <bool DENSE>
@@ -130,11 +81,11 @@ __global__ __launch_bounds__(SE_WG_QUERY) void k_query_points(DevMap m, const fl
       if (o.interp) ip = se_interp<DENSE>(m, fc, q, c);
       if (o.grad) {
         // se_grad (both forms) takes the stencil's voxels from the blocks of its two extreme clamped coordinates per axis, which holds while
-        // -1 <= floor(q) <= size - 1 on every axis (always, for the raycast).  Outside that band the checked form below reads each voxel by itself.
+        // -1 <= floor(q) <= size - 1 on every axis.  Outside that band se_grad_checked (se_kernels.h) reads each voxel by itself.
         const int hi = m.size - 1;
         const int bx = cvt_i32(floorf(q.x)), by = cvt_i32(floorf(q.y)), bz = cvt_i32(floorf(q.z));
         const bool band = bx >= -1 && bx <= hi && by >= -1 && by <= hi && bz >= -1 && bz <= hi;
-        g = f3_scale(grad_scale, band ? se_grad<DENSE>(m, fc, q, c) : se_query_grad_checked(m, fc, q));
+        g = f3_scale(grad_scale, band ? se_grad<DENSE>(m, fc, q, c) : se_grad_checked(m, fc, q));
       }
     }
     if (o.fine) { o.fine[2 * i] = fine_x; o.fine[2 * i + 1] = fine_y; }

@@ -234,10 +234,10 @@ template <typename VT> static float beam_start(const Octree<VT>& m, const std::v
     const float ti = nearP + (float)l * dt;
     const V3f p = org + dc * ti;
     const int cx = (int)floorf(p.x * inv_cell), cy = (int)floorf(p.y * inv_cell), cz = (int)floorf(p.z * inv_cell);
-    // (a sample in the one-cell shell around the volume takes the dilated bit of the boundary cell it touches, as the kernel does)
+    // (a sample in the one-cell shell around the volume -- cells -1 and n on each axis -- takes the dilated bit of the boundary cell it touches, as the kernel does)
     const int nC = 1 << C;
     auto cl = [](int v, int n) { return std::min(std::max(v, 0), n - 1); };
-    const bool in = (uint32_t)(cx + 1) <= (uint32_t)nC && (uint32_t)(cy + 1) <= (uint32_t)nC && (uint32_t)(cz + 1) <= (uint32_t)nC;
+    const bool in = (uint32_t)(cx + 1) <= (uint32_t)(nC + 1) && (uint32_t)(cy + 1) <= (uint32_t)(nC + 1) && (uint32_t)(cz + 1) <= (uint32_t)(nC + 1);
     const uint32_t idx = in ? (((uint32_t)cl(cz, nC) << (2 * C)) | ((uint32_t)cl(cy, nC) << C) | (uint32_t)cl(cx, nC)) : 0u;
     const bool occupied = in && ((cbits[idx >> 5] >> (idx & 31u)) & 1u);
     const bool clear = !occupied && ((ti + 0.5f * dt) * rad + 0.5f * dt <= 0.9f * cell);
@@ -256,7 +256,7 @@ template <typename VT> static float beam_start(const Octree<VT>& m, const std::v
       const int cx = (int)floorf(p.x * inv_cellf), cy = (int)floorf(p.y * inv_cellf), cz = (int)floorf(p.z * inv_cellf);
       const int nF = 1 << Fl;
       auto cl = [](int v, int n) { return std::min(std::max(v, 0), n - 1); };
-      const bool in = (uint32_t)(cx + 1) <= (uint32_t)nF && (uint32_t)(cy + 1) <= (uint32_t)nF && (uint32_t)(cz + 1) <= (uint32_t)nF;
+      const bool in = (uint32_t)(cx + 1) <= (uint32_t)(nF + 1) && (uint32_t)(cy + 1) <= (uint32_t)(nF + 1) && (uint32_t)(cz + 1) <= (uint32_t)(nF + 1);
       const uint32_t idx = in ? (((uint32_t)cl(cz, nF) << (2 * Fl)) | ((uint32_t)cl(cy, nF) << Fl) | (uint32_t)cl(cx, nF)) : 0u;
       const bool occupied = in && (((*fbits)[idx >> 5] >> (idx & 31u)) & 1u);
       const bool clear = !occupied && ((ti + 0.5f * dt2) * rad + 0.5f * dt2 <= 0.9f * cellf);

@@ -35,6 +35,41 @@ def run_both(field, W, H, N, dim, mu, frames, holes=True, max_blocks=0, on_frame
     return cpu, gpu, out
 
 
+def look(position, yaw_deg=0.0, pitch_deg=0.0, roll_deg=0.0):
+    """Camera->world pose: yaw about y, then pitch about x, then roll about z, at `position` (metres)."""
+    y, p, r = np.deg2rad([yaw_deg, pitch_deg, roll_deg])
+    Ry = np.array([[np.cos(y), 0, np.sin(y)], [0, 1, 0], [-np.sin(y), 0, np.cos(y)]])
+    Rx = np.array([[1, 0, 0], [0, np.cos(p), -np.sin(p)], [0, np.sin(p), np.cos(p)]])
+    Rz = np.array([[np.cos(r), -np.sin(r), 0], [np.sin(r), np.cos(r), 0], [0, 0, 1]])
+    T = np.eye(4)
+    T[:3, :3] = Ry @ Rx @ Rz
+    T[:3, 3] = position
+    return T.astype(np.float32)
+
+
+# Cameras outside the volume (all lengths as fractions of its edge): name -> (position on the face, outward direction, rotation of look()).  The
+# camera sits at position + d * outward.  The six face views look in along the face's normal; the tilted ones look back in obliquely, so that
+# their rays cross the one-cell shell around the volume near an edge or a corner.
+OUTSIDE_VIEWS = {
+    "-x": ((0.0, 0.5, 0.5), (-1, 0, 0), dict(yaw_deg=90)),
+    "+x": ((1.0, 0.5, 0.5), (1, 0, 0), dict(yaw_deg=-90)),
+    "-y": ((0.5, 0.0, 0.5), (0, -1, 0), dict(pitch_deg=-90)),     # (image rows run along world z)
+    "+y": ((0.5, 1.0, 0.5), (0, 1, 0), dict(pitch_deg=90)),
+    "-z": ((0.5, 0.5, 0.0), (0, 0, -1), {}),
+    "+z": ((0.5, 0.5, 1.0), (0, 0, 1), dict(yaw_deg=180)),
+    "+z_tilted": ((0.8, 0.7, 1.0), (0, 0, 1), dict(yaw_deg=160, pitch_deg=15)),
+    "+x_tilted": ((1.0, 0.75, 0.85), (1, 0, 0), dict(yaw_deg=-115, pitch_deg=20)),
+    "+y_tilted": ((0.8, 1.0, 0.8), (0, 1, 0), dict(yaw_deg=-135, pitch_deg=60)),
+    "upper_corner": ((1.0, 1.0, 1.0), (1, 1, 1), dict(yaw_deg=-135, pitch_deg=35)),
+}
+
+
+def outside_view(name, d, dim):
+    """The camera of OUTSIDE_VIEWS[name], `d` volume edges beyond its face (along each outward axis)."""
+    pos, out, rot = OUTSIDE_VIEWS[name]
+    return look((np.asarray(pos, np.float64) + d * np.asarray(out, np.float64)) * dim, **rot)
+
+
 def compare_maps(cpu, gpu):
     """Returns a dict of mismatch statistics between oracle and HIP map state (blocks sorted by key)."""
     cc, cx, cy, ca = cpu.blocks()

@@ -13,6 +13,7 @@ import pytest
 
 from oracle import binding
 from supereight_amd.synthetic import make_stream, to_colmajor
+from tests.parity_util import OUTSIDE_VIEWS, outside_view
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -26,6 +27,16 @@ def lib(tmp_path_factory):
     lib.fl_compare.restype = None
     lib.fl_compare.argtypes = [C.c_void_p, binding.c_f32p, binding.c_f32p, np.ctypeslib.ndpointer(np.int64), np.ctypeslib.ndpointer(np.int32), C.c_int]
     return lib
+
+
+FIELDS = ("rays", "irregular", "flagged", "mismatch", "found", "trips_ref", "trips_lite", "model_bug")
+
+
+def _compare(lib, h, view, k, beam):
+    out = np.zeros(8, np.int64)
+    bad = np.zeros(2, np.int32)
+    lib.fl_compare(h, to_colmajor(view), k, out, bad, beam)
+    return out, bad
 
 
 def _run(lib, field, kind, W, H, N, mu, frames, pose_shift=None, beam=0, first_view=3):
@@ -42,14 +53,12 @@ def _run(lib, field, kind, W, H, N, mu, frames, pose_shift=None, beam=0, first_v
                 view = pose.copy()
                 if pose_shift is not None:
                     view[:3, 3] += np.asarray(pose_shift, np.float32)
-                out = np.zeros(8, np.int64)
-                bad = np.zeros(2, np.int32)
-                lib.fl_compare(h, to_colmajor(view), k, out, bad, beam)
+                out, bad = _compare(lib, h, view, k, beam)
                 assert out[3] == 0 and out[7] == 0, f"frame {f}: {out[3]} rays differ from the iterator (e.g. pixel {bad.tolist()}), model errors {out[7]}"
                 tot += out
     finally:
         lib.so_pipe_destroy(h)
-    return dict(zip(("rays", "irregular", "flagged", "mismatch", "found", "trips_ref", "trips_lite", "model_bug"), tot.tolist()))
+    return dict(zip(FIELDS, tot.tolist()))
 
 
 @pytest.mark.parametrize("field,kind,N,mu", [(binding.SDF, "room", 512, 0.1), (binding.SDF, "stress", 256, 0.1), (binding.OFUSION, "stress", 512, 0.02),
@@ -95,3 +104,55 @@ def test_beam_start_returns_the_iterators_leaf(lib, field, kind, W, H, N, mu, fr
 def test_beam_start_from_outside_the_volume(lib):
     r = _run(lib, binding.SDF, "room", 160, 120, 256, 0.1, 5, pose_shift=(0.0, 0.0, -6.0), beam=1)
     assert r["irregular"] > 0 and r["mismatch"] == 0
+
+
+# Maps for the views from beyond the faces (160x120, frames 0-5, 4.8 m): name -> field, stream, N, mu
+FACE_MAPS = {
+    "room_sdf_256": (binding.SDF, "room", 256, 0.1),          # the back wall's band reaches the +z face's boundary coarse cells
+    "stress_sdf_256": (binding.SDF, "stress", 256, 0.1),      # the stress room is cut by the -x and +z faces: blocks in the boundary cells
+    "stress_sdf_512": (binding.SDF, "stress", 512, 0.1),      # (the second stage's fine grid exists from leaf level 6 on)
+    "stress_ofusion_512": (binding.OFUSION, "stress", 512, 0.02),
+    "room_sdf_128": (binding.SDF, "room", 128, 0.1),          # leaf level 4: the coarse grid IS the block grid
+}
+# camera offsets beyond the face, as fractions of the edge: from inside the one-cell shell (a coarse cell is 1/32 of the edge, 1/16 at 128^3) out to
+# ~10 coarse cells, a fifth of a coarse cell apart, so that the beam's samples (half a coarse cell apart) land at every depth of the shell
+FACE_OFFSETS = [i * 0.00625 for i in range(1, 49)]
+
+
+@pytest.fixture(scope="module")
+def face_maps(lib):
+    made = {}
+
+    def get(name):
+        if name not in made:
+            field, kind, N, mu = FACE_MAPS[name]
+            st = make_stream(kind, 160, 120, 4.8)
+            h = lib.so_pipe_create(field, N, 4.8, 160, 120)
+            k = np.asarray(st.k, np.float32)
+            for f in range(6):
+                lib.so_pipe_integrate(h, np.ascontiguousarray(st.depth(f), np.float32).reshape(-1), to_colmajor(st.pose(f)), k, 1, mu, f)
+            made[name] = (h, k)
+        return made[name]
+    yield get
+    for h, _ in made.values():
+        lib.so_pipe_destroy(h)
+
+
+@pytest.mark.parametrize("view", list(OUTSIDE_VIEWS))
+@pytest.mark.parametrize("name", list(FACE_MAPS))
+def test_beam_start_from_beyond_every_face(lib, face_maps, name, view):
+    """A beam sample outside the volume but within one coarse (stage 2: fine) cell of it takes the dilated bit of the boundary cell it touches --
+    on every face.  The shell test of se_beam_start once accepted only the cells -1 .. n-1: a sample just beyond an upper face counted as clear,
+    and tiles seen from outside +z started their search up to ~0.9 cell inside the boundary cell, behind the blocks there (room 256^3 from
+    0.075-0.30 edges beyond +z: 17 of 19 offsets with 2-61 rays each that missed the iterator's first leaf).  From each camera of OUTSIDE_VIEWS,
+    at every offset and with one and two stages, every ray that is not handed back must find the iterator's leaf at its t_min."""
+    h, k = face_maps(name)
+    bad = []
+    for d in FACE_OFFSETS:
+        view_pose = outside_view(view, d, 4.8)
+        for beam in (1, 2):
+            out, px = _compare(lib, h, view_pose, k, beam)
+            r = dict(zip(FIELDS, out.tolist()))
+            if r["mismatch"] or r["model_bug"] or not r["found"]:
+                bad.append((round(d, 5), beam, r["mismatch"], r["model_bug"], r["found"], px.tolist()))
+    assert not bad, f"(offset, stage, rays that differ from the iterator, model errors, rays found, a differing pixel): {bad}"

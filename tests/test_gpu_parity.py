@@ -11,6 +11,7 @@ import pytest
 
 from oracle.binding import OFUSION, SDF
 from tests.parity_util import compare_maps, compare_raycast, run_both
+from tests.parity_util import look as _look
 
 pytestmark = pytest.mark.gpu
 
@@ -170,18 +171,6 @@ def test_weight_saturated_blocks_stay_bit_exact(max_blocks):
     cpu.close(); gpu.close()
 
 
-def _look(position, yaw_deg=0.0, pitch_deg=0.0, roll_deg=0.0):
-    """Camera->world pose: yaw about y, then pitch about x, then roll about z, at `position` (metres)."""
-    y, p, r = np.deg2rad([yaw_deg, pitch_deg, roll_deg])
-    Ry = np.array([[np.cos(y), 0, np.sin(y)], [0, 1, 0], [-np.sin(y), 0, np.cos(y)]])
-    Rx = np.array([[1, 0, 0], [0, np.cos(p), -np.sin(p)], [0, np.sin(p), np.cos(p)]])
-    Rz = np.array([[np.cos(r), -np.sin(r), 0], [np.sin(r), np.cos(r), 0], [0, 0, 1]])
-    T = np.eye(4)
-    T[:3, :3] = Ry @ Rx @ Rz
-    T[:3, 3] = position
-    return T.astype(np.float32)
-
-
 @pytest.mark.parametrize("field,W,H,N,dim,mu,frames", [(SDF, 320, 240, 512, 4.8, 0.1, 8), (SDF, 160, 120, 1024, 4.8, 0.1, 5), (OFUSION, 160, 120, 256, 2.4, 0.02, 8)],
                          ids=["sdf512", "sdf1024", "ofusion256"])
 def test_raycast_from_unusual_viewpoints(field, W, H, N, dim, mu, frames):
@@ -198,6 +187,13 @@ def test_raycast_from_unusual_viewpoints(field, W, H, N, dim, mu, frames):
         "behind_the_volume": _look(c + [0, 0, -0.8 * dim]),                       # enters through z = 0 after 0.3 dim of nothing
         "beside_the_volume": _look(c + [-0.7 * dim, 0, 0], yaw_deg=90),           # enters through x = 0
         "above_looking_down": _look(c + [0, -0.75 * dim, 0], pitch_deg=-90),      # enters through y = 0 (rows run along world z)
+        # the same three beyond the upper faces, and each once more from inside the one-cell shell of the beam start's coarse grid (se_beam_start)
+        "beyond_the_back": _look(c + [0, 0, 0.8 * dim], yaw_deg=180),            # enters through z = dim
+        "beyond_the_back_near": _look(c + [0, 0, 0.6 * dim], yaw_deg=180),
+        "beside_the_volume_at_x_max": _look(c + [0.7 * dim, 0, 0], yaw_deg=-90),  # enters through x = dim
+        "beside_the_volume_at_x_max_near": _look(c + [0.6 * dim, 0, 0], yaw_deg=-90),
+        "below_looking_up": _look(c + [0, 0.75 * dim, 0], pitch_deg=90),          # enters through y = dim
+        "below_looking_up_near": _look(c + [0, 0.6 * dim, 0], pitch_deg=90),
         "far_away": _look(c + [0, 0, -6.0 * dim]),                                # far plane (4 m) ends every ray before the volume
         "turned_around": _look(np.array([0.34, 0.5, 0.24]) * dim, yaw_deg=180),   # back wall at 0.19 dim, against the integration direction
         "diagonal_from_corner": _look(np.array([0.02, 0.02, 0.02]) * dim, yaw_deg=45, pitch_deg=-35),
