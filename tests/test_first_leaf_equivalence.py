@@ -13,6 +13,7 @@ import pytest
 
 from oracle import binding
 from supereight_amd.synthetic import make_stream, to_colmajor
+from tests.edge_frames import RES_CASES, SHAPE_CASES, RoomStream
 from tests.parity_util import OUTSIDE_VIEWS, outside_view
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,9 +40,9 @@ def _compare(lib, h, view, k, beam):
     return out, bad
 
 
-def _run(lib, field, kind, W, H, N, mu, frames, pose_shift=None, beam=0, first_view=3):
-    st = make_stream(kind, W, H, 4.8)
-    h = lib.so_pipe_create(field, N, 4.8, W, H)
+def _run(lib, field, kind, W, H, N, mu, frames, pose_shift=None, beam=0, first_view=3, stream=None):
+    st = make_stream(kind, W, H, 4.8) if stream is None else stream
+    h = lib.so_pipe_create(field, N, st.dim, W, H)
     tot = np.zeros(8, np.int64)
     try:
         for f in range(frames):
@@ -99,6 +100,26 @@ def test_beam_start_returns_the_iterators_leaf(lib, field, kind, W, H, N, mu, fr
     assert r["flagged"] <= base["flagged"] + r["rays"] // 5000
     if N >= 512:
         assert r["trips_lite"] < 0.85 * base["trips_lite"]
+
+
+EDGE_BEAM_CASES = [c for c in SHAPE_CASES + RES_CASES if c["W"] * c["H"] < 100000] + [
+    # a 3-pixel column through a very narrow lens: one partial tile column, an 8x8 beam much thinner than a cell
+    dict(name="column_3x203_fx1000_sdf", W=3, H=203, N=512, dim=4.8, k=(1000.0, 1000.0, 1.5, 101.5), field=binding.SDF, mu=0.1, frames=6),
+]
+
+
+@pytest.mark.parametrize("case", EDGE_BEAM_CASES, ids=[c["name"] for c in EDGE_BEAM_CASES])
+def test_beam_start_at_edge_cameras_and_resolutions(lib, case):
+    """The same claim for the cameras and volume resolutions of tests/test_gpu_edge_configs.py: partial tiles, fx != fy, off-centre principal
+    points, negative fy, wide and narrow lenses, 64^3 (no fine grid, leaf level below the staged levels) and 4096^3 (three levels beyond them)."""
+    args = (lib, case["field"], "room", case["W"], case["H"], case["N"], case["mu"], case["frames"])
+    base = _run(*args, stream=RoomStream(case["W"], case["H"], case["dim"], case["k"]))
+    for beam in (1, 2):
+        r = _run(*args, beam=beam, stream=RoomStream(case["W"], case["H"], case["dim"], case["k"]))
+        print(case["name"], "beam", beam, r)
+        assert r["rays"] == base["rays"] == 3 * case["W"] * case["H"] and r["mismatch"] == 0 and r["model_bug"] == 0, r
+        assert r["found"] + r["flagged"] >= base["found"] > 0
+        assert r["flagged"] <= base["flagged"] + r["rays"] // 5000 + 1
 
 
 def test_beam_start_from_outside_the_volume(lib):

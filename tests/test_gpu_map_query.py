@@ -53,17 +53,18 @@ def _decode(code):
 
 
 class _Map:
-    """The device map as downloaded, with the oracle's octree (FTree) built from it."""
+    """The device map as downloaded, with the oracle's octree (FTree) built from it (a map of n^3 voxels over dim metres)."""
 
-    def __init__(self, oracle, p, field):
+    def __init__(self, oracle, p, field, n=N, dim=DIM):
         self.lib, self.field = oracle, field
+        self.N, self.dim = n, dim
         self.coords, self.x, self.y, _ = p.blocks()
         self.ncode, _, self.nx, self.ny = p.nodes()
         self.row = {tuple(int(v) for v in c): i for i, c in enumerate(self.coords)}
         self.nrow = {int(c): i for i, c in enumerate(self.ncode)}
         self.init = INIT[field]
-        self.max_level = N.bit_length() - 1
-        t = oracle.so_ft_create(N, DIM, self.init[0], self.init[0])
+        self.max_level = n.bit_length() - 1
+        t = oracle.so_ft_create(n, dim, self.init[0], self.init[0])
         code, co, isb = C.c_uint64(0), np.zeros(3, np.int32), C.c_int(0)
         for c in sorted(self.ncode, key=lambda k: int(k) & 0x1FF):
             x, y, z, lvl = _decode(c)
@@ -90,8 +91,8 @@ class _Map:
 
     def expected(self, pts):
         """Oracle answers for float32 points [n, 3] in metres."""
-        lib, t = self.lib, self.t
-        s = np.float32(N) / np.float32(DIM)
+        lib, t, N = self.lib, self.t, self.N
+        s = np.float32(N) / np.float32(self.dim)
         q = (s * pts).astype(np.float32)
         n = len(pts)
         fine, coarse = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32)
@@ -141,6 +142,7 @@ class _Map:
     def points(self, p, rng):
         """Random points in the volume, jittered raycast hits, block faces / edges / corners, points next to missing blocks, and
         points just outside each face of the volume (metres, float32)."""
+        N, DIM = self.N, self.dim
         vox = np.float32(DIM) / np.float32(N)
         sets = [rng.uniform(0, DIM, (600, 3))]
         v, nrm = p.vertex_normal()

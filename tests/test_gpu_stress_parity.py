@@ -109,21 +109,23 @@ def test_fused_launch_at_bench_shape(name, stream, field, N, mu, frames, max_blo
     _pipelined_case(stream, 640, 480, field, N, mu, frames, max_blocks, True, min_hits_per_frame=100000)
 
 
-def _pipelined_case(stream_kind, W, H, field, N, mu, frames, max_blocks, streaming, min_hits_per_frame=300):
+def _pipelined_case(stream_kind, W, H, field, N, mu, frames, max_blocks, streaming, min_hits_per_frame=300, stream=None, fuses=True):
     """The stress stream enqueued back to back with NO call between the se_hip_frame calls, every frame's vertex / normal images kept in an
     image ring (se_hip_set_image_ring) and EVERY slot compared with the oracle's raycast of that frame, bit for bit, plus the final map.
       one-queue (se_hip_set_streaming): the raycast of frame f runs inside k_raycast_scan, the launch that also scans frame f+1 -- the kernel
         the benchmark's headline times.  Its scan half inserts into the index (and, pooled bricks, hands out bricks) that its raycast half is
         reading; asserted through the launch counters: all raycasts but the last (flushed by the final sync) were fused launches.
       two-queue (the eager schedule): k_raycast on the main stream beside k_alloc_scan on the scan stream, released by the host gate.
-    Pooled maps: the serial schedule (SE_HIP_POOLED_OVERLAP=0) must give the same images."""
+    Pooled maps: the serial schedule (SE_HIP_POOLED_OVERLAP=0) must give the same images.
+    `stream`: a frame source of the caller's in place of make_stream(stream_kind, W, H, 4.8).  `fuses`: whether a one-queue handle of this shape
+    fuses at all (False: the raycast does not fit the chip in one round, se_hip_frame_is_fused is false and the eager schedule runs)."""
     import os
     import torch
     from oracle.binding import OraclePipeline
     from supereight_amd.pipeline import DenseSLAMPipeline
     from supereight_amd.synthetic import make_stream, to_colmajor
-    dim = 4.8
-    s = make_stream(stream_kind, W, H, dim)
+    s = make_stream(stream_kind, W, H, 4.8) if stream is None else stream
+    dim = s.dim
     depths = [s.depth(f) for f in range(frames)]
     poses = [s.pose(f) for f in range(frames)]
     dev = torch.from_numpy(np.stack(depths)).cuda()
@@ -137,12 +139,12 @@ def _pipelined_case(stream_kind, W, H, field, N, mu, frames, max_blocks, streami
         assert gpu.image_tile_bytes(H) == ring[0].numel() * 4
         gpu.set_image_ring(ring.data_ptr(), frames, keepalive=ring)
         if stream_mode:
-            assert gpu.set_streaming(True) == expect_overlap and gpu.frame_is_fused() == expect_overlap
+            assert gpu.set_streaming(True) == (expect_overlap and fuses) and gpu.frame_is_fused() == (expect_overlap and fuses)
         gpu.launch_counts(reset=True)
         for f in range(frames):
             assert gpu.frame(dev[f].data_ptr(), pcm[f], k, mu, f) == (3 if f > 2 else 1)      # nothing else is called between the frames
         n = gpu.launch_counts()
-        if stream_mode and expect_overlap:
+        if stream_mode and expect_overlap and fuses:
             assert n["pending"] and n["raycast"] == frames - 4 and n["fused"] == frames - 4, n     # frames 3 .. frames-2: fused; the last one is held back
         else:
             assert not n["pending"] and n["raycast"] == frames - 3 and n["fused"] == 0, n
