@@ -192,6 +192,13 @@ class DenseSLAMSystem {
   bool queryMap(const float* host_points_m, size_t n, se_hip_query_out& host_out) {
     return ok(se_hip_query_points_host(h_, host_points_m, (int64_t)n, &host_out));
   }
+  /* Not in the reference's class (an addition of this mirror): se::geometry::collides_with for n axis-aligned boxes (host_boxes[n][6]: lo xyz,
+   * side xyz in voxels) answered on the device map without getMap() -- se_hip_collide_boxes_host, definitions in se_hip.h.  mode
+   * SE_HIP_COLLIDE_REFERENCE returns what collides_with (include/se/octree_collision.hpp) returns on the getMap() snapshot, SE_HIP_COLLIDE_STRICT
+   * the min over the box's voxels; host_status[n] receives 0 occupied, 1 unseen, 2 empty, 255 invalid box. */
+  bool collidesWith(const int32_t* host_boxes, size_t n, const se_hip_collide_test& test, int32_t mode, uint8_t* host_status) {
+    return ok(se_hip_collide_boxes_host(h_, host_boxes, (int64_t)n, &test, mode, host_status));
+  }
   /* vertex_ / normal_ of the last raycasting(): width*height packed xyz */
   bool getVertexNormal(std::vector<float>& vertex, std::vector<float>& normal) {
     const size_t n = (size_t)computation_size_.x() * computation_size_.y() * 3;

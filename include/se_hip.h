@@ -332,6 +332,55 @@ typedef struct se_hip_query_out {
 int se_hip_query_points(se_hip_pipeline* p, const float* device_points_m, int64_t n, const se_hip_query_out* device_out);
 int se_hip_query_points_host(se_hip_pipeline* p, const float* host_points_m, int64_t n, const se_hip_query_out* host_out);
 
+/* ---- batched collision queries for axis-aligned boxes against the resident map: the reference's map read algorithm
+ *      se::geometry::collides_with (se_core/include/se/geometry/octree_collision.hpp:74-167, overlap test aabb_collision.hpp),
+ *      for N boxes at once, without getMap().  The host restatement of that function is include/se/octree_collision.hpp.
+ * Box: int32 lo[3], side[3] in voxel units (collides_with(map, bbox = lo, side, test)).  A box with side < 1 on any axis, or with any
+ *   coordinate of lo or lo + side outside [-2^30, 2^30], gets status SE_HIP_COLLISION_INVALID and reads no map memory.
+ * Voxel classification (the reference passes a functor; here a parameter struct).  v = (x, y), y read as float as se_hip_download_blocks
+ *   returns it (the SDF weight byte converted; OFusion's y as stored):
+ *     unseen    if x == initValue().x && y == initValue().y (the rule of the reference's own test functor: SDF {1, 0}, OFusion {0, 0});
+ *     occupied  else if (occupied_above ? x > threshold : x < threshold);
+ *     empty     otherwise.
+ * Status codes follow the order of se::geometry::collision_status; combining two statuses takes the smaller code (the reference's
+ *   update_status: empty < unseen < occupied by severity).
+ * Modes:
+ *   SE_HIP_COLLIDE_STRICT     B = [lo, lo + side) per axis (half open).  status = min over the voxels v of B ∩ [0, size)^3 of
+ *                             classify(Octree::get(v)) -- the voxel if its block is allocated, else value_[child] of the deepest existing
+ *                             node on the path (exactly the coarse output of se_hip_query_points at v).  Any part of B outside the volume
+ *                             counts as unseen; a box entirely outside is unseen.
+ *   SE_HIP_COLLIDE_REFERENCE  exactly what the reference's collides_with returns, quirks included (deliberate parity):
+ *                             - inclusive overlap test on integer midpoints, |(b + be/2) - (a + ae/2)| <= (ae + be)/2, for octants and for
+ *                               voxels (edge 1): a box of side 2 touches 3 voxels per axis (evaluated without int32 overflow);
+ *                             - an absent overlapping child is judged by its parent's value_[0], not value_[child];
+ *                             - a visited leaf's status replaces the running status instead of being merged into it;
+ *                             - the root is always visited and is not itself overlap-tested; a node without children adds nothing.
+ *                             The traversal is a stack DFS that visits children in order 7..0, so the result has a closed form (DESIGN.md
+ *                             4.7): with L* the visited leaf of smallest Morton code, result = min(class(L*), ev(Q) for the visited internal
+ *                             nodes Q whose octant ends at or before L*'s code); without a visited leaf, the min of every ev(Q) from empty.
+ *                             ev(Q) = classify(Q.value_[0]) if Q has children and an overlapping absent child.  Only L*'s voxels are read.
+ * Both entries answer for the map after everything enqueued before them (a scan that ran on the side stream included), refuse n < 0, a null
+ * boxes or status pointer with n > 0, a null test, a non-finite threshold, occupied_above other than 0 / 1 and an unknown mode with
+ * SE_HIP_E_INVALID (n == 0 is a no-op), report a sticky SE_HIP_E_CAPACITY like the other read-back calls, and leave the map, the images and
+ * the launch counters (SE_HIP_K_*) alone.
+ *   se_hip_collide_boxes       device arrays (boxes [n][6] int32: lo xyz, side xyz; status [n] uint8); enqueued on the handle's stream,
+ *                              asynchronous like the stage calls.
+ *   se_hip_collide_boxes_host  host arrays; staged through a device buffer the handle keeps (and grows); synchronises before it returns. */
+#define SE_HIP_COLLISION_OCCUPIED 0
+#define SE_HIP_COLLISION_UNSEEN 1
+#define SE_HIP_COLLISION_EMPTY 2
+#define SE_HIP_COLLISION_INVALID 255
+#define SE_HIP_COLLIDE_STRICT 0
+#define SE_HIP_COLLIDE_REFERENCE 1
+typedef struct se_hip_collide_test {
+  float threshold;
+  int32_t occupied_above;   /* 1: x > threshold is occupied (OFusion log-odds), 0: x < threshold (SDF) */
+} se_hip_collide_test;
+int se_hip_collide_boxes(se_hip_pipeline* p, const int32_t* device_boxes, int64_t n, const se_hip_collide_test* test, int32_t mode,
+                         uint8_t* device_status);
+int se_hip_collide_boxes_host(se_hip_pipeline* p, const int32_t* host_boxes, int64_t n, const se_hip_collide_test* test, int32_t mode,
+                              uint8_t* host_status);
+
 /* ---- "next" row f-4: Octree::save (se_core/include/se/octree.hpp:898-914, io/se_serialise.hpp:54-86),
  *      written straight from the device map in the reference's byte layout:
  *        int32 size, float dim, uint64 n_nodes, n_nodes x {uint64 code, int32 side, value_[8]},

@@ -23,6 +23,7 @@
 #include "se_track_kernels.h"
 #include "se_mesh_kernels.h"
 #include "se_query_kernels.h"
+#include "se_collide_kernels.h"
 
 int flush_pending_raycast(se_hip_pipeline* p);   // (defined next to se_hip_frame)
 
@@ -146,6 +147,8 @@ struct se_hip_pipeline {
   unsigned long long* mesh_ctr = nullptr;
   unsigned char* query_buf = nullptr;   // se_hip_query_points_host: device staging of the points and the outputs, grown on demand
   size_t query_cap = 0;
+  unsigned char* collide_buf = nullptr; // se_hip_collide_boxes_host: device staging of the boxes and the statuses, grown on demand
+  size_t collide_cap = 0;
   bool filter_input = false;   // preprocessing(..., filterInput): tracking sees the bilateral-filtered depth
   bool occ_commit_due = false; // the next sweep kernel must publish the scan's occupancy bits
   OccLists occ_lists{nullptr, 0, 0};   // ... of these key lists (own list, or every rank's after se_hip_alloc_commit)
@@ -712,6 +715,7 @@ int se_hip_destroy(se_hip_pipeline* p) {
   if (p->gate_host) hipHostFree(p->gate_host);
   if (p->mesh_ctr) hipFree(p->mesh_ctr);
   if (p->query_buf) hipFree(p->query_buf);
+  if (p->collide_buf) hipFree(p->collide_buf);
   for (int i = 0; i < se_hip_pipeline::kIn; ++i) { if (p->in_host[i]) hipHostFree(p->in_host[i]); if (p->in_done[i]) hipEventDestroy(p->in_done[i]); }
   if (p->own_side && p->side) hipStreamDestroy(p->side);
   if (p->ev_sweep) hipEventDestroy(p->ev_sweep);
@@ -1966,6 +1970,61 @@ int se_hip_query_points_host(se_hip_pipeline* p, const float* host_points_m, int
   void* dst[5] = {host_out->fine, host_out->coarse, host_out->interp, host_out->grad, host_out->status};
   for (int k = 0; k < 5; ++k)
     if (sz[k]) HIP_TRY(hipMemcpyAsync(dst[k], b + off[k], sz[k], hipMemcpyDeviceToHost, p->stream));
+  // (synchronises; a sticky overflow is reported as the other read-back calls report it)
+  return fetch_counters(p);
+}
+
+
+// ------------------------------------------------------------------------------------ box collision queries
+namespace {
+int collide_args(const int32_t* boxes, int64_t n, const se_hip_collide_test* test, int32_t mode, const uint8_t* status) {
+  if (n < 0) return fail(SE_HIP_E_INVALID, "se_hip_collide_boxes: n < 0");
+  if (n > 0 && (!boxes || !status)) return fail(SE_HIP_E_INVALID, "se_hip_collide_boxes: null boxes or status");
+  if (!test) return fail(SE_HIP_E_INVALID, "se_hip_collide_boxes: null test");
+  if (!std::isfinite(test->threshold)) return fail(SE_HIP_E_INVALID, "se_hip_collide_boxes: non-finite threshold");
+  if (test->occupied_above != 0 && test->occupied_above != 1) return fail(SE_HIP_E_INVALID, "se_hip_collide_boxes: occupied_above must be 0 or 1");
+  if (mode != SE_HIP_COLLIDE_STRICT && mode != SE_HIP_COLLIDE_REFERENCE) return fail(SE_HIP_E_INVALID, "se_hip_collide_boxes: unknown mode");
+  return SE_HIP_OK;
+}
+void launch_collide(se_hip_pipeline* p, const int32_t* boxes, int64_t n, const se_hip_collide_test* test, int32_t mode, uint8_t* status) {
+  const DevMap& m = p->map;
+  const CollideArgs a{boxes, (long long)n, status, test->threshold, test->occupied_above, mode == SE_HIP_COLLIDE_REFERENCE ? 1 : 0};
+  const int grid = (int)std::min<int64_t>(n, 1 << 20);   // one wave per box, grid-stride beyond
+  if (m.dense) hipLaunchKernelGGL((k_collide_boxes<true>), dim3(grid), dim3(SE_WG_COLLIDE), 0, p->stream, m, a);
+  else hipLaunchKernelGGL((k_collide_boxes<false>), dim3(grid), dim3(SE_WG_COLLIDE), 0, p->stream, m, a);
+}
+}  // namespace
+
+int se_hip_collide_boxes(se_hip_pipeline* p, const int32_t* device_boxes, int64_t n, const se_hip_collide_test* test, int32_t mode,
+                         uint8_t* device_status) {
+  if (int r = check(p)) return r;
+  if (int r = collide_args(device_boxes, n, test, mode, device_status)) return r;
+  if (int r = join_scan(p)) return r;
+  if (int r = check_overflow(p)) return r;
+  if (n == 0) return SE_HIP_OK;
+  launch_collide(p, device_boxes, n, test, mode, device_status);
+  HIP_TRY(hipGetLastError());
+  return SE_HIP_OK;
+}
+
+int se_hip_collide_boxes_host(se_hip_pipeline* p, const int32_t* host_boxes, int64_t n, const se_hip_collide_test* test, int32_t mode,
+                              uint8_t* host_status) {
+  if (int r = check(p)) return r;
+  if (int r = collide_args(host_boxes, n, test, mode, host_status)) return r;
+  if (int r = join_scan(p)) return r;
+  if (n == 0) return fetch_counters(p);
+  // staging: [boxes n x 6 int32][status n]
+  const size_t un = (size_t)n, need = un * 6 * sizeof(int32_t) + un;
+  if (need > p->collide_cap) {
+    if (p->collide_buf) { HIP_TRY(hipStreamSynchronize(p->stream)); hipFree(p->collide_buf); p->collide_buf = nullptr; p->collide_cap = 0; }
+    HIP_TRY(hipMalloc((void**)&p->collide_buf, need));
+    p->collide_cap = need;
+  }
+  unsigned char* b = p->collide_buf;
+  HIP_TRY(hipMemcpyAsync(b, host_boxes, un * 6 * sizeof(int32_t), hipMemcpyHostToDevice, p->stream));
+  launch_collide(p, (const int32_t*)b, n, test, mode, b + un * 6 * sizeof(int32_t));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(host_status, b + un * 6 * sizeof(int32_t), un, hipMemcpyDeviceToHost, p->stream));
   // (synchronises; a sticky overflow is reported as the other read-back calls report it)
   return fetch_counters(p);
 }

@@ -38,6 +38,16 @@ class _QueryOut(C.Structure):
     _fields_ = [("fine", C.c_void_p), ("coarse", C.c_void_p), ("interp", C.c_void_p), ("grad", C.c_void_p), ("status", C.c_void_p)]
 
 
+class _CollideTest(C.Structure):
+    """se_hip_collide_test of include/se_hip.h."""
+    _fields_ = [("threshold", C.c_float), ("occupied_above", C.c_int32)]
+
+
+# status codes of se_hip_collide_boxes (the order of se::geometry::collision_status; combining takes the minimum)
+COLLISION_OCCUPIED, COLLISION_UNSEEN, COLLISION_EMPTY, COLLISION_INVALID = 0, 1, 2, 255
+_COLLIDE_MODES = {"strict": 0, "reference": 1}
+
+
 class _Config(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("volume_resolution", C.c_int32),
                 ("volume_dimension", C.c_float), ("field_type", C.c_int32), ("device", C.c_int32),
@@ -108,6 +118,8 @@ EXPORTS = {
     "se_hip_get_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32]),
     "se_hip_query_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_QueryOut)]),
     "se_hip_query_points_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_QueryOut)]),
+    "se_hip_collide_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
+    "se_hip_collide_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
 }
 
 
@@ -590,6 +602,56 @@ class DenseSLAMPipeline:
         self._check(self.lib.se_hip_query_points(self._h, points.data_ptr() if n else None, n, C.byref(out)))
         self.sync()
         return res
+
+    def collides(self, boxes, threshold: float = 0.0, occupied_above=None, mode: str = "strict"):
+        """Batched collision queries for axis-aligned boxes (se_hip_collide_boxes, include/se_hip.h): boxes [N, 6] int32 = lo xyz, side xyz
+        in voxels.  Returns one status per box: COLLISION_OCCUPIED (0), COLLISION_UNSEEN (1), COLLISION_EMPTY (2), COLLISION_INVALID (255).
+        A voxel is unseen where it equals initValue(), else occupied where x > threshold (occupied_above) or x < threshold, else empty;
+        occupied_above defaults by field: False for SDF, True for OFusion.  mode "strict": the min over the voxels of [lo, lo + side)
+        (outside the volume counts as unseen); "reference": exactly what the reference's se::geometry::collides_with returns.
+          - numpy int32 [N, 6]: through the host entry; a numpy uint8 array out.
+          - a torch int32 tensor on this handle's GPU (contiguous, [N, 6]): through the device entry; a torch uint8 tensor on the same
+            device out.  The caller's current torch stream is synchronised first, and the handle before the tensor is returned.
+        Anything else raises TypeError / ValueError before any library call."""
+        if mode not in _COLLIDE_MODES:
+            raise ValueError(f"collides: mode must be one of {sorted(_COLLIDE_MODES)}, got {mode!r}")
+        if occupied_above is None:
+            occupied_above = self.field == OFUSION
+        if not isinstance(occupied_above, (bool, np.bool_)):
+            raise TypeError(f"collides: occupied_above must be a bool, got {type(occupied_above).__name__}")
+        thr = float(threshold)
+        if not np.isfinite(np.float32(thr)):
+            raise ValueError(f"collides: threshold must be finite as a float32, got {threshold!r}")
+        test = _CollideTest(thr, int(bool(occupied_above)))
+        m = _COLLIDE_MODES[mode]
+        if type(boxes) is np.ndarray:
+            if boxes.dtype != np.int32:
+                raise TypeError(f"collides: boxes must be int32, got {boxes.dtype}")
+            if boxes.ndim != 2 or boxes.shape[1] != 6:
+                raise ValueError(f"collides: boxes must have shape [N, 6], got {list(boxes.shape)}")
+            b = np.ascontiguousarray(boxes)
+            n = b.shape[0]
+            out = np.empty(n, np.uint8)
+            self._check(self.lib.se_hip_collide_boxes_host(self._h, b.ctypes.data if n else None, n, C.byref(test), m,
+                                                           out.ctypes.data if n else None))
+            return out
+        torch = _torch_module(boxes)
+        if torch is None:
+            raise TypeError(f"collides: boxes must be a numpy int32 array or a torch tensor on the GPU, got {type(boxes).__name__}")
+        if boxes.dtype != torch.int32:
+            raise TypeError(f"collides: boxes must be int32, got {boxes.dtype}")
+        if boxes.dim() != 2 or boxes.shape[1] != 6:
+            raise ValueError(f"collides: boxes must have shape [N, 6], got {list(boxes.shape)}")
+        if not boxes.is_contiguous():
+            raise ValueError("collides: boxes must be contiguous")
+        if boxes.device.type != "cuda" or (self._device is not None and boxes.device.index != self._device):
+            raise ValueError(f"collides: boxes must be on this handle's GPU (cuda:{self._device}), got {boxes.device}")
+        n = int(boxes.shape[0])
+        out = torch.empty(n, dtype=torch.uint8, device=boxes.device)
+        torch.cuda.current_stream(boxes.device).synchronize()
+        self._check(self.lib.se_hip_collide_boxes(self._h, boxes.data_ptr() if n else None, n, C.byref(test), m, out.data_ptr() if n else None))
+        self.sync()
+        return out
 
     def save(self, filename: str):
         """Octree::save of the reference (octree.hpp:898-914): same byte layout, entries sorted by key."""
