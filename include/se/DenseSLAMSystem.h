@@ -199,6 +199,12 @@ class DenseSLAMSystem {
   bool collidesWith(const int32_t* host_boxes, size_t n, const se_hip_collide_test& test, int32_t mode, uint8_t* host_status) {
     return ok(se_hip_collide_boxes_host(h_, host_boxes, (int64_t)n, &test, mode, host_status));
   }
+  /* Not in the reference's class (an addition of this mirror): the per-pixel body of raycastKernel for n rays of the caller's
+   * (host_rays[n][8]: origin xyz, direction xyz, near, far in metres) answered on the device map without getMap() --
+   * se_hip_cast_rays_host, definitions in se_hip.h.  host_out.hit[n][4], .normal[n][3], .status[n]; a null pointer: not wanted. */
+  bool castRays(const float* host_rays, size_t n, float mu, se_hip_ray_out& host_out) {
+    return ok(se_hip_cast_rays_host(h_, host_rays, (int64_t)n, mu, &host_out));
+  }
   /* vertex_ / normal_ of the last raycasting(): width*height packed xyz */
   bool getVertexNormal(std::vector<float>& vertex, std::vector<float>& normal) {
     const size_t n = (size_t)computation_size_.x() * computation_size_.y() * 3;

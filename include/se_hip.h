@@ -381,6 +381,50 @@ int se_hip_collide_boxes(se_hip_pipeline* p, const int32_t* device_boxes, int64_
 int se_hip_collide_boxes_host(se_hip_pipeline* p, const int32_t* host_boxes, int64_t n, const se_hip_collide_test* test, int32_t mode,
                               uint8_t* host_status);
 
+/* ---- batched ray casts against the resident map: the per-pixel body of the reference's raycastKernel (se_denseslam/src/rendering.cpp:51-90)
+ *      for N rays of the caller's at once, without getMap() -- simulated range sensors, line-of-sight checks, views from poses that are not
+ *      the tracked camera's.
+ * Ray: 8 floats, ox oy oz dx dy dz near far, in metres in the world frame (rays [n][8] float32).  For each ray, with o, d, near, far in place
+ *   of the camera's origin, pixel direction and planes:
+ *     1. the ray iterator (ray_iterator.hpp) over the map index from o along d within [near, far]: ray.next(), then t_min = ray.tcmin();
+ *     2. if t_min > 0: hit = raycast(volume, o, d, t_min, ray.tmax(), mu, step, largestep), the field's march (kfusion for SDF, bfusion
+ *        for OFusion), step = dim / size, largestep = 8 * step (as the camera raycast sets them);
+ *     3. if hit.w > 0: normal = normalized(-grad(hit)) for SDF, normalized(+grad(hit)) for OFusion (Octree::grad, scaled by 0.5 * dim / size);
+ *        a zero gradient gives INVALID (-2, 0, 0).
+ *   d is used as given: it is not normalised on the device, so a caller who normalised it in float (as the camera does, f3_normalized) gets
+ *   the camera raycast's bits.  near > far and near <= 0 are not refused: they take whatever the reference does (t_min clamping, then the
+ *   t_min > 0 test).  There is no frame gate (the camera path's frame > 2 does not apply).
+ * Outputs (a null pointer means "not wanted"; at least one must be set):
+ *   hit[n][4]     x y z t: the V4f raycast returns, {0, 0, 0, 0} when it finds no crossing (and for a ray that does not reach step 2);
+ *   normal[n][3]  as in step 3; (-2, 0, 0) without a hit;
+ *   status[n]     (uint8) bit 0 (1) VALID: the ray passed the checks below; bit 1 (2) ENTERED: the iterator returned an allocated block at
+ *                 t_min > 0, the march ran; bit 2 (4) HIT: hit.w > 0; bit 3 (8) NORMAL: the gradient at the hit is not zero.
+ * Defined beyond the reference -- INVALID rays: status 0, hit {0, 0, 0, 0}, normal (-2, 0, 0), no map memory read:
+ *   - any non-finite value among the 8 floats;
+ *   - |s * o| >= 2^20 on any axis, s = (float)size / dim (the limit of se_hip_query_points);
+ *   - a direction whose squared norm (dx * dx + dy * dy) + dz * dz lies outside [0.98, 1.02] (float arithmetic, no FMA).  The band bounds
+ *     the march: a near-zero direction would mean an effectively unbounded number of steps for one ray.
+ * mu (kfusion's march uses it; one value per call) must be finite and > 0.  The first-leaf search stops after 4096 trips, as the camera
+ * raycast's does.
+ * Both entries answer for the map after everything enqueued before them (a scan that ran on the side stream included), refuse n < 0, a null
+ * rays pointer with n > 0, no output or a bad mu with SE_HIP_E_INVALID (n == 0 is a no-op), and report a sticky SE_HIP_E_CAPACITY like the
+ * other read-back calls.  They leave the map, the vertex / normal images and the image ring, a deferred raycast (not launched by them), the
+ * launch counters (SE_HIP_K_*) and the timing sums alone.
+ *   se_hip_cast_rays       device arrays; enqueued on the handle's stream, asynchronous like the stage calls (batches beyond 2^24 rays are
+ *                          split into several launches).
+ *   se_hip_cast_rays_host  host arrays; staged through a device buffer the handle keeps (and grows); synchronises before it returns. */
+#define SE_HIP_RAY_VALID 1
+#define SE_HIP_RAY_ENTERED 2
+#define SE_HIP_RAY_HIT 4
+#define SE_HIP_RAY_NORMAL 8
+typedef struct se_hip_ray_out {
+  float* hit;       /* [n][4] */
+  float* normal;    /* [n][3] */
+  uint8_t* status;  /* [n]    */
+} se_hip_ray_out;
+int se_hip_cast_rays(se_hip_pipeline* p, const float* device_rays, int64_t n, float mu, const se_hip_ray_out* device_out);
+int se_hip_cast_rays_host(se_hip_pipeline* p, const float* host_rays, int64_t n, float mu, const se_hip_ray_out* host_out);
+
 /* ---- "next" row f-4: Octree::save (se_core/include/se/octree.hpp:898-914, io/se_serialise.hpp:54-86),
  *      written straight from the device map in the reference's byte layout:
  *        int32 size, float dim, uint64 n_nodes, n_nodes x {uint64 code, int32 side, value_[8]},

@@ -24,6 +24,7 @@
 #include "se_mesh_kernels.h"
 #include "se_query_kernels.h"
 #include "se_collide_kernels.h"
+#include "se_ray_kernels.h"
 
 int flush_pending_raycast(se_hip_pipeline* p);   // (defined next to se_hip_frame)
 
@@ -149,6 +150,8 @@ struct se_hip_pipeline {
   size_t query_cap = 0;
   unsigned char* collide_buf = nullptr; // se_hip_collide_boxes_host: device staging of the boxes and the statuses, grown on demand
   size_t collide_cap = 0;
+  unsigned char* ray_buf = nullptr;     // se_hip_cast_rays_host: device staging of the rays and the outputs, grown on demand
+  size_t ray_cap = 0;
   bool filter_input = false;   // preprocessing(..., filterInput): tracking sees the bilateral-filtered depth
   bool occ_commit_due = false; // the next sweep kernel must publish the scan's occupancy bits
   OccLists occ_lists{nullptr, 0, 0};   // ... of these key lists (own list, or every rank's after se_hip_alloc_commit)
@@ -308,16 +311,10 @@ M4 rigid_inverse(const M4& a) {   // raycast_pose_.inverse() of a rigid transfor
 
 struct RayLaunchArgs { RayArgs a; size_t smem; dim3 grid; };
 
-// RayArgs of raycastKernel for pose * K^-1 (DenseSLAMSystem.cpp:197-200)
-RayLaunchArgs make_ray_args(se_hip_pipeline* p, const float pose_cm[16], const float k[4], float mu) {
-  RayLaunchArgs L{};
+// The fields of RayArgs that depend on the map and mu only (raycastKernel's step / largestep, the iterator's constants, the LDS staging),
+// shared by the camera raycast and the batch of se_hip_cast_rays; the smem size that goes with them
+size_t ray_map_args(se_hip_pipeline* p, float mu, RayArgs& a) {
   const DevMap& m = p->map;
-  const M4 view = mul(from_colmajor(pose_cm), inverse_camera_matrix(k));  // DenseSLAMSystem.cpp:199
-  RayArgs& a = L.a;
-  for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) a.view3[i * 3 + j] = view.m[i][j]; a.org[i] = view.m[i][3]; }
-  a.nearp = 0.4f; a.farp = 4.0f;  // constant_parameters.h:22-32
-  a.near_n = a.nearp / m.dim; a.far_n = a.farp / m.dim;
-  for (int i = 0; i < 3; ++i) a.scaled_origin[i] = a.org[i] / m.dim + 1.f;
   a.mu = mu;
   a.step = m.dim / (float)m.size;           // DenseSLAMSystem.cpp:197
   a.largestep = a.step * 8;                 // step * BLOCK_SIDE
@@ -325,7 +322,6 @@ RayLaunchArgs make_ray_args(se_hip_pipeline* p, const float pose_cm[16], const f
   a.grad_scale = 0.5f * m.dim / (float)m.size;  // octree.hpp:736
   a.epsilon = exp2f(-(float)p->max_level);  // ray_iterator.hpp:63
   a.min_scale = 23 - p->leaf_level;         // ray_iterator.hpp:62
-  a.W = p->cfg.width; a.H = p->cfg.height; a.row_begin = p->row_begin; a.row_end = p->row_end;
   // occupancy levels staged in LDS: levels 1..5 (4.7 KB; measured: level 6 = +32 KB costs more
   // occupancy and staging time than the leaf-level bit tests it saves) unless overridden
   int cl = p->ray_cache_levels >= 0 ? p->ray_cache_levels : 5;
@@ -336,6 +332,21 @@ RayLaunchArgs make_ray_args(se_hip_pipeline* p, const float pose_cm[16], const f
   a.cache_codes = 2u << (3 * cl);
   a.has_deep = cl < p->leaf_level - 1 ? 1 : 0;
   a.stack_depth = p->leaf_level;
+  return ((size_t)a.cache_words + (size_t)2 * a.stack_depth * SE_WG_RAY) * sizeof(uint32_t);
+}
+
+// RayArgs of raycastKernel for pose * K^-1 (DenseSLAMSystem.cpp:197-200)
+RayLaunchArgs make_ray_args(se_hip_pipeline* p, const float pose_cm[16], const float k[4], float mu) {
+  RayLaunchArgs L{};
+  const DevMap& m = p->map;
+  const M4 view = mul(from_colmajor(pose_cm), inverse_camera_matrix(k));  // DenseSLAMSystem.cpp:199
+  RayArgs& a = L.a;
+  for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) a.view3[i * 3 + j] = view.m[i][j]; a.org[i] = view.m[i][3]; }
+  a.nearp = 0.4f; a.farp = 4.0f;  // constant_parameters.h:22-32
+  a.near_n = a.nearp / m.dim; a.far_n = a.farp / m.dim;
+  for (int i = 0; i < 3; ++i) a.scaled_origin[i] = a.org[i] / m.dim + 1.f;
+  L.smem = ray_map_args(p, mu, a);
+  a.W = p->cfg.width; a.H = p->cfg.height; a.row_begin = p->row_begin; a.row_end = p->row_end;
   a.tile_cost = p->prio_hint ? p->tile_cost : nullptr;
   a.prio_thr = p->prio_thr;
   a.cost_shift = std::max(0, p->leaf_level - 6);
@@ -372,11 +383,21 @@ RayLaunchArgs make_ray_args(se_hip_pipeline* p, const float pose_cm[16], const f
     if (wl) { hipStreamSynchronize(p->stream); if (FILE* f = std::fopen(std::getenv("SE_HIP_WLOG"), "wb")) { std::fwrite(wl, 8, 4 * 32768, f); std::fclose(f); } std::memset(wl, 0, 4 * 8 * 32768); }
   }
 #endif
-  L.smem = ((size_t)a.cache_words + (size_t)2 * a.stack_depth * SE_WG_RAY) * sizeof(uint32_t);
   const int tiles_x = (a.W + SE_TILE_W - 1) / SE_TILE_W, tiles_y = (a.row_end - a.row_begin + SE_TILE_H - 1) / SE_TILE_H;
   // one workgroup per tile pair, in whole rounds over the compute units (workgroups of the last round beyond the list idle)
   const int n_pairs = (tiles_x * tiles_y + 1) / 2;
   L.grid = dim3((unsigned)(((n_pairs + p->n_cus - 1) / p->n_cus) * p->n_cus));
+  return L;
+}
+
+// RayArgs of se_hip_cast_rays: the map's constants; the camera, the image and every scheduling aid off (gate, tile costs, ray order, issue
+// priorities, beam start, the OFusion leap, wave records).  The kernel forms the per-ray fields (scaled_origin, near_n, far_n) itself.
+RayLaunchArgs make_batch_ray_args(se_hip_pipeline* p, float mu) {
+  RayLaunchArgs L{};
+  RayArgs& a = L.a;
+  L.smem = ray_map_args(p, mu, a);
+  a.gate = nullptr; a.tile_cost = nullptr; a.ray_order = nullptr; a.prio_thr = nullptr; a.wlog = nullptr; a.leap_bits = nullptr;
+  a.beam = 0;
   return L;
 }
 
@@ -716,6 +737,7 @@ int se_hip_destroy(se_hip_pipeline* p) {
   if (p->mesh_ctr) hipFree(p->mesh_ctr);
   if (p->query_buf) hipFree(p->query_buf);
   if (p->collide_buf) hipFree(p->collide_buf);
+  if (p->ray_buf) hipFree(p->ray_buf);
   for (int i = 0; i < se_hip_pipeline::kIn; ++i) { if (p->in_host[i]) hipHostFree(p->in_host[i]); if (p->in_done[i]) hipEventDestroy(p->in_done[i]); }
   if (p->own_side && p->side) hipStreamDestroy(p->side);
   if (p->ev_sweep) hipEventDestroy(p->ev_sweep);
@@ -2025,6 +2047,90 @@ int se_hip_collide_boxes_host(se_hip_pipeline* p, const int32_t* host_boxes, int
   launch_collide(p, (const int32_t*)b, n, test, mode, b + un * 6 * sizeof(int32_t));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(host_status, b + un * 6 * sizeof(int32_t), un, hipMemcpyDeviceToHost, p->stream));
+  // (synchronises; a sticky overflow is reported as the other read-back calls report it)
+  return fetch_counters(p);
+}
+
+
+// ------------------------------------------------------------------------------------ batched ray casts
+static_assert(SE_HIP_RAY_VALID == SE_R_VALID && SE_HIP_RAY_ENTERED == SE_R_ENTERED && SE_HIP_RAY_HIT == SE_R_HIT && SE_HIP_RAY_NORMAL == SE_R_NORMAL,
+              "status bits of se_hip_ray_out");
+namespace {
+int ray_args(const float* rays, int64_t n, float mu, const se_hip_ray_out* out) {
+  if (n < 0) return fail(SE_HIP_E_INVALID, "se_hip_cast_rays: n < 0");
+  if (n > 0 && !rays) return fail(SE_HIP_E_INVALID, "se_hip_cast_rays: null rays");
+  if (!out || !(out->hit || out->normal || out->status)) return fail(SE_HIP_E_INVALID, "se_hip_cast_rays: no output requested");
+  if (!(std::isfinite(mu) && mu > 0.f)) return fail(SE_HIP_E_INVALID, "se_hip_cast_rays: mu must be finite and > 0");
+  return SE_HIP_OK;
+}
+// Launches of at most SE_RAY_MAX_LAUNCH rays (each a grid of whole workgroups: every thread reaches the staging barrier)
+void launch_rays(se_hip_pipeline* p, const float* rays, int64_t n, float mu, const CastRayOut& o) {
+  const DevMap& m = p->map;
+  const RayLaunchArgs L = make_batch_ray_args(p, mu);
+  const float s = (float)m.size / m.dim;   // VolumeTemplate: inverseVoxelSize = _size / _dim (the point queries' limit)
+  const bool of = p->cfg.field_type != SE_HIP_FIELD_SDF;
+  const bool shallow = !L.a.has_deep;
+  const size_t nb = (size_t)(m.size >> 3);
+  const bool o32 = m.dense && shallow && nb * nb * nb * (size_t)SE_BRICK_STRIDE * sizeof(float) <= ((size_t)4 << 30);   // (as se_hip_raycast)
+  for (int64_t b = 0; b < n; b += SE_RAY_MAX_LAUNCH) {
+    const long long k = (long long)std::min<int64_t>(n - b, SE_RAY_MAX_LAUNCH);
+    const CastRayOut ob{o.hit ? o.hit + 4 * b : nullptr, o.normal ? o.normal + 3 * b : nullptr, o.status ? o.status + b : nullptr};
+    const dim3 grid((unsigned)((k + SE_WG_RAY - 1) / SE_WG_RAY)), block(SE_WG_RAY);
+    const float* rb = rays + 8 * b;
+#define SE_CR(OF, DN, SH, O3) hipLaunchKernelGGL((k_cast_rays<OF, DN, SH, O3>), grid, block, L.smem, p->stream, m, L.a, rb, k, ob, s)
+    if (!of) {
+      if (o32) SE_CR(false, true, true, true);
+      else if (m.dense) { if (shallow) SE_CR(false, true, true, false); else SE_CR(false, true, false, false); }
+      else { if (shallow) SE_CR(false, false, true, false); else SE_CR(false, false, false, false); }
+    } else {
+      if (o32) SE_CR(true, true, true, true);
+      else if (m.dense) { if (shallow) SE_CR(true, true, true, false); else SE_CR(true, true, false, false); }
+      else { if (shallow) SE_CR(true, false, true, false); else SE_CR(true, false, false, false); }
+    }
+#undef SE_CR
+  }
+}
+}  // namespace
+
+// (InFrame: a deferred raycast stays deferred -- the batch reads the map, which the deferred launch does not change)
+int se_hip_cast_rays(se_hip_pipeline* p, const float* device_rays, int64_t n, float mu, const se_hip_ray_out* device_out) {
+  if (!p) return fail(SE_HIP_E_INVALID, "null handle");
+  InFrame guard(p);
+  if (int r = check(p)) return r;
+  if (int r = ray_args(device_rays, n, mu, device_out)) return r;
+  if (int r = join_scan(p)) return r;
+  if (int r = check_overflow(p)) return r;
+  if (n == 0) return SE_HIP_OK;
+  launch_rays(p, device_rays, n, mu, CastRayOut{device_out->hit, device_out->normal, device_out->status});
+  HIP_TRY(hipGetLastError());
+  return SE_HIP_OK;
+}
+
+int se_hip_cast_rays_host(se_hip_pipeline* p, const float* host_rays, int64_t n, float mu, const se_hip_ray_out* host_out) {
+  if (!p) return fail(SE_HIP_E_INVALID, "null handle");
+  InFrame guard(p);
+  if (int r = check(p)) return r;
+  if (int r = ray_args(host_rays, n, mu, host_out)) return r;
+  if (int r = join_scan(p)) return r;
+  if (n == 0) return fetch_counters(p);
+  // staging: [rays n x 8][hit n x 4][normal n x 3][status n], only the outputs asked for (floats first: 4-byte aligned)
+  const size_t un = (size_t)n;
+  const size_t sz[3] = {host_out->hit ? 4 * un * 4 : 0, host_out->normal ? 3 * un * 4 : 0, host_out->status ? un : 0};
+  size_t off[3], need = 8 * un * 4;
+  for (int k = 0; k < 3; ++k) { off[k] = need; need += sz[k]; }
+  if (need > p->ray_cap) {
+    if (p->ray_buf) { HIP_TRY(hipStreamSynchronize(p->stream)); hipFree(p->ray_buf); p->ray_buf = nullptr; p->ray_cap = 0; }
+    HIP_TRY(hipMalloc((void**)&p->ray_buf, need));
+    p->ray_cap = need;
+  }
+  unsigned char* b = p->ray_buf;
+  HIP_TRY(hipMemcpyAsync(b, host_rays, 8 * un * 4, hipMemcpyHostToDevice, p->stream));
+  auto dev = [&](int k) { return sz[k] ? b + off[k] : nullptr; };
+  launch_rays(p, (const float*)b, n, mu, CastRayOut{(float*)dev(0), (float*)dev(1), (uint8_t*)dev(2)});
+  HIP_TRY(hipGetLastError());
+  void* dst[3] = {host_out->hit, host_out->normal, host_out->status};
+  for (int k = 0; k < 3; ++k)
+    if (sz[k]) HIP_TRY(hipMemcpyAsync(dst[k], b + off[k], sz[k], hipMemcpyDeviceToHost, p->stream));
   // (synchronises; a sticky overflow is reported as the other read-back calls report it)
   return fetch_counters(p);
 }

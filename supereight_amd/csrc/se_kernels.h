@@ -1333,7 +1333,7 @@ __device__ __forceinline__ f3 se_grad(const DevMap& m, const FieldConst fc, f3 p
   return g;  // the caller applies (0.5f * dim / size)
 }
 
-struct RaySpan { float tcmin, tmax; int trips; };
+struct RaySpan { float tcmin, tmax; int trips; bool found = false; };   // found: se_first_leaf stopped at a leaf (the batch raycast's status bit)
 // se::ray_iterator (se_core/include/se/ray_iterator.hpp:53-250) up to the first leaf, on the occupancy
 // bits.  Same float arithmetic on t and pos as the reference; what is restated is the integer side:
 //  * a node is its heap code (occ_code), the child test is one bit of one word;
@@ -1472,7 +1472,7 @@ __device__ __forceinline__ RaySpan se_first_leaf(const DevMap& m, const RayArgs&
     if (scale < 23) SE_TRIP_PREFETCH();
   }
 #undef SE_TRIP_PREFETCH
-  return {t_min * m.dim, tmax_m, guard};
+  return {t_min * m.dim, tmax_m, guard, guard < max_trips && scale < 23};   // (the loop's condition still holds only after the break at a leaf)
 }
 
 // The same iterator without its stack (r04).  For a ray that is regular at set-up (it enters the volume before it

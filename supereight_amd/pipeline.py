@@ -38,6 +38,15 @@ class _QueryOut(C.Structure):
     _fields_ = [("fine", C.c_void_p), ("coarse", C.c_void_p), ("interp", C.c_void_p), ("grad", C.c_void_p), ("status", C.c_void_p)]
 
 
+class _RayOut(C.Structure):
+    """se_hip_ray_out of include/se_hip.h: output addresses, 0 = not wanted."""
+    _fields_ = [("hit", C.c_void_p), ("normal", C.c_void_p), ("status", C.c_void_p)]
+
+
+# status bits of se_hip_cast_rays
+RAY_VALID, RAY_ENTERED, RAY_HIT, RAY_NORMAL = 1, 2, 4, 8
+
+
 class _CollideTest(C.Structure):
     """se_hip_collide_test of include/se_hip.h."""
     _fields_ = [("threshold", C.c_float), ("occupied_above", C.c_int32)]
@@ -120,6 +129,8 @@ EXPORTS = {
     "se_hip_query_points_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_QueryOut)]),
     "se_hip_collide_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
     "se_hip_collide_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
+    "se_hip_cast_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.POINTER(_RayOut)]),
+    "se_hip_cast_rays_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.POINTER(_RayOut)]),
 }
 
 
@@ -652,6 +663,88 @@ class DenseSLAMPipeline:
         self._check(self.lib.se_hip_collide_boxes(self._h, boxes.data_ptr() if n else None, n, C.byref(test), m, out.data_ptr() if n else None))
         self.sync()
         return out
+
+    _RAY_OUTPUTS = (("hit", (4,), np.float32), ("normal", (3,), np.float32), ("status", (), np.uint8))
+
+    def cast_rays(self, origins, directions, near=0.4, far=4.0, *, mu: float, normalize: bool = False, hit: bool = True, normal: bool = True,
+                  status: bool = True) -> dict:
+        """Batched ray casts (se_hip_cast_rays, include/se_hip.h): for each ray, the reference's raycastKernel body from `origins` along
+        `directions` within [near, far] (metres, world frame) -- hit (x, y, z, t), normal, and status bits (RAY_VALID, RAY_ENTERED, RAY_HIT,
+        RAY_NORMAL).  Returns a dict of the outputs asked for.  near / far: a scalar or one value per ray.  Directions are used as given
+        (the library refuses rays whose squared norm lies outside [0.98, 1.02]); normalize=True divides them by their norm first, in the
+        caller's framework (numpy: the float32 arithmetic of Eigen's normalized(); torch: torch's).  mu: the truncation distance of the
+        SDF march, as raycasting() takes it.
+          - numpy float32 [N, 3] arrays: through the host entry; numpy arrays out.
+          - torch float32 [N, 3] tensors on this handle's GPU: packed to [N, 8] on the device, through the device entry; outputs are torch
+            tensors on the same device.  The caller's current torch stream is synchronised first, and the handle before the tensors are
+            returned.
+        Anything else raises TypeError / ValueError before any library call."""
+        want = {"hit": hit, "normal": normal, "status": status}
+        if not any(want.values()):
+            raise ValueError("cast_rays: no output requested")
+        mu = float(mu)
+        if not (np.isfinite(np.float32(mu)) and mu > 0):
+            raise ValueError(f"cast_rays: mu must be finite and > 0, got {mu!r}")
+        if type(origins) is np.ndarray and type(directions) is np.ndarray:
+            for name, a in (("origins", origins), ("directions", directions)):
+                if a.dtype != np.float32:
+                    raise TypeError(f"cast_rays: {name} must be float32, got {a.dtype}")
+                if a.ndim != 2 or a.shape[1] != 3:
+                    raise ValueError(f"cast_rays: {name} must have shape [N, 3], got {list(a.shape)}")
+            n = origins.shape[0]
+            if directions.shape[0] != n:
+                raise ValueError(f"cast_rays: {n} origins but {directions.shape[0]} directions")
+            d = directions
+            if normalize:
+                z = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+                d = np.where((z > 0)[:, None], d / np.sqrt(z)[:, None], d).astype(np.float32)
+            rays = np.empty((n, 8), np.float32)
+            rays[:, 0:3] = origins
+            rays[:, 3:6] = d
+            for j, (name, v) in ((6, ("near", near)), (7, ("far", far))):
+                v = np.asarray(v)
+                if v.ndim == 0 or v.shape == (n,):
+                    rays[:, j] = v.astype(np.float32)
+                else:
+                    raise ValueError(f"cast_rays: {name} must be a scalar or have shape [{n}], got {list(v.shape)}")
+            res = {k: np.empty((n,) + shp, dt) for k, shp, dt in self._RAY_OUTPUTS if want[k]}
+            out = _RayOut(*(res[k].ctypes.data if k in res else None for k, _, _ in self._RAY_OUTPUTS))
+            self._check(self.lib.se_hip_cast_rays_host(self._h, rays.ctypes.data if n else None, n, mu, C.byref(out)))
+            return res
+        torch = _torch_module(origins)
+        if torch is None or _torch_module(directions) is None:
+            raise TypeError("cast_rays: origins and directions must both be numpy float32 arrays or both torch tensors on the GPU, got "
+                            f"{type(origins).__name__} and {type(directions).__name__}")
+        for name, a in (("origins", origins), ("directions", directions)):
+            if a.dtype != torch.float32:
+                raise TypeError(f"cast_rays: {name} must be float32, got {a.dtype}")
+            if a.dim() != 2 or a.shape[1] != 3:
+                raise ValueError(f"cast_rays: {name} must have shape [N, 3], got {list(a.shape)}")
+            if a.device.type != "cuda" or (self._device is not None and a.device.index != self._device):
+                raise ValueError(f"cast_rays: {name} must be on this handle's GPU (cuda:{self._device}), got {a.device}")
+        n = int(origins.shape[0])
+        if int(directions.shape[0]) != n:
+            raise ValueError(f"cast_rays: {n} origins but {int(directions.shape[0])} directions")
+        dev = origins.device
+        d = directions
+        if normalize:
+            z = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+            d = torch.where((z > 0)[:, None], d / torch.sqrt(z)[:, None], d)
+        rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        rays[:, 0:3] = origins
+        rays[:, 3:6] = d
+        for j, name, v in ((6, "near", near), (7, "far", far)):
+            v = v if _torch_module(v) is not None else torch.as_tensor(np.asarray(v, np.float32))
+            if v.dim() != 0 and tuple(v.shape) != (n,):
+                raise ValueError(f"cast_rays: {name} must be a scalar or have shape [{n}], got {list(v.shape)}")
+            rays[:, j] = v.to(device=dev, dtype=torch.float32)
+        dt = {np.float32: torch.float32, np.uint8: torch.uint8}
+        res = {k: torch.empty((n,) + shp, dtype=dt[npdt], device=dev) for k, shp, npdt in self._RAY_OUTPUTS if want[k]}
+        out = _RayOut(*(res[k].data_ptr() if k in res else None for k, _, _ in self._RAY_OUTPUTS))
+        torch.cuda.current_stream(dev).synchronize()
+        self._check(self.lib.se_hip_cast_rays(self._h, rays.data_ptr() if n else None, n, mu, C.byref(out)))
+        self.sync()
+        return res
 
     def save(self, filename: str):
         """Octree::save of the reference (octree.hpp:898-914): same byte layout, entries sorted by key."""
