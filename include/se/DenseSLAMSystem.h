@@ -205,6 +205,12 @@ class DenseSLAMSystem {
   bool castRays(const float* host_rays, size_t n, float mu, se_hip_ray_out& host_out) {
     return ok(se_hip_cast_rays_host(h_, host_rays, (int64_t)n, mu, &host_out));
   }
+  /* Not in the reference's class (an addition of this mirror): the triangles dump_mesh() would write, for the allocated blocks a region and up to
+   * 64 views select, grouped per block in host memory -- se_hip_mesh_blocks_host, definitions in se_hip.h.  False (SE_HIP_E_CAPACITY) when
+   * host_out is too small: host_out.header[0] and [1] then give the sizes needed. */
+  bool meshBlocks(const se_hip_mesh_select& select, se_hip_mesh_out& host_out) {
+    return ok(se_hip_mesh_blocks_host(h_, &select, &host_out));
+  }
   /* vertex_ / normal_ of the last raycasting(): width*height packed xyz */
   bool getVertexNormal(std::vector<float>& vertex, std::vector<float>& normal) {
     const size_t n = (size_t)computation_size_.x() * computation_size_.y() * 3;

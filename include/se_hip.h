@@ -451,6 +451,59 @@ int se_hip_mesh_download(se_hip_pipeline* p, float* host_triangles, int64_t capa
 /* dump_mesh(filename): ASCII VTK polydata in writeVtkMesh's format, triangles sorted for reproducibility */
 int se_hip_dump_mesh(se_hip_pipeline* p, const char* filename);
 
+/* ---- live meshing: the triangles of the blocks that a region and a set of views select, grouped per block
+ * The same cells, vertices and triangles as se_hip_mesh_download, produced in one pass on the handle's stream, for a viewer or a mesh
+ * publisher that replaces exactly the blocks that may have changed.
+ * Selection (se_hip_mesh_select, host memory, read before the call returns):
+ *   lo, hi    a half-open box in voxels.  A block is in the region if its 8^3 voxels intersect it; lo = 0, hi = size is the whole volume.
+ *             Coordinates outside the volume are clamped; an empty or inverted box selects nothing.
+ *   n_views   0 .. SE_HIP_MESH_MAX_VIEWS.  0: the region alone decides.  Otherwise a block must also be possibly touched by at least one of
+ *   views[]   the views: camera-to-world pose (column-major, as the stage calls take it), k = fx fy cx cy, image width and height.  The test
+ *             is conservative -- a superset of the blocks with a voxel of their 9^3 dependency box (own voxels plus the +1 layer the cells
+ *             read) that integration would update under that view: the box's bounding sphere (centre 8 b + 4, radius rounded up to 9
+ *             voxels) against the half space z > 0 and the four side planes through pixel columns -1 and width, rows -1 and height.
+ *             fx or fy may be negative.
+ *   flags     SE_HIP_MESH_SKIP_EMPTY: selected blocks without a triangle are left out of the table (default: listed with count 0, so that a
+ *             receiver can delete a block whose surface has gone).
+ * Output (se_hip_mesh_out; device pointers for se_hip_mesh_blocks, host pointers for se_hip_mesh_blocks_host):
+ *   triangles[capacity_triangles][9]  floats, metres;
+ *   block_coords[capacity_blocks][3]  voxel coordinates of the block's corner; block_range[capacity_blocks][2]  first, count into triangles;
+ *   header[4]  blocks listed (the table size needed), triangles needed, blocks written, triangles written.
+ * Only whole blocks are written: the table rows [0, header[2]) and the triangles [0, header[3]), ranges disjoint and without gaps.  When a
+ * capacity is too small, header[0] and header[1] still give the sizes needed.  triangles == NULL with both capacities 0 is the sizing call.
+ * The order of the table's rows is unspecified.  Within a block the order is defined: cells x fastest, then y, then z, a cell's triangles
+ * in table order -- a block's payload is a function of the map alone.
+ * Both entries answer for the map after everything enqueued before them (a scan that ran on the side stream included), and leave the map,
+ * the images and the image ring, a deferred raycast, the launch counters and the timing sums alone.  They refuse null pointers where one
+ * is needed (header; triangles / the block arrays with a capacity > 0; views with n_views > 0), negative capacities, n_views out of range,
+ * unknown flags, non-finite view values, fx or fy == 0 and non-positive image sizes with SE_HIP_E_INVALID before any launch.
+ *   se_hip_mesh_blocks       asynchronous on the handle's stream; no synchronisation, no allocation per call; on overflow the header tells.
+ *   se_hip_mesh_blocks_host  staged through a device buffer the handle keeps (and grows); synchronises; SE_HIP_E_CAPACITY after filling
+ *                            what fitted (the sizing call returns SE_HIP_OK). */
+#define SE_HIP_MESH_MAX_VIEWS 64
+#define SE_HIP_MESH_SKIP_EMPTY 1u
+typedef struct se_hip_mesh_view {
+  float pose[16];   /* camera -> world, column-major */
+  float k[4];       /* fx, fy, cx, cy */
+  int32_t width, height;
+} se_hip_mesh_view;
+typedef struct se_hip_mesh_select {
+  int32_t lo[3], hi[3];
+  int32_t n_views;
+  uint32_t flags;
+  const se_hip_mesh_view* views;   /* [n_views] */
+} se_hip_mesh_select;
+typedef struct se_hip_mesh_out {
+  float* triangles;       /* [capacity_triangles][9] */
+  int64_t capacity_triangles;
+  int32_t* block_coords;  /* [capacity_blocks][3] */
+  int64_t* block_range;   /* [capacity_blocks][2] */
+  int64_t capacity_blocks;
+  int64_t* header;        /* [4] */
+} se_hip_mesh_out;
+int se_hip_mesh_blocks(se_hip_pipeline* p, const se_hip_mesh_select* select, const se_hip_mesh_out* device_out);
+int se_hip_mesh_blocks_host(se_hip_pipeline* p, const se_hip_mesh_select* select, const se_hip_mesh_out* host_out);
+
 /* ---- measurement (replaces TICK()/TOCK() + PerfStats, se_shared/timings.h:7-15) */
 #define SE_HIP_K_ALLOC_SCAN 0
 #define SE_HIP_K_ALLOC_COMMIT 1

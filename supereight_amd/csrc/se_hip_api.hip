@@ -150,6 +150,9 @@ struct se_hip_pipeline {
   size_t query_cap = 0;
   unsigned char* collide_buf = nullptr; // se_hip_collide_boxes_host: device staging of the boxes and the statuses, grown on demand
   size_t collide_cap = 0;
+  unsigned char* meshb_dev = nullptr;   // se_hip_mesh_blocks: view planes [20][64] floats, then the reservation state (3 x uint64); allocated on first use
+  unsigned char* meshb_buf = nullptr;   // se_hip_mesh_blocks_host: device staging of the outputs, grown on demand
+  size_t meshb_cap = 0;
   unsigned char* ray_buf = nullptr;     // se_hip_cast_rays_host: device staging of the rays and the outputs, grown on demand
   size_t ray_cap = 0;
   bool filter_input = false;   // preprocessing(..., filterInput): tracking sees the bilateral-filtered depth
@@ -738,6 +741,8 @@ int se_hip_destroy(se_hip_pipeline* p) {
   if (p->query_buf) hipFree(p->query_buf);
   if (p->collide_buf) hipFree(p->collide_buf);
   if (p->ray_buf) hipFree(p->ray_buf);
+  if (p->meshb_dev) hipFree(p->meshb_dev);
+  if (p->meshb_buf) hipFree(p->meshb_buf);
   for (int i = 0; i < se_hip_pipeline::kIn; ++i) { if (p->in_host[i]) hipHostFree(p->in_host[i]); if (p->in_done[i]) hipEventDestroy(p->in_done[i]); }
   if (p->own_side && p->side) hipStreamDestroy(p->side);
   if (p->ev_sweep) hipEventDestroy(p->ev_sweep);
@@ -1933,6 +1938,137 @@ int se_hip_download_nodes(se_hip_pipeline* p, uint64_t* code, uint32_t* side, fl
     if (x) std::memcpy(x + i * 8, hx.data() + s * 8, 8 * sizeof(float));
     if (y) std::memcpy(y + i * 8, hy.data() + s * 8, 8 * sizeof(float));
   }
+  return SE_HIP_OK;
+}
+
+
+// ------------------------------------------------------------------------------------ live meshing per block
+static_assert(SE_HIP_MESH_MAX_VIEWS == SE_MB_MAX_VIEWS && SE_HIP_MESH_SKIP_EMPTY == SE_MB_SKIP_EMPTY, "se_hip_mesh_select");
+namespace {
+int mesh_blocks_args(const se_hip_mesh_select* sel, const se_hip_mesh_out* out) {
+  if (!sel || !out) return fail(SE_HIP_E_INVALID, "se_hip_mesh_blocks: null selection or output");
+  if (!out->header) return fail(SE_HIP_E_INVALID, "se_hip_mesh_blocks: null header");
+  if (out->capacity_triangles < 0 || out->capacity_blocks < 0) return fail(SE_HIP_E_INVALID, "se_hip_mesh_blocks: negative capacity");
+  if (out->capacity_triangles > 0 && !out->triangles) return fail(SE_HIP_E_INVALID, "se_hip_mesh_blocks: null triangles with a capacity");
+  if (out->capacity_blocks > 0 && !(out->block_coords && out->block_range)) return fail(SE_HIP_E_INVALID, "se_hip_mesh_blocks: null block table with a capacity");
+  if (sel->n_views < 0 || sel->n_views > SE_HIP_MESH_MAX_VIEWS) return fail(SE_HIP_E_INVALID, "se_hip_mesh_blocks: n_views outside 0 .. SE_HIP_MESH_MAX_VIEWS");
+  if (sel->n_views > 0 && !sel->views) return fail(SE_HIP_E_INVALID, "se_hip_mesh_blocks: null views");
+  if (sel->flags & ~SE_HIP_MESH_SKIP_EMPTY) return fail(SE_HIP_E_INVALID, "se_hip_mesh_blocks: unknown flags");
+  for (int v = 0; v < sel->n_views; ++v) {
+    const se_hip_mesh_view& w = sel->views[v];
+    if (!finite_pose(w.pose, w.k)) return fail(SE_HIP_E_INVALID, "se_hip_mesh_blocks: non-finite view pose or intrinsics (or fx, fy == 0)");
+    if (w.width <= 0 || w.height <= 0) return fail(SE_HIP_E_INVALID, "se_hip_mesh_blocks: non-positive image size");
+  }
+  return SE_HIP_OK;
+}
+// The five planes of a view in voxel units, unit normals pointing inwards: a point q (voxels) is inside plane j if
+// n_j . q + d_j >= 0.  Camera frame: c = R^T (w - t); z > 0, and the side planes through pixel columns -1 and width, rows -1 and height
+// (u = fx x / z + cx).  Formed in double; the kernel evaluates them in float against a 9-voxel margin of which the sphere needs 6.93.
+void view_planes(const se_hip_mesh_view& w, double voxel, float out[SE_MB_VIEW_FLOATS]) {
+  double R[3][3], t[3];
+  for (int c = 0; c < 3; ++c) { for (int r = 0; r < 3; ++r) R[r][c] = w.pose[c * 4 + r]; t[c] = w.pose[12 + c]; }
+  const double fx = w.k[0], fy = w.k[1], cx = w.k[2], cy = w.k[3];
+  const double sx = fx > 0 ? 1.0 : -1.0, sy = fy > 0 ? 1.0 : -1.0;
+  const double xl = (-1.0 - cx) / fx, xr = ((double)w.width - cx) / fx, yt = (-1.0 - cy) / fy, yb = ((double)w.height - cy) / fy;
+  const double cam[5][3] = {{0, 0, 1}, {sx, 0, -sx * xl}, {-sx, 0, sx * xr}, {0, sy, -sy * yt}, {0, -sy, sy * yb}};
+  for (int j = 0; j < 5; ++j) {
+    const double len = std::sqrt(cam[j][0] * cam[j][0] + cam[j][1] * cam[j][1] + cam[j][2] * cam[j][2]);
+    double n[3], d = 0;   // world normal = R * camera normal; n . (w - t) with w = voxel * q
+    for (int r = 0; r < 3; ++r) { n[r] = (R[r][0] * cam[j][0] + R[r][1] * cam[j][1] + R[r][2] * cam[j][2]) / len; d -= n[r] * t[r]; }
+    for (int r = 0; r < 3; ++r) out[4 * j + r] = (float)n[r];
+    out[4 * j + 3] = (float)(d / voxel);
+  }
+}
+int ensure_mc_table(se_hip_pipeline* p) {
+  if (!p->mc_table_ready) {
+    signed char table[256][SE_MC_WIDTH];
+    se_mc_expand(table);
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(SE_MC_TRI), table, sizeof(table)));
+    p->mc_table_ready = true;
+  }
+  return SE_HIP_OK;
+}
+// Enqueues begin (state reset + the views' planes, 16 views per launch, passed by value), the meshing kernel and end (header) on the stream.
+int launch_mesh_blocks(se_hip_pipeline* p, const se_hip_mesh_select* sel, const se_hip_mesh_out& o) {
+  const DevMap& m = p->map;
+  if ((unsigned long long)m.cap_blocks * 2560ull >= (1ull << SE_MB_TRI_BITS) || (unsigned long long)m.cap_blocks >= (1ull << (64 - SE_MB_TRI_BITS)))
+    return fail(SE_HIP_E_INVALID, "se_hip_mesh_blocks: the block pool is too large for the packed reservation counter");
+  if (int r = ensure_mc_table(p)) return r;
+  const size_t plane_bytes = (size_t)SE_MB_VIEW_FLOATS * SE_MB_MAX_VIEWS * sizeof(float);
+  if (!p->meshb_dev) HIP_TRY(hipMalloc((void**)&p->meshb_dev, plane_bytes + 3 * sizeof(unsigned long long)));
+  float* planes = (float*)p->meshb_dev;
+  unsigned long long* state = (unsigned long long*)(p->meshb_dev + plane_bytes);
+  MeshBlocksArgs a{};
+  bool empty = false;
+  for (int i = 0; i < 3; ++i) {
+    a.lo[i] = std::max(sel->lo[i], 0); a.hi[i] = std::min(sel->hi[i], m.size);
+    empty = empty || a.lo[i] >= a.hi[i];
+  }
+  a.n_views = sel->n_views; a.flags = sel->flags; a.planes = planes; a.state = state;
+  a.tri = o.triangles; a.coords = o.block_coords; a.range = (long long*)o.block_range;
+  a.cap_tri = (unsigned long long)o.capacity_triangles; a.cap_blk = (unsigned long long)o.capacity_blocks;
+  const double voxel = (double)(m.dim / (float)m.size);
+  int base = 0;
+  do {
+    MeshViewChunk c;
+    const int n = std::min(sel->n_views - base, SE_MB_VIEWS_PER_LAUNCH);
+    for (int v = 0; v < n; ++v) view_planes(sel->views[base + v], voxel, c.v[v]);
+    hipLaunchKernelGGL(k_mesh_blocks_begin, dim3(1), dim3(64), 0, p->stream, c, base, n, planes, state);
+    base += SE_MB_VIEWS_PER_LAUNCH;
+  } while (base < sel->n_views);
+  if (!empty) {
+    // one wave per block, grid-stride beyond 4 096 workgroups as k_mesh (the block count lives on the device: the grid is sized by the list's capacity)
+    const int grid = grid_for((size_t)m.cap_blocks * 64, SE_WG, 4096);
+    if (m.dense) hipLaunchKernelGGL((k_mesh_blocks<true>), dim3(grid), dim3(SE_WG), 0, p->stream, m, a);
+    else hipLaunchKernelGGL((k_mesh_blocks<false>), dim3(grid), dim3(SE_WG), 0, p->stream, m, a);
+  }
+  hipLaunchKernelGGL(k_mesh_blocks_end, dim3(1), dim3(1), 0, p->stream, state, (long long*)o.header);
+  HIP_TRY(hipGetLastError());
+  return SE_HIP_OK;
+}
+}  // namespace
+
+// (InFrame: a deferred raycast stays deferred -- meshing reads the map, which the deferred launch does not change)
+int se_hip_mesh_blocks(se_hip_pipeline* p, const se_hip_mesh_select* select, const se_hip_mesh_out* device_out) {
+  if (!p) return fail(SE_HIP_E_INVALID, "null handle");
+  InFrame guard(p);
+  if (int r = check(p)) return r;
+  if (int r = mesh_blocks_args(select, device_out)) return r;
+  if (int r = join_scan(p)) return r;
+  if (int r = check_overflow(p)) return r;
+  return launch_mesh_blocks(p, select, *device_out);
+}
+
+int se_hip_mesh_blocks_host(se_hip_pipeline* p, const se_hip_mesh_select* select, const se_hip_mesh_out* host_out) {
+  if (!p) return fail(SE_HIP_E_INVALID, "null handle");
+  InFrame guard(p);
+  if (int r = check(p)) return r;
+  if (int r = mesh_blocks_args(select, host_out)) return r;
+  if (int r = join_scan(p)) return r;
+  // staging: [header 4 x int64][range capB x 2 int64][triangles capT x 9 floats][coords capB x 3 int32]
+  const size_t ct = (size_t)host_out->capacity_triangles, cb = (size_t)host_out->capacity_blocks;
+  const size_t off_range = 4 * sizeof(int64_t), off_tri = off_range + cb * 2 * sizeof(int64_t), off_coords = off_tri + ct * 9 * sizeof(float);
+  const size_t need = off_coords + cb * 3 * sizeof(int32_t);
+  if (need > p->meshb_cap) {
+    if (p->meshb_buf) { HIP_TRY(hipStreamSynchronize(p->stream)); hipFree(p->meshb_buf); p->meshb_buf = nullptr; p->meshb_cap = 0; }
+    HIP_TRY(hipMalloc((void**)&p->meshb_buf, need));
+    p->meshb_cap = need;
+  }
+  unsigned char* b = p->meshb_buf;
+  se_hip_mesh_out dev{ct ? (float*)(b + off_tri) : nullptr, host_out->capacity_triangles, cb ? (int32_t*)(b + off_coords) : nullptr,
+                      cb ? (int64_t*)(b + off_range) : nullptr, host_out->capacity_blocks, (int64_t*)b};
+  if (int r = launch_mesh_blocks(p, select, dev)) return r;
+  int64_t* h = host_out->header;
+  HIP_TRY(hipMemcpyAsync(h, b, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  if (h[2] > 0) {
+    HIP_TRY(hipMemcpyAsync(host_out->block_range, b + off_range, (size_t)h[2] * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyAsync(host_out->block_coords, b + off_coords, (size_t)h[2] * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
+  }
+  if (h[3] > 0) HIP_TRY(hipMemcpyAsync(host_out->triangles, b + off_tri, (size_t)h[3] * 9 * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+  // (synchronises; a sticky overflow is reported as the other read-back calls report it)
+  if (int r = fetch_counters(p)) return r;
+  if ((h[0] > h[2] || h[1] > h[3]) && (ct || cb)) return fail(SE_HIP_E_CAPACITY, "se_hip_mesh_blocks_host: output too small (the header gives the sizes needed)");
   return SE_HIP_OK;
 }
 

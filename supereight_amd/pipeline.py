@@ -43,6 +43,24 @@ class _RayOut(C.Structure):
     _fields_ = [("hit", C.c_void_p), ("normal", C.c_void_p), ("status", C.c_void_p)]
 
 
+class _MeshView(C.Structure):
+    """se_hip_mesh_view of include/se_hip.h."""
+    _fields_ = [("pose", C.c_float * 16), ("k", C.c_float * 4), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class _MeshSelect(C.Structure):
+    """se_hip_mesh_select of include/se_hip.h."""
+    _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("n_views", C.c_int32), ("flags", C.c_uint32), ("views", C.POINTER(_MeshView))]
+
+
+class _MeshOut(C.Structure):
+    """se_hip_mesh_out of include/se_hip.h: output addresses and capacities."""
+    _fields_ = [("triangles", C.c_void_p), ("capacity_triangles", C.c_int64), ("block_coords", C.c_void_p), ("block_range", C.c_void_p),
+                ("capacity_blocks", C.c_int64), ("header", C.c_void_p)]
+
+
+MESH_MAX_VIEWS, MESH_SKIP_EMPTY = 64, 1
+
 # status bits of se_hip_cast_rays
 RAY_VALID, RAY_ENTERED, RAY_HIT, RAY_NORMAL = 1, 2, 4, 8
 
@@ -131,6 +149,8 @@ EXPORTS = {
     "se_hip_collide_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
     "se_hip_cast_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.POINTER(_RayOut)]),
     "se_hip_cast_rays_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.POINTER(_RayOut)]),
+    "se_hip_mesh_blocks": (C.c_int, [C.c_void_p, C.POINTER(_MeshSelect), C.POINTER(_MeshOut)]),
+    "se_hip_mesh_blocks_host": (C.c_int, [C.c_void_p, C.POINTER(_MeshSelect), C.POINTER(_MeshOut)]),
 }
 
 
@@ -745,6 +765,93 @@ class DenseSLAMPipeline:
         self._check(self.lib.se_hip_cast_rays(self._h, rays.data_ptr() if n else None, n, mu, C.byref(out)))
         self.sync()
         return res
+
+    def _mesh_select(self, region, views, skip_empty):
+        """se_hip_mesh_select for mesh_blocks, checked here (TypeError / ValueError) so that nothing bad reaches the library."""
+        sel = _MeshSelect()
+        if region is None:
+            lo, hi = (0, 0, 0), (self.size,) * 3
+        else:
+            try:
+                lo, hi = region
+                lo, hi = tuple(lo), tuple(hi)
+            except TypeError:
+                raise TypeError("mesh_blocks: region must be (lo, hi), two triples of voxel coordinates") from None
+            if len(lo) != 3 or len(hi) != 3:
+                raise ValueError(f"mesh_blocks: region must be (lo, hi) with three coordinates each, got {len(lo)} and {len(hi)}")
+            for v in lo + hi:
+                if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                    raise TypeError(f"mesh_blocks: region coordinates must be integers (voxels), got {type(v).__name__}")
+                if not -2**31 <= int(v) < 2**31:
+                    raise ValueError(f"mesh_blocks: region coordinate {v} does not fit int32")
+        sel.lo[:], sel.hi[:] = [int(v) for v in lo], [int(v) for v in hi]
+        views = [] if views is None else list(views)
+        if len(views) > MESH_MAX_VIEWS:
+            raise ValueError(f"mesh_blocks: at most {MESH_MAX_VIEWS} views, got {len(views)}")
+        arr = (_MeshView * max(len(views), 1))()
+        for i, v in enumerate(views):
+            try:
+                pose, k = v[0], v[1]
+                w, h = (self.W, self.H) if len(v) == 2 else (v[2], v[3])
+            except (TypeError, IndexError, KeyError):
+                raise TypeError("mesh_blocks: a view is (pose 4x4 camera-to-world, k) or (pose, k, width, height)") from None
+            pose, k = np.asarray(pose), np.asarray(k)
+            for name, a, n in (("pose", pose, 16), ("k", k, 4)):
+                if a.dtype.kind not in "fiu":
+                    raise TypeError(f"mesh_blocks: view {i}: {name} must be numeric, got {a.dtype}")
+                if a.size != n:
+                    raise ValueError(f"mesh_blocks: view {i}: {name} must have {n} values, got {a.size}")
+            pose, k = pose.astype(np.float32).reshape(4, 4), k.astype(np.float32).reshape(4)
+            if not (np.isfinite(pose).all() and np.isfinite(k).all()):
+                raise ValueError(f"mesh_blocks: view {i}: non-finite pose or intrinsics")
+            if k[0] == 0 or k[1] == 0:
+                raise ValueError(f"mesh_blocks: view {i}: fx and fy must not be 0")
+            if isinstance(w, (bool, np.bool_)) or isinstance(h, (bool, np.bool_)) or not (isinstance(w, (int, np.integer)) and isinstance(h, (int, np.integer))):
+                raise TypeError(f"mesh_blocks: view {i}: width and height must be integers")
+            if w <= 0 or h <= 0:
+                raise ValueError(f"mesh_blocks: view {i}: image size must be positive, got {w} x {h}")
+            arr[i].pose[:] = pose.T.reshape(16).tolist()
+            arr[i].k[:] = k.tolist()
+            arr[i].width, arr[i].height = int(w), int(h)
+        sel.n_views, sel.flags = len(views), MESH_SKIP_EMPTY if skip_empty else 0
+        sel.views = C.cast(arr, C.POINTER(_MeshView))
+        return sel, arr
+
+    def mesh_blocks(self, region=None, views=None, skip_empty: bool = False, device: bool = False) -> dict:
+        """Live meshing per block (se_hip_mesh_blocks, include/se_hip.h): the marching-cubes triangles of the allocated blocks that intersect
+        `region` ((lo, hi) in voxels, half-open; None = the whole volume) and, if `views` is given, may have been touched by one of them --
+        up to 64 views, each (pose 4x4 camera-to-world, k) with this handle's image size or (pose, k, width, height).
+        Returns {"coords": [B, 3] int32 voxel coordinates of the block corners, "ranges": [B, 2] int64 (first, count) into "triangles",
+        "triangles": [T, 3, 3] float32 metres}.  A block's triangles are contiguous and in a defined order; blocks without a triangle are
+        listed with count 0 unless skip_empty.  numpy arrays through the host entry (a sizing call, then the real one); device=True: torch
+        tensors on this handle's GPU through the device entry.  Bad input raises TypeError / ValueError before any library call."""
+        sel, keep = self._mesh_select(region, views, bool(skip_empty))
+        head = np.zeros(4, np.int64)
+        if not device:
+            self._check(self.lib.se_hip_mesh_blocks_host(self._h, C.byref(sel), C.byref(_MeshOut(None, 0, None, None, 0, head.ctypes.data))))
+            nb, nt = int(head[0]), int(head[1])
+            coords, ranges, tris = np.empty((nb, 3), np.int32), np.empty((nb, 2), np.int64), np.empty((nt, 3, 3), np.float32)
+            if nb:
+                out = _MeshOut(tris.ctypes.data if nt else None, nt, coords.ctypes.data, ranges.ctypes.data, nb, head.ctypes.data)
+                self._check(self.lib.se_hip_mesh_blocks_host(self._h, C.byref(sel), C.byref(out)))
+                assert (head == (nb, nt, nb, nt)).all(), head
+            return {"coords": coords, "ranges": ranges, "triangles": tris}
+        import torch
+        dev = torch.device("cuda", self._device or 0)
+        torch.cuda.current_stream(dev).synchronize()
+        hd = torch.zeros(4, dtype=torch.int64, device=dev)
+        self._check(self.lib.se_hip_mesh_blocks(self._h, C.byref(sel), C.byref(_MeshOut(None, 0, None, None, 0, hd.data_ptr()))))
+        self.sync()
+        nb, nt = (int(v) for v in hd[:2].tolist())
+        coords = torch.empty((nb, 3), dtype=torch.int32, device=dev)
+        ranges = torch.empty((nb, 2), dtype=torch.int64, device=dev)
+        tris = torch.empty((nt, 3, 3), dtype=torch.float32, device=dev)
+        if nb:
+            out = _MeshOut(tris.data_ptr() if nt else None, nt, coords.data_ptr(), ranges.data_ptr(), nb, hd.data_ptr())
+            self._check(self.lib.se_hip_mesh_blocks(self._h, C.byref(sel), C.byref(out)))
+            self.sync()
+            assert hd.tolist() == [nb, nt, nb, nt], hd.tolist()
+        return {"coords": coords, "ranges": ranges, "triangles": tris}
 
     def save(self, filename: str):
         """Octree::save of the reference (octree.hpp:898-914): same byte layout, entries sorted by key."""

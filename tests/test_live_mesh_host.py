@@ -1,0 +1,158 @@
+"""Live meshing per block, the parts that need no GPU: the C ABI's declarations, mesh_blocks' argument checks, the selection rule restated
+in float64 against the oracle (no block whose triangles changed lies outside the selection), LiveMesh driven by a source built from the
+oracle's full mesh, and the C++ mirror program that calls DenseSLAMSystem::meshBlocks."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle.binding import OFUSION, SDF, OraclePipeline
+from supereight_amd import pipeline as P
+from supereight_amd.livemesh import LiveMesh
+from supereight_amd.synthetic import StressStream
+from tests import live_mesh_util as L
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_header_and_ctypes_declare_the_entries():
+    h = open(os.path.join(ROOT, "include", "se_hip.h")).read()
+    for name in ("se_hip_mesh_blocks", "se_hip_mesh_blocks_host"):
+        assert re.search(r"int " + name + r"\(se_hip_pipeline\* p, const se_hip_mesh_select\* select, const se_hip_mesh_out\* \w+\);", h), name
+        res, args = P.EXPORTS[name]
+        assert res is C.c_int and len(args) == 3 and args[0] is C.c_void_p
+        assert args[1]._type_ is P._MeshSelect and args[2]._type_ is P._MeshOut
+    for s in ("} se_hip_mesh_select;", "} se_hip_mesh_out;", "} se_hip_mesh_view;"):
+        assert s in h, s
+    assert re.search(r"#define SE_HIP_MESH_MAX_VIEWS 64\b", h) and P.MESH_MAX_VIEWS == 64
+    assert re.search(r"#define SE_HIP_MESH_SKIP_EMPTY 1u?\b", h) and P.MESH_SKIP_EMPTY == 1
+    # the structs as the header lays them out (LP64): view 16 + 4 floats + 2 int32; select 6 + 1 int32, uint32, pointer; out 6 x 8 bytes
+    assert C.sizeof(P._MeshView) == 88 and C.sizeof(P._MeshSelect) == 40 and C.sizeof(P._MeshOut) == 48
+    assert [f[0] for f in P._MeshOut._fields_] == ["triangles", "capacity_triangles", "block_coords", "block_range", "capacity_blocks", "header"]
+    assert [f[0] for f in P._MeshSelect._fields_] == ["lo", "hi", "n_views", "flags", "views"]
+
+
+class _NoLibrary:
+    def __getattr__(self, name):
+        raise AssertionError(f"library call {name} after bad input")
+
+
+def _bare(size=256, W=160, H=120):
+    p = P.DenseSLAMPipeline.__new__(P.DenseSLAMPipeline)
+    p.lib, p._h, p.size, p.dim, p.W, p.H, p._device = _NoLibrary(), None, size, 4.8, W, H, 0
+    return p
+
+
+def test_mesh_blocks_refuses_bad_input_before_any_library_call():
+    p = _bare()
+    pose, k = np.eye(4, dtype=np.float32), np.float32([100, 100, 80, 60])
+    bad_pose = pose.copy(); bad_pose[0, 3] = np.nan
+    cases = [
+        (dict(region=5), TypeError), (dict(region=((0, 0), (8, 8, 8))), ValueError), (dict(region=((0, 0, 0), (8, 8, 8), (1, 1, 1))), ValueError),
+        (dict(region=((0, 0, 0.5), (8, 8, 8))), TypeError), (dict(region=((0, 0, 0), (8, 8, 2**31))), ValueError),
+        (dict(region=((0, 0, True), (8, 8, 8))), TypeError),
+        (dict(views=[(pose, k)] * 65), ValueError), (dict(views=[pose]), (TypeError, ValueError)), (dict(views=[(pose[:3], k)]), ValueError),
+        (dict(views=[(pose, k[:3])]), ValueError), (dict(views=[(bad_pose, k)]), ValueError), (dict(views=[(pose, np.float32([0, 100, 80, 60]))]), ValueError),
+        (dict(views=[(pose, np.float32([100, np.inf, 80, 60]))]), ValueError), (dict(views=[(pose, k, 0, 120)]), ValueError),
+        (dict(views=[(pose, k, 160, -1)]), ValueError), (dict(views=[(pose, k, 160.0, 120)]), TypeError),
+        (dict(views=[(np.array([["a"] * 4] * 4), k)]), TypeError), (dict(views=[(pose.astype(complex), k)]), TypeError), (dict(views=[5]), TypeError),
+    ]
+    for kw, exc in cases:
+        with pytest.raises(exc):
+            p.mesh_blocks(**kw)
+    # good input gets as far as the library
+    for kw in (dict(), dict(region=((0, 0, 0), (8, 8, 8))), dict(region=((-5, 0, 0), (300, 8, 8)), views=[(pose, k), (pose, k, 64, 48)], skip_empty=True),
+               dict(region=(np.int32([0, 0, 0]), np.int64([8, 8, 8])))):
+        with pytest.raises(AssertionError, match="library call se_hip_mesh_blocks_host"):
+            p.mesh_blocks(**kw)
+    sel, keep = p._mesh_select(((-5, 0, 0), (300, 8, 8)), [(pose * 2, k, 64, 48)], True)
+    assert list(sel.lo) == [-5, 0, 0] and list(sel.hi) == [300, 8, 8] and sel.n_views == 1 and sel.flags == 1
+    assert sel.views[0].width == 64 and sel.views[0].height == 48 and list(sel.views[0].k) == k.tolist()
+    assert list(sel.views[0].pose) == (pose * 2).T.reshape(16).tolist()
+
+
+def test_the_rule_covers_the_exact_set_and_is_not_vacuous():
+    """Geometry alone: on a grid of blocks and a handful of cameras (negative fy, a camera outside the volume, one looking away) every
+    exactly-touched block is possibly touched, the loosened rule covers the rule, and the rule leaves blocks out."""
+    size, dim = 256, 4.8
+    g = np.arange(0, size, 8)
+    corners = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)[::7]
+    from tests.parity_util import look
+    views = [L.view_of(look((2.4, 2.4, 0.3)), [120, 120, 80, 60], 160, 120), L.view_of(look((2.4, 2.4, 2.4), yaw_deg=70, pitch_deg=20, roll_deg=30), [120, -120, 80, 60], 160, 120),
+             L.view_of(look((-1.0, 2.0, 2.0), yaw_deg=90), [-90, 100, 70, 65], 160, 120), L.view_of(look((2.4, 2.4, 5.5)), [120, 120, 80, 60], 160, 120)]
+    for v in views:
+        exact = L.exactly_touched(corners, [v], size, dim)
+        rule = L.possibly_touched(corners, [v], size, dim)
+        loose = L.possibly_touched(corners, [v], size, dim, radius=12.0, border=2.0)
+        assert not (exact & ~rule).any() and not (rule & ~loose).any()
+        assert rule.sum() < len(corners)
+    assert L.exactly_touched(corners, views[:3], size, dim).sum() > 100
+
+
+@pytest.mark.parametrize("field,mu,frames", [(SDF, 0.1, 60), (OFUSION, 0.02, 40)], ids=["sdf", "ofusion"])
+def test_no_changed_block_outside_the_selection_and_livemesh_follows_the_oracle(field, mu, frames):
+    """Stress stream, 160x120 -> 256^3, compared every 10 frames: the blocks whose triangles (assigned by centroid) changed since the last
+    comparison all pass the restated rule for the views in between; and a LiveMesh fed by the rule-filtered split of the oracle's full
+    mesh equals that full mesh after every update, sorted, bit for bit."""
+    W, H, N, dim, step = 160, 120, 256, 4.8, 10
+    s = StressStream(W, H, dim)
+    o = OraclePipeline(field, N, dim, W, H)
+    src, live = L.MeshSource(N, dim, W, H), LiveMesh()
+    prev, views = {}, []
+    try:
+        for f in range(frames):
+            o.integrate(s.depth(f), s.pose(f), s.k, mu, f)
+            views.append((np.asarray(s.pose(f), np.float32), np.asarray(s.k, np.float32)))
+            if (f + 1) % step:
+                continue
+            full = o.mesh()
+            corners = np.asarray(o.blocks()[0], np.int64)
+            cur = {c: t.tobytes() for c, t in L.split_by_block(full, N, dim).items()}
+            changed = [c for c in set(cur) | set(prev) if cur.get(c) != prev.get(c)]
+            assert changed
+            sel = L.possibly_touched(changed, [L.view_of(p, k, W, H) for p, k in views], N, dim)
+            missed = int((~sel).sum())
+            all_sel = L.possibly_touched(corners, [L.view_of(p, k, W, H) for p, k in views], N, dim)
+            print(f"frame {f}: blocks {len(corners)} with triangles {len(cur)} changed {len(changed)} selected {int(all_sel.sum())} missed {missed}")
+            assert missed == 0, (f, missed)
+            src.set(full, corners)
+            live.update(src, views)
+            assert L.same_triangle_set(live.triangles(), full), f
+            prev, views = cur, []
+        assert int(all_sel.sum()) < len(corners)
+    finally:
+        o.close()
+
+
+def test_livemesh_replaces_deletes_and_falls_back_beyond_64_views():
+    class Src:
+        def __init__(self):
+            self.calls = []
+
+        def mesh_blocks(self, region=None, views=None, skip_empty=False):
+            self.calls.append((region, None if views is None else len(views), skip_empty))
+            return self.res
+    t = np.arange(27, dtype=np.float32).reshape(3, 3, 3)
+    s, m = Src(), LiveMesh()
+    s.res = {"coords": np.int32([[8, 0, 0], [0, 0, 0]]), "ranges": np.int64([[0, 1], [1, 2]]), "triangles": t}
+    assert m.update(s, [("p", "k")] * 3) == 2 and s.calls[-1] == (None, 3, False)
+    assert (m.triangles() == t[[1, 2, 0]]).all()           # blocks in coordinate order
+    s.res = {"coords": np.int32([[0, 0, 0], [16, 0, 0]]), "ranges": np.int64([[0, 0], [0, 0]]), "triangles": t[:0]}
+    m.update(s, [("p", "k")] * 65)
+    assert s.calls[-1] == (None, None, False)               # more than 64 pending views: the region alone
+    assert (m.triangles() == t[:1]).all() and list(m.blocks) == [(8, 0, 0)]
+    m.update(s, [], region=((0, 0, 0), (8, 8, 8)))
+    assert s.calls[-1] == (((0, 0, 0), (8, 8, 8)), None, False)
+    import supereight_amd.livemesh as lm
+    assert "oracle" not in open(lm.__file__).read().replace("the oracle", "")
+
+
+def test_cpp_mirror_compiles(tmp_path):
+    obj = os.path.join(str(tmp_path), "mesh_blocks_mirror.o")
+    for tag in ("SDF", "OFusion"):
+        subprocess.run(["g++", "-std=c++14", "-O1", "-c", f"-DSE_FIELD_TYPE={tag}", "-I" + os.path.join(ROOT, "include"),
+                        os.path.join(ROOT, "tests", "cpp", "mesh_blocks_mirror.cpp"), "-o", obj], check=True, capture_output=True)
+        assert os.path.getsize(obj) > 0
