@@ -146,15 +146,12 @@ struct se_hip_pipeline {
   size_t shard_cap = 0;                  // bricks per segment
   bool mc_table_ready = false;   // SE_MC_TRI uploaded to constant memory
   unsigned long long* mesh_ctr = nullptr;
-  unsigned char* query_buf = nullptr;   // se_hip_query_points_host: device staging of the points and the outputs, grown on demand
-  size_t query_cap = 0;
-  unsigned char* collide_buf = nullptr; // se_hip_collide_boxes_host: device staging of the boxes and the statuses, grown on demand
-  size_t collide_cap = 0;
+  // Device staging of the _host entries of the batched queries (points, boxes, rays, per-block meshes): the caller's input and the outputs, grown on
+  // demand (reserve_staging).  One buffer serves them all because no two are ever in use at once: a handle has one caller thread at a time
+  // (include/se_hip.h) and every _host entry synchronises the stream before it returns.  A host entry that returned with work in flight would break that.
+  unsigned char* staging = nullptr;
+  size_t staging_cap = 0;
   unsigned char* meshb_dev = nullptr;   // se_hip_mesh_blocks: view planes [20][64] floats, then the reservation state (3 x uint64); allocated on first use
-  unsigned char* meshb_buf = nullptr;   // se_hip_mesh_blocks_host: device staging of the outputs, grown on demand
-  size_t meshb_cap = 0;
-  unsigned char* ray_buf = nullptr;     // se_hip_cast_rays_host: device staging of the rays and the outputs, grown on demand
-  size_t ray_cap = 0;
   bool filter_input = false;   // preprocessing(..., filterInput): tracking sees the bilateral-filtered depth
   bool occ_commit_due = false; // the next sweep kernel must publish the scan's occupancy bits
   OccLists occ_lists{nullptr, 0, 0};   // ... of these key lists (own list, or every rank's after se_hip_alloc_commit)
@@ -404,6 +401,18 @@ RayLaunchArgs make_batch_ray_args(se_hip_pipeline* p, float mu) {
   return L;
 }
 
+// Which instantiation of a ray kernel (k_raycast, k_raycast_scan, k_cast_rays) a launch with `a` takes.
+//   shallow  every non-leaf occupancy level is in LDS (volumes <= 512^3): specialised traversal loop
+//   o32      ... and dense voxel planes of <= 4 GiB (512^3: 1 GiB): the lean march addresses them by 32-bit byte offsets from the scalar base
+struct RaySel { bool ofusion, dense, shallow, o32; };
+RaySel ray_kernel_sel(const se_hip_pipeline* p, const RayArgs& a) {
+  const DevMap& m = p->map;
+  const size_t nb = (size_t)(m.size >> 3);
+  const bool shallow = !a.has_deep;
+  return {p->cfg.field_type != SE_HIP_FIELD_SDF, m.dense != 0, shallow,
+          m.dense && shallow && nb * nb * nb * (size_t)SE_BRICK_STRIDE * sizeof(float) <= ((size_t)4 << 30)};
+}
+
 // Host gate: returns once the last integration sweep has completed -- known from the sequence word the raycast kernel
 // behind it wrote when it started (no raycast behind it: the frames before the first raycast, integration-only
 // callers -> a stream synchronisation).
@@ -479,6 +488,74 @@ int check_overflow(se_hip_pipeline* p) {
   if (o) return fail(SE_HIP_E_CAPACITY, o == 2 ? "new-key list overflow: blocks were allocated locally but not reported to the peers (raise the exchange capacity)"
                                               : "block / node pool exhausted (raise max_blocks)");
   return SE_HIP_OK;
+}
+
+// the device counters on the host (synchronises the stream); a sticky overflow is reported
+int fetch_counters(se_hip_pipeline* p) {
+  if (int r = join_scan(p)) return r;
+  HIP_TRY(hipMemcpyAsync(p->ctr_host, p->map.ctr, C_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return check_overflow(p);
+}
+
+// ---- batched queries (points, boxes, rays, per-block meshes): the host path they share
+// Grows the handle's staging buffer to `need` bytes (see se_hip_pipeline::staging): work that still reads the old one is waited for first.
+int reserve_staging(se_hip_pipeline* p, size_t need) {
+  if (need <= p->staging_cap) return SE_HIP_OK;
+  if (p->staging) { HIP_TRY(hipStreamSynchronize(p->stream)); hipFree(p->staging); p->staging = nullptr; p->staging_cap = 0; }
+  HIP_TRY(hipMalloc((void**)&p->staging, need));
+  p->staging_cap = need;
+  return SE_HIP_OK;
+}
+// Layout of a staging buffer: the offsets of `k` parts of `bytes[i]` bytes packed in the order given; returns the total.  Nothing is padded: the
+// callers list 8-byte items first, then 4-byte items, then bytes, each part a whole number of its items, so every part is naturally aligned.
+size_t staging_layout(const size_t* bytes, int k, size_t* off) {
+  size_t at = 0;
+  for (int i = 0; i < k; ++i) { off[i] = at; at += bytes[i]; }
+  return at;
+}
+// What every batched query does first: the handle (and a deferred raycast, unless the entry point holds an InFrame), the family's own
+// argument check, then the side stream's allocation scan joined so that the launch reads a complete map.
+template <typename Check> int query_prologue(se_hip_pipeline* p, Check args_ok) {
+  if (int r = check(p)) return r;
+  if (int r = args_ok()) return r;
+  return join_scan(p);
+}
+// The outputs of an array-in / array-out family (points, boxes, rays): per output the caller's array (null: not asked for) and its bytes per item.
+struct BatchOut { void* ptr; size_t item_bytes; };
+struct BatchOuts { int count; BatchOut o[5]; };
+// Device form: the caller's arrays are device memory and go to `launch(in, out pointers)` as they are; nothing is waited for.
+template <typename Check, typename Launch>
+int batch_device(se_hip_pipeline* p, const void* in, int64_t n, const BatchOuts& out, Check args_ok, Launch launch) {
+  if (int r = query_prologue(p, args_ok)) return r;
+  if (int r = check_overflow(p)) return r;
+  if (n == 0) return SE_HIP_OK;
+  void* dev[5];
+  for (int k = 0; k < out.count; ++k) dev[k] = out.o[k].ptr;
+  launch(in, dev);
+  HIP_TRY(hipGetLastError());
+  return SE_HIP_OK;
+}
+// Host form: staging = [input n x in_item_bytes][the outputs asked for, in the order given]; upload, launch on the staged arrays, download.
+template <typename Check, typename Launch>
+int batch_host(se_hip_pipeline* p, const void* in, size_t in_item_bytes, int64_t n, const BatchOuts& out, Check args_ok, Launch launch) {
+  if (int r = query_prologue(p, args_ok)) return r;
+  if (n == 0) return fetch_counters(p);
+  const size_t un = (size_t)n;
+  size_t bytes[6], off[6];
+  bytes[0] = un * in_item_bytes;
+  for (int k = 0; k < out.count; ++k) bytes[k + 1] = out.o[k].ptr ? un * out.o[k].item_bytes : 0;
+  if (int r = reserve_staging(p, staging_layout(bytes, out.count + 1, off))) return r;
+  unsigned char* b = p->staging;
+  HIP_TRY(hipMemcpyAsync(b, in, bytes[0], hipMemcpyHostToDevice, p->stream));
+  void* dev[5];
+  for (int k = 0; k < out.count; ++k) dev[k] = bytes[k + 1] ? b + off[k + 1] : nullptr;
+  launch(b, dev);
+  HIP_TRY(hipGetLastError());
+  for (int k = 0; k < out.count; ++k)
+    if (bytes[k + 1]) HIP_TRY(hipMemcpyAsync(out.o[k].ptr, dev[k], bytes[k + 1], hipMemcpyDeviceToHost, p->stream));
+  // (synchronises; a sticky overflow is reported as the other read-back calls report it)
+  return fetch_counters(p);
 }
 
 // the images the raycast of `frame` writes, and every consumer (tracking, rendering, the getters) reads from then on
@@ -738,11 +815,8 @@ int se_hip_destroy(se_hip_pipeline* p) {
   if (p->sort_tmp) hipFree(p->sort_tmp);
   if (p->gate_host) hipHostFree(p->gate_host);
   if (p->mesh_ctr) hipFree(p->mesh_ctr);
-  if (p->query_buf) hipFree(p->query_buf);
-  if (p->collide_buf) hipFree(p->collide_buf);
-  if (p->ray_buf) hipFree(p->ray_buf);
+  if (p->staging) hipFree(p->staging);
   if (p->meshb_dev) hipFree(p->meshb_dev);
-  if (p->meshb_buf) hipFree(p->meshb_buf);
   for (int i = 0; i < se_hip_pipeline::kIn; ++i) { if (p->in_host[i]) hipHostFree(p->in_host[i]); if (p->in_done[i]) hipEventDestroy(p->in_done[i]); }
   if (p->own_side && p->side) hipStreamDestroy(p->side);
   if (p->ev_sweep) hipEventDestroy(p->ev_sweep);
@@ -903,18 +977,17 @@ int launch_raycast_scan(se_hip_pipeline* p, const DevMap& ms, const AllocArgs& s
   const int ray_wgs = (int)L.grid.x;
   const size_t smem = std::max(L.smem, (size_t)SE_SCAN_SLOTS * SE_WG_SCAN * sizeof(uint32_t));
   const dim3 grid((unsigned)(ray_wgs + scan_wgs)), block(SE_WG_RAY);
-  const bool sdf = p->cfg.field_type == SE_HIP_FIELD_SDF;
-  const size_t nb = (size_t)(m.size >> 3);
+  const RaySel s = ray_kernel_sel(p, a);
   // (a dense grid of > 4 GiB with every level staged -- only with SE_HIP_RAY_CACHE_LEVELS raised -- takes the generic instantiation)
-  const bool shallow = !a.has_deep && !(m.dense && nb * nb * nb * (size_t)SE_BRICK_STRIDE * sizeof(float) > ((size_t)4 << 30));
+  const bool shallow = s.dense ? s.o32 : s.shallow;
   {
     ScopedTimer t(p, SE_HIP_K_RAYCAST);
 #define SE_RS(OF, DN, SH, O3) hipLaunchKernelGGL((k_raycast_scan<OF, DN, SH, O3>), grid, block, smem, p->stream, m, a, p->vertex, p->normal, ray_wgs, ms, p->depth, sa, ds)
-    if (sdf) {
-      if (m.dense) { if (shallow) SE_RS(false, true, true, true); else SE_RS(false, true, false, false); }
+    if (!s.ofusion) {
+      if (s.dense) { if (shallow) SE_RS(false, true, true, true); else SE_RS(false, true, false, false); }
       else { if (shallow) SE_RS(false, false, true, false); else SE_RS(false, false, false, false); }
     } else {
-      if (m.dense) { if (shallow) SE_RS(true, true, true, true); else SE_RS(true, true, false, false); }
+      if (s.dense) { if (shallow) SE_RS(true, true, true, true); else SE_RS(true, true, false, false); }
       else { if (shallow) SE_RS(true, false, true, false); else SE_RS(true, false, false, false); }
     }
 #undef SE_RS
@@ -1416,15 +1489,12 @@ int se_hip_raycast(se_hip_pipeline* p, const float pose_cm[16], const float k[4]
   const RayArgs& a = L.a;
   const size_t smem = L.smem;
   const dim3 grid = L.grid, block(SE_WG_RAY);
-  const bool sdf = p->cfg.field_type == SE_HIP_FIELD_SDF;
   {
     ScopedTimer t(p, SE_HIP_K_RAYCAST);
 #define SE_RAY(OF, ST, DN, SH) hipLaunchKernelGGL((k_raycast<OF, ST, DN, SH>), grid, block, smem, p->stream, m, a, p->vertex, p->normal)
-    const bool shallow = !a.has_deep;   // every non-leaf occupancy level is in LDS (volumes <= 512^3): specialised traversal loop
-    // dense voxel planes of <= 4 GiB (512^3: 1 GiB): the lean march addresses them by 32-bit byte offsets from the scalar base
-    const size_t nb = (size_t)(m.size >> 3);
-    const bool o32 = m.dense && shallow && nb * nb * nb * (size_t)SE_BRICK_STRIDE * sizeof(float) <= ((size_t)4 << 30);
-    const int variant = (sdf ? 0 : 4) | (p->stats ? 2 : 0) | (m.dense ? 1 : 0);
+    const RaySel s = ray_kernel_sel(p, a);
+    const bool shallow = s.shallow, o32 = s.o32;
+    const int variant = (s.ofusion ? 4 : 0) | (p->stats ? 2 : 0) | (s.dense ? 1 : 0);
     switch (variant) {
       case 0: if (shallow) SE_RAY(false, false, false, true); else SE_RAY(false, false, false, false); break;
       case 1: if (o32) hipLaunchKernelGGL((k_raycast<false, false, true, true, true>), grid, block, smem, p->stream, m, a, p->vertex, p->normal);
@@ -1758,24 +1828,21 @@ int se_hip_render_track(se_hip_pipeline* p, uint8_t* host_rgbw) {
   return render_download(p, host_rgbw);
 }
 
-// ----------------------------------------------------------------------------------- read-back
-static int fetch_counters(se_hip_pipeline* p) {
-  if (int r = join_scan(p)) return r;
-  HIP_TRY(hipMemcpyAsync(p->ctr_host, p->map.ctr, C_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return check_overflow(p);
-}
-
 // ---------------------------------------------------------------------------------- mesh export
 namespace {
-int run_mesh(se_hip_pipeline* p, float* dev_out, unsigned long long capacity, unsigned long long* n) {
-  if (int r = join_scan(p)) return r;
+// the marching-cubes table in constant memory, uploaded once per handle (k_mesh, k_mesh_blocks)
+int ensure_mc_table(se_hip_pipeline* p) {
   if (!p->mc_table_ready) {
     signed char table[256][SE_MC_WIDTH];
     se_mc_expand(table);
     HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(SE_MC_TRI), table, sizeof(table)));
     p->mc_table_ready = true;
   }
+  return SE_HIP_OK;
+}
+int run_mesh(se_hip_pipeline* p, float* dev_out, unsigned long long capacity, unsigned long long* n) {
+  if (int r = join_scan(p)) return r;
+  if (int r = ensure_mc_table(p)) return r;
   if (!p->mesh_ctr) HIP_TRY(hipMalloc((void**)&p->mesh_ctr, 2 * sizeof(unsigned long long)));
   HIP_TRY(hipMemsetAsync(p->mesh_ctr, 0, 2 * sizeof(unsigned long long), p->stream));
   MeshArgs a{dev_out, p->mesh_ctr, capacity};
@@ -1979,15 +2046,6 @@ void view_planes(const se_hip_mesh_view& w, double voxel, float out[SE_MB_VIEW_F
     out[4 * j + 3] = (float)(d / voxel);
   }
 }
-int ensure_mc_table(se_hip_pipeline* p) {
-  if (!p->mc_table_ready) {
-    signed char table[256][SE_MC_WIDTH];
-    se_mc_expand(table);
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(SE_MC_TRI), table, sizeof(table)));
-    p->mc_table_ready = true;
-  }
-  return SE_HIP_OK;
-}
 // Enqueues begin (state reset + the views' planes, 16 views per launch, passed by value), the meshing kernel and end (header) on the stream.
 int launch_mesh_blocks(se_hip_pipeline* p, const se_hip_mesh_select* sel, const se_hip_mesh_out& o) {
   const DevMap& m = p->map;
@@ -2032,9 +2090,7 @@ int launch_mesh_blocks(se_hip_pipeline* p, const se_hip_mesh_select* sel, const 
 int se_hip_mesh_blocks(se_hip_pipeline* p, const se_hip_mesh_select* select, const se_hip_mesh_out* device_out) {
   if (!p) return fail(SE_HIP_E_INVALID, "null handle");
   InFrame guard(p);
-  if (int r = check(p)) return r;
-  if (int r = mesh_blocks_args(select, device_out)) return r;
-  if (int r = join_scan(p)) return r;
+  if (int r = query_prologue(p, [&] { return mesh_blocks_args(select, device_out); })) return r;
   if (int r = check_overflow(p)) return r;
   return launch_mesh_blocks(p, select, *device_out);
 }
@@ -2042,30 +2098,25 @@ int se_hip_mesh_blocks(se_hip_pipeline* p, const se_hip_mesh_select* select, con
 int se_hip_mesh_blocks_host(se_hip_pipeline* p, const se_hip_mesh_select* select, const se_hip_mesh_out* host_out) {
   if (!p) return fail(SE_HIP_E_INVALID, "null handle");
   InFrame guard(p);
-  if (int r = check(p)) return r;
-  if (int r = mesh_blocks_args(select, host_out)) return r;
-  if (int r = join_scan(p)) return r;
+  if (int r = query_prologue(p, [&] { return mesh_blocks_args(select, host_out); })) return r;
   // staging: [header 4 x int64][range capB x 2 int64][triangles capT x 9 floats][coords capB x 3 int32]
   const size_t ct = (size_t)host_out->capacity_triangles, cb = (size_t)host_out->capacity_blocks;
-  const size_t off_range = 4 * sizeof(int64_t), off_tri = off_range + cb * 2 * sizeof(int64_t), off_coords = off_tri + ct * 9 * sizeof(float);
-  const size_t need = off_coords + cb * 3 * sizeof(int32_t);
-  if (need > p->meshb_cap) {
-    if (p->meshb_buf) { HIP_TRY(hipStreamSynchronize(p->stream)); hipFree(p->meshb_buf); p->meshb_buf = nullptr; p->meshb_cap = 0; }
-    HIP_TRY(hipMalloc((void**)&p->meshb_buf, need));
-    p->meshb_cap = need;
-  }
-  unsigned char* b = p->meshb_buf;
-  se_hip_mesh_out dev{ct ? (float*)(b + off_tri) : nullptr, host_out->capacity_triangles, cb ? (int32_t*)(b + off_coords) : nullptr,
-                      cb ? (int64_t*)(b + off_range) : nullptr, host_out->capacity_blocks, (int64_t*)b};
+  const size_t bytes[4] = {4 * sizeof(int64_t), cb * 2 * sizeof(int64_t), ct * 9 * sizeof(float), cb * 3 * sizeof(int32_t)};
+  size_t off[4];
+  if (int r = reserve_staging(p, staging_layout(bytes, 4, off))) return r;
+  unsigned char* b = p->staging;
+  unsigned char *range = b + off[1], *tri = b + off[2], *coords = b + off[3];
+  se_hip_mesh_out dev{ct ? (float*)tri : nullptr, host_out->capacity_triangles, cb ? (int32_t*)coords : nullptr,
+                      cb ? (int64_t*)range : nullptr, host_out->capacity_blocks, (int64_t*)b};
   if (int r = launch_mesh_blocks(p, select, dev)) return r;
   int64_t* h = host_out->header;
-  HIP_TRY(hipMemcpyAsync(h, b, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipMemcpyAsync(h, b, bytes[0], hipMemcpyDeviceToHost, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
   if (h[2] > 0) {
-    HIP_TRY(hipMemcpyAsync(host_out->block_range, b + off_range, (size_t)h[2] * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipMemcpyAsync(host_out->block_coords, b + off_coords, (size_t)h[2] * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyAsync(host_out->block_range, range, (size_t)h[2] * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyAsync(host_out->block_coords, coords, (size_t)h[2] * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
   }
-  if (h[3] > 0) HIP_TRY(hipMemcpyAsync(host_out->triangles, b + off_tri, (size_t)h[3] * 9 * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+  if (h[3] > 0) HIP_TRY(hipMemcpyAsync(host_out->triangles, tri, (size_t)h[3] * 9 * sizeof(float), hipMemcpyDeviceToHost, p->stream));
   // (synchronises; a sticky overflow is reported as the other read-back calls report it)
   if (int r = fetch_counters(p)) return r;
   if ((h[0] > h[2] || h[1] > h[3]) && (ct || cb)) return fail(SE_HIP_E_CAPACITY, "se_hip_mesh_blocks_host: output too small (the header gives the sizes needed)");
@@ -2081,8 +2132,15 @@ int query_args(const float* points, int64_t n, const se_hip_query_out* out) {
   if (!out || !(out->fine || out->coarse || out->interp || out->grad || out->status)) return fail(SE_HIP_E_INVALID, "se_hip_query_points: no output requested");
   return SE_HIP_OK;
 }
-void launch_query(se_hip_pipeline* p, const float* points, int64_t n, const QueryOut& o) {
+// the outputs in the order of se_hip_query_out (a null `out` is refused by query_args before the list is looked at; static: called from the
+// drivers' template arguments, a function of this C-linkage block would otherwise be emitted as an exported symbol)
+static BatchOuts query_outs(const se_hip_query_out* out) {
+  if (!out) return {5, {}};
+  return {5, {{out->fine, 2 * sizeof(float)}, {out->coarse, 2 * sizeof(float)}, {out->interp, sizeof(float)}, {out->grad, 3 * sizeof(float)}, {out->status, 1}}};
+}
+void launch_query(se_hip_pipeline* p, const float* points, int64_t n, void* const* out) {
   const DevMap& m = p->map;
+  const QueryOut o{(float*)out[0], (float*)out[1], (float*)out[2], (float*)out[3], (uint8_t*)out[4]};
   const float s = (float)m.size / m.dim;                // VolumeTemplate: inverseVoxelSize = _size / _dim
   const float grad_scale = 0.5f * m.dim / (float)m.size;  // octree.hpp:736
   const int grid = grid_for((size_t)n, SE_WG_QUERY, 16384);
@@ -2092,44 +2150,13 @@ void launch_query(se_hip_pipeline* p, const float* points, int64_t n, const Quer
 }  // namespace
 
 int se_hip_query_points(se_hip_pipeline* p, const float* device_points_m, int64_t n, const se_hip_query_out* device_out) {
-  if (int r = check(p)) return r;
-  if (int r = query_args(device_points_m, n, device_out)) return r;
-  if (int r = join_scan(p)) return r;
-  if (int r = check_overflow(p)) return r;
-  if (n == 0) return SE_HIP_OK;
-  const QueryOut o{device_out->fine, device_out->coarse, device_out->interp, device_out->grad, device_out->status};
-  launch_query(p, device_points_m, n, o);
-  HIP_TRY(hipGetLastError());
-  return SE_HIP_OK;
+  return batch_device(p, device_points_m, n, query_outs(device_out), [&] { return query_args(device_points_m, n, device_out); },
+                      [&](const void* pts, void* const* o) { launch_query(p, (const float*)pts, n, o); });
 }
 
 int se_hip_query_points_host(se_hip_pipeline* p, const float* host_points_m, int64_t n, const se_hip_query_out* host_out) {
-  if (int r = check(p)) return r;
-  if (int r = query_args(host_points_m, n, host_out)) return r;
-  if (int r = join_scan(p)) return r;
-  if (n == 0) return fetch_counters(p);
-  // staging: [points n x 3][fine n x 2][coarse n x 2][interp n][grad n x 3][status n], only the parts asked for (floats first: 4-byte aligned)
-  const size_t un = (size_t)n;
-  const size_t sz[5] = {host_out->fine ? 2 * un * 4 : 0, host_out->coarse ? 2 * un * 4 : 0, host_out->interp ? un * 4 : 0,
-                        host_out->grad ? 3 * un * 4 : 0, host_out->status ? un : 0};
-  size_t off[5], need = 3 * un * 4;
-  for (int k = 0; k < 5; ++k) { off[k] = need; need += sz[k]; }
-  if (need > p->query_cap) {
-    if (p->query_buf) { HIP_TRY(hipStreamSynchronize(p->stream)); hipFree(p->query_buf); p->query_buf = nullptr; p->query_cap = 0; }
-    HIP_TRY(hipMalloc((void**)&p->query_buf, need));
-    p->query_cap = need;
-  }
-  unsigned char* b = p->query_buf;
-  HIP_TRY(hipMemcpyAsync(b, host_points_m, 3 * un * 4, hipMemcpyHostToDevice, p->stream));
-  auto dev = [&](int k) { return sz[k] ? b + off[k] : nullptr; };
-  const QueryOut o{(float*)dev(0), (float*)dev(1), (float*)dev(2), (float*)dev(3), (uint8_t*)dev(4)};
-  launch_query(p, (const float*)b, n, o);
-  HIP_TRY(hipGetLastError());
-  void* dst[5] = {host_out->fine, host_out->coarse, host_out->interp, host_out->grad, host_out->status};
-  for (int k = 0; k < 5; ++k)
-    if (sz[k]) HIP_TRY(hipMemcpyAsync(dst[k], b + off[k], sz[k], hipMemcpyDeviceToHost, p->stream));
-  // (synchronises; a sticky overflow is reported as the other read-back calls report it)
-  return fetch_counters(p);
+  return batch_host(p, host_points_m, 3 * sizeof(float), n, query_outs(host_out), [&] { return query_args(host_points_m, n, host_out); },
+                    [&](const void* pts, void* const* o) { launch_query(p, (const float*)pts, n, o); });
 }
 
 
@@ -2155,36 +2182,16 @@ void launch_collide(se_hip_pipeline* p, const int32_t* boxes, int64_t n, const s
 
 int se_hip_collide_boxes(se_hip_pipeline* p, const int32_t* device_boxes, int64_t n, const se_hip_collide_test* test, int32_t mode,
                          uint8_t* device_status) {
-  if (int r = check(p)) return r;
-  if (int r = collide_args(device_boxes, n, test, mode, device_status)) return r;
-  if (int r = join_scan(p)) return r;
-  if (int r = check_overflow(p)) return r;
-  if (n == 0) return SE_HIP_OK;
-  launch_collide(p, device_boxes, n, test, mode, device_status);
-  HIP_TRY(hipGetLastError());
-  return SE_HIP_OK;
+  const BatchOuts out{1, {{device_status, 1}}};
+  return batch_device(p, device_boxes, n, out, [&] { return collide_args(device_boxes, n, test, mode, device_status); },
+                      [&](const void* boxes, void* const* o) { launch_collide(p, (const int32_t*)boxes, n, test, mode, (uint8_t*)o[0]); });
 }
 
 int se_hip_collide_boxes_host(se_hip_pipeline* p, const int32_t* host_boxes, int64_t n, const se_hip_collide_test* test, int32_t mode,
                               uint8_t* host_status) {
-  if (int r = check(p)) return r;
-  if (int r = collide_args(host_boxes, n, test, mode, host_status)) return r;
-  if (int r = join_scan(p)) return r;
-  if (n == 0) return fetch_counters(p);
-  // staging: [boxes n x 6 int32][status n]
-  const size_t un = (size_t)n, need = un * 6 * sizeof(int32_t) + un;
-  if (need > p->collide_cap) {
-    if (p->collide_buf) { HIP_TRY(hipStreamSynchronize(p->stream)); hipFree(p->collide_buf); p->collide_buf = nullptr; p->collide_cap = 0; }
-    HIP_TRY(hipMalloc((void**)&p->collide_buf, need));
-    p->collide_cap = need;
-  }
-  unsigned char* b = p->collide_buf;
-  HIP_TRY(hipMemcpyAsync(b, host_boxes, un * 6 * sizeof(int32_t), hipMemcpyHostToDevice, p->stream));
-  launch_collide(p, (const int32_t*)b, n, test, mode, b + un * 6 * sizeof(int32_t));
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(host_status, b + un * 6 * sizeof(int32_t), un, hipMemcpyDeviceToHost, p->stream));
-  // (synchronises; a sticky overflow is reported as the other read-back calls report it)
-  return fetch_counters(p);
+  const BatchOuts out{1, {{host_status, 1}}};
+  return batch_host(p, host_boxes, 6 * sizeof(int32_t), n, out, [&] { return collide_args(host_boxes, n, test, mode, host_status); },
+                    [&](const void* boxes, void* const* o) { launch_collide(p, (const int32_t*)boxes, n, test, mode, (uint8_t*)o[0]); });
 }
 
 
@@ -2199,15 +2206,19 @@ int ray_args(const float* rays, int64_t n, float mu, const se_hip_ray_out* out) 
   if (!(std::isfinite(mu) && mu > 0.f)) return fail(SE_HIP_E_INVALID, "se_hip_cast_rays: mu must be finite and > 0");
   return SE_HIP_OK;
 }
+// the outputs in the order of se_hip_ray_out (a null `out` is refused by ray_args before the list is looked at; static: as query_outs)
+static BatchOuts ray_outs(const se_hip_ray_out* out) {
+  if (!out) return {3, {}};
+  return {3, {{out->hit, 4 * sizeof(float)}, {out->normal, 3 * sizeof(float)}, {out->status, 1}}};
+}
 // Launches of at most SE_RAY_MAX_LAUNCH rays (each a grid of whole workgroups: every thread reaches the staging barrier)
-void launch_rays(se_hip_pipeline* p, const float* rays, int64_t n, float mu, const CastRayOut& o) {
+void launch_rays(se_hip_pipeline* p, const float* rays, int64_t n, float mu, void* const* out) {
   const DevMap& m = p->map;
+  const CastRayOut o{(float*)out[0], (float*)out[1], (uint8_t*)out[2]};
   const RayLaunchArgs L = make_batch_ray_args(p, mu);
   const float s = (float)m.size / m.dim;   // VolumeTemplate: inverseVoxelSize = _size / _dim (the point queries' limit)
-  const bool of = p->cfg.field_type != SE_HIP_FIELD_SDF;
-  const bool shallow = !L.a.has_deep;
-  const size_t nb = (size_t)(m.size >> 3);
-  const bool o32 = m.dense && shallow && nb * nb * nb * (size_t)SE_BRICK_STRIDE * sizeof(float) <= ((size_t)4 << 30);   // (as se_hip_raycast)
+  const RaySel sel = ray_kernel_sel(p, L.a);   // (as se_hip_raycast)
+  const bool of = sel.ofusion, shallow = sel.shallow, o32 = sel.o32;
   for (int64_t b = 0; b < n; b += SE_RAY_MAX_LAUNCH) {
     const long long k = (long long)std::min<int64_t>(n - b, SE_RAY_MAX_LAUNCH);
     const CastRayOut ob{o.hit ? o.hit + 4 * b : nullptr, o.normal ? o.normal + 3 * b : nullptr, o.status ? o.status + b : nullptr};
@@ -2232,43 +2243,15 @@ void launch_rays(se_hip_pipeline* p, const float* rays, int64_t n, float mu, con
 int se_hip_cast_rays(se_hip_pipeline* p, const float* device_rays, int64_t n, float mu, const se_hip_ray_out* device_out) {
   if (!p) return fail(SE_HIP_E_INVALID, "null handle");
   InFrame guard(p);
-  if (int r = check(p)) return r;
-  if (int r = ray_args(device_rays, n, mu, device_out)) return r;
-  if (int r = join_scan(p)) return r;
-  if (int r = check_overflow(p)) return r;
-  if (n == 0) return SE_HIP_OK;
-  launch_rays(p, device_rays, n, mu, CastRayOut{device_out->hit, device_out->normal, device_out->status});
-  HIP_TRY(hipGetLastError());
-  return SE_HIP_OK;
+  return batch_device(p, device_rays, n, ray_outs(device_out), [&] { return ray_args(device_rays, n, mu, device_out); },
+                      [&](const void* rays, void* const* o) { launch_rays(p, (const float*)rays, n, mu, o); });
 }
 
 int se_hip_cast_rays_host(se_hip_pipeline* p, const float* host_rays, int64_t n, float mu, const se_hip_ray_out* host_out) {
   if (!p) return fail(SE_HIP_E_INVALID, "null handle");
   InFrame guard(p);
-  if (int r = check(p)) return r;
-  if (int r = ray_args(host_rays, n, mu, host_out)) return r;
-  if (int r = join_scan(p)) return r;
-  if (n == 0) return fetch_counters(p);
-  // staging: [rays n x 8][hit n x 4][normal n x 3][status n], only the outputs asked for (floats first: 4-byte aligned)
-  const size_t un = (size_t)n;
-  const size_t sz[3] = {host_out->hit ? 4 * un * 4 : 0, host_out->normal ? 3 * un * 4 : 0, host_out->status ? un : 0};
-  size_t off[3], need = 8 * un * 4;
-  for (int k = 0; k < 3; ++k) { off[k] = need; need += sz[k]; }
-  if (need > p->ray_cap) {
-    if (p->ray_buf) { HIP_TRY(hipStreamSynchronize(p->stream)); hipFree(p->ray_buf); p->ray_buf = nullptr; p->ray_cap = 0; }
-    HIP_TRY(hipMalloc((void**)&p->ray_buf, need));
-    p->ray_cap = need;
-  }
-  unsigned char* b = p->ray_buf;
-  HIP_TRY(hipMemcpyAsync(b, host_rays, 8 * un * 4, hipMemcpyHostToDevice, p->stream));
-  auto dev = [&](int k) { return sz[k] ? b + off[k] : nullptr; };
-  launch_rays(p, (const float*)b, n, mu, CastRayOut{(float*)dev(0), (float*)dev(1), (uint8_t*)dev(2)});
-  HIP_TRY(hipGetLastError());
-  void* dst[3] = {host_out->hit, host_out->normal, host_out->status};
-  for (int k = 0; k < 3; ++k)
-    if (sz[k]) HIP_TRY(hipMemcpyAsync(dst[k], b + off[k], sz[k], hipMemcpyDeviceToHost, p->stream));
-  // (synchronises; a sticky overflow is reported as the other read-back calls report it)
-  return fetch_counters(p);
+  return batch_host(p, host_rays, 8 * sizeof(float), n, ray_outs(host_out), [&] { return ray_args(host_rays, n, mu, host_out); },
+                    [&](const void* rays, void* const* o) { launch_rays(p, (const float*)rays, n, mu, o); });
 }
 
 

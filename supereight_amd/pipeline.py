@@ -586,6 +586,45 @@ class DenseSLAMPipeline:
         self._check(self.lib.se_hip_download_nodes(self._h, code.ctypes.data, side.ctypes.data, x.ctypes.data, y.ctypes.data))
         return code, side, x, y
 
+    # ------------------------------------------------------------------ batched queries: what query, collides and cast_rays share
+    def _batch_input(self, who, name, a, dtype, cols, contiguous=True):
+        """The rule for an [N, cols] input of the batched queries: a numpy array of `dtype` (host entry) or a torch tensor of that dtype on
+        this handle's GPU (device entry).  Returns (torch or None, the array or tensor, N); anything else raises before any library call.
+        contiguous: a numpy array is made contiguous, a torch tensor has to be (False: the caller packs the rows itself)."""
+        dt = np.dtype(dtype)
+        is_numpy = type(a) is np.ndarray
+        torch = None if is_numpy else _torch_module(a)
+        if not is_numpy and torch is None:
+            raise TypeError(f"{who}: {name} must be a numpy {dt.name} array or a torch tensor on the GPU, got {type(a).__name__}")
+        if a.dtype != (dt if torch is None else getattr(torch, dt.name)):
+            raise TypeError(f"{who}: {name} must be {dt.name}, got {a.dtype}")
+        if a.ndim != 2 or a.shape[1] != cols:
+            raise ValueError(f"{who}: {name} must have shape [N, {cols}], got {list(a.shape)}")
+        if torch is None:
+            return None, np.ascontiguousarray(a) if contiguous else a, a.shape[0]
+        if contiguous and not a.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous")
+        if a.device.type != "cuda" or (self._device is not None and a.device.index != self._device):
+            raise ValueError(f"{who}: {name} must be on this handle's GPU (cuda:{self._device}), got {a.device}")
+        return torch, a, int(a.shape[0])
+
+    @staticmethod
+    def _batch_outputs(torch, like, n, table, want, struct):
+        """The outputs asked for (`want`) of a (name, shape per item, numpy dtype) table as numpy arrays, or as torch tensors on the device
+        of `like`, and the ctypes `struct` of their addresses (NULL where not asked for)."""
+        if torch is None:
+            res = {k: np.empty((n,) + shp, dt) for k, shp, dt in table if want[k]}
+            return res, struct(*(res[k].ctypes.data if k in res else None for k, _, _ in table))
+        res = {k: torch.empty((n,) + shp, dtype=getattr(torch, np.dtype(dt).name), device=like.device) for k, shp, dt in table if want[k]}
+        return res, struct(*(res[k].data_ptr() if k in res else None for k, _, _ in table))
+
+    def _device_call(self, torch, device, fn, *args):
+        """A device entry on torch tensors: the caller's current torch stream is synchronised first (the inputs must be complete when the
+        handle's stream reads them), and the handle before the outputs are handed back."""
+        torch.cuda.current_stream(device).synchronize()
+        self._check(fn(self._h, *args))
+        self.sync()
+
     # (shape of each output per point, dtype)
     _QUERY_OUTPUTS = (("fine", (2,), np.float32), ("coarse", (2,), np.float32), ("interp", (), np.float32), ("grad", (3,), np.float32),
                       ("status", (), np.uint8))
@@ -603,35 +642,12 @@ class DenseSLAMPipeline:
         want = {"fine": fine, "coarse": coarse, "interp": interp, "grad": grad, "status": status}
         if not any(want.values()):
             raise ValueError("query: no output requested")
-        if type(points) is np.ndarray:
-            if points.dtype != np.float32:
-                raise TypeError(f"query: points must be float32, got {points.dtype}")
-            if points.ndim != 2 or points.shape[1] != 3:
-                raise ValueError(f"query: points must have shape [N, 3], got {list(points.shape)}")
-            pts = np.ascontiguousarray(points)
-            n = pts.shape[0]
-            res = {k: np.empty((n,) + shp, dt) for k, shp, dt in self._QUERY_OUTPUTS if want[k]}
-            out = _QueryOut(*(res[k].ctypes.data if k in res else None for k, _, _ in self._QUERY_OUTPUTS))
-            self._check(self.lib.se_hip_query_points_host(self._h, pts.ctypes.data if n else None, n, C.byref(out)))
-            return res
-        torch = _torch_module(points)
+        torch, pts, n = self._batch_input("query", "points", points, np.float32, 3)
+        res, out = self._batch_outputs(torch, pts, n, self._QUERY_OUTPUTS, want, _QueryOut)
         if torch is None:
-            raise TypeError(f"query: points must be a numpy float32 array or a torch tensor on the GPU, got {type(points).__name__}")
-        if points.dtype != torch.float32:
-            raise TypeError(f"query: points must be float32, got {points.dtype}")
-        if points.dim() != 2 or points.shape[1] != 3:
-            raise ValueError(f"query: points must have shape [N, 3], got {list(points.shape)}")
-        if not points.is_contiguous():
-            raise ValueError("query: points must be contiguous")
-        if points.device.type != "cuda" or (self._device is not None and points.device.index != self._device):
-            raise ValueError(f"query: points must be on this handle's GPU (cuda:{self._device}), got {points.device}")
-        n = int(points.shape[0])
-        dt = {np.float32: torch.float32, np.uint8: torch.uint8}
-        res = {k: torch.empty((n,) + shp, dtype=dt[npdt], device=points.device) for k, shp, npdt in self._QUERY_OUTPUTS if want[k]}
-        out = _QueryOut(*(res[k].data_ptr() if k in res else None for k, _, _ in self._QUERY_OUTPUTS))
-        torch.cuda.current_stream(points.device).synchronize()
-        self._check(self.lib.se_hip_query_points(self._h, points.data_ptr() if n else None, n, C.byref(out)))
-        self.sync()
+            self._check(self.lib.se_hip_query_points_host(self._h, pts.ctypes.data if n else None, n, C.byref(out)))
+        else:
+            self._device_call(torch, pts.device, self.lib.se_hip_query_points, pts.data_ptr() if n else None, n, C.byref(out))
         return res
 
     def collides(self, boxes, threshold: float = 0.0, occupied_above=None, mode: str = "strict"):
@@ -655,33 +671,14 @@ class DenseSLAMPipeline:
             raise ValueError(f"collides: threshold must be finite as a float32, got {threshold!r}")
         test = _CollideTest(thr, int(bool(occupied_above)))
         m = _COLLIDE_MODES[mode]
-        if type(boxes) is np.ndarray:
-            if boxes.dtype != np.int32:
-                raise TypeError(f"collides: boxes must be int32, got {boxes.dtype}")
-            if boxes.ndim != 2 or boxes.shape[1] != 6:
-                raise ValueError(f"collides: boxes must have shape [N, 6], got {list(boxes.shape)}")
-            b = np.ascontiguousarray(boxes)
-            n = b.shape[0]
-            out = np.empty(n, np.uint8)
+        torch, b, n = self._batch_input("collides", "boxes", boxes, np.int32, 6)
+        out = np.empty(n, np.uint8) if torch is None else torch.empty(n, dtype=torch.uint8, device=b.device)
+        if torch is None:
             self._check(self.lib.se_hip_collide_boxes_host(self._h, b.ctypes.data if n else None, n, C.byref(test), m,
                                                            out.ctypes.data if n else None))
-            return out
-        torch = _torch_module(boxes)
-        if torch is None:
-            raise TypeError(f"collides: boxes must be a numpy int32 array or a torch tensor on the GPU, got {type(boxes).__name__}")
-        if boxes.dtype != torch.int32:
-            raise TypeError(f"collides: boxes must be int32, got {boxes.dtype}")
-        if boxes.dim() != 2 or boxes.shape[1] != 6:
-            raise ValueError(f"collides: boxes must have shape [N, 6], got {list(boxes.shape)}")
-        if not boxes.is_contiguous():
-            raise ValueError("collides: boxes must be contiguous")
-        if boxes.device.type != "cuda" or (self._device is not None and boxes.device.index != self._device):
-            raise ValueError(f"collides: boxes must be on this handle's GPU (cuda:{self._device}), got {boxes.device}")
-        n = int(boxes.shape[0])
-        out = torch.empty(n, dtype=torch.uint8, device=boxes.device)
-        torch.cuda.current_stream(boxes.device).synchronize()
-        self._check(self.lib.se_hip_collide_boxes(self._h, boxes.data_ptr() if n else None, n, C.byref(test), m, out.data_ptr() if n else None))
-        self.sync()
+        else:
+            self._device_call(torch, b.device, self.lib.se_hip_collide_boxes, b.data_ptr() if n else None, n, C.byref(test), m,
+                              out.data_ptr() if n else None)
         return out
 
     _RAY_OUTPUTS = (("hit", (4,), np.float32), ("normal", (3,), np.float32), ("status", (), np.uint8))
@@ -705,65 +702,35 @@ class DenseSLAMPipeline:
         mu = float(mu)
         if not (np.isfinite(np.float32(mu)) and mu > 0):
             raise ValueError(f"cast_rays: mu must be finite and > 0, got {mu!r}")
-        if type(origins) is np.ndarray and type(directions) is np.ndarray:
-            for name, a in (("origins", origins), ("directions", directions)):
-                if a.dtype != np.float32:
-                    raise TypeError(f"cast_rays: {name} must be float32, got {a.dtype}")
-                if a.ndim != 2 or a.shape[1] != 3:
-                    raise ValueError(f"cast_rays: {name} must have shape [N, 3], got {list(a.shape)}")
-            n = origins.shape[0]
-            if directions.shape[0] != n:
-                raise ValueError(f"cast_rays: {n} origins but {directions.shape[0]} directions")
-            d = directions
-            if normalize:
-                z = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
-                d = np.where((z > 0)[:, None], d / np.sqrt(z)[:, None], d).astype(np.float32)
-            rays = np.empty((n, 8), np.float32)
-            rays[:, 0:3] = origins
-            rays[:, 3:6] = d
-            for j, (name, v) in ((6, ("near", near)), (7, ("far", far))):
-                v = np.asarray(v)
-                if v.ndim == 0 or v.shape == (n,):
-                    rays[:, j] = v.astype(np.float32)
-                else:
-                    raise ValueError(f"cast_rays: {name} must be a scalar or have shape [{n}], got {list(v.shape)}")
-            res = {k: np.empty((n,) + shp, dt) for k, shp, dt in self._RAY_OUTPUTS if want[k]}
-            out = _RayOut(*(res[k].ctypes.data if k in res else None for k, _, _ in self._RAY_OUTPUTS))
-            self._check(self.lib.se_hip_cast_rays_host(self._h, rays.ctypes.data if n else None, n, mu, C.byref(out)))
-            return res
-        torch = _torch_module(origins)
-        if torch is None or _torch_module(directions) is None:
+        both_numpy = type(origins) is np.ndarray and type(directions) is np.ndarray
+        if not both_numpy and (_torch_module(origins) is None or _torch_module(directions) is None):
             raise TypeError("cast_rays: origins and directions must both be numpy float32 arrays or both torch tensors on the GPU, got "
                             f"{type(origins).__name__} and {type(directions).__name__}")
-        for name, a in (("origins", origins), ("directions", directions)):
-            if a.dtype != torch.float32:
-                raise TypeError(f"cast_rays: {name} must be float32, got {a.dtype}")
-            if a.dim() != 2 or a.shape[1] != 3:
-                raise ValueError(f"cast_rays: {name} must have shape [N, 3], got {list(a.shape)}")
-            if a.device.type != "cuda" or (self._device is not None and a.device.index != self._device):
-                raise ValueError(f"cast_rays: {name} must be on this handle's GPU (cuda:{self._device}), got {a.device}")
-        n = int(origins.shape[0])
-        if int(directions.shape[0]) != n:
-            raise ValueError(f"cast_rays: {n} origins but {int(directions.shape[0])} directions")
-        dev = origins.device
-        d = directions
+        torch, origins, n = self._batch_input("cast_rays", "origins", origins, np.float32, 3, contiguous=False)
+        _, d, nd = self._batch_input("cast_rays", "directions", directions, np.float32, 3, contiguous=False)
+        if nd != n:
+            raise ValueError(f"cast_rays: {n} origins but {nd} directions")
+        # the [N, 8] rays, packed by the library the inputs came from (numpy on the host, torch on the device)
+        xp = np if torch is None else torch
         if normalize:
             z = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
-            d = torch.where((z > 0)[:, None], d / torch.sqrt(z)[:, None], d)
-        rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
+            d = xp.where((z > 0)[:, None], d / xp.sqrt(z)[:, None], d)
+        rays = np.empty((n, 8), np.float32) if torch is None else torch.empty((n, 8), dtype=torch.float32, device=origins.device)
         rays[:, 0:3] = origins
         rays[:, 3:6] = d
         for j, name, v in ((6, "near", near), (7, "far", far)):
-            v = v if _torch_module(v) is not None else torch.as_tensor(np.asarray(v, np.float32))
-            if v.dim() != 0 and tuple(v.shape) != (n,):
+            if torch is None:
+                v = np.asarray(v)
+            elif _torch_module(v) is None:
+                v = torch.as_tensor(np.asarray(v, np.float32))
+            if v.ndim != 0 and tuple(v.shape) != (n,):
                 raise ValueError(f"cast_rays: {name} must be a scalar or have shape [{n}], got {list(v.shape)}")
-            rays[:, j] = v.to(device=dev, dtype=torch.float32)
-        dt = {np.float32: torch.float32, np.uint8: torch.uint8}
-        res = {k: torch.empty((n,) + shp, dtype=dt[npdt], device=dev) for k, shp, npdt in self._RAY_OUTPUTS if want[k]}
-        out = _RayOut(*(res[k].data_ptr() if k in res else None for k, _, _ in self._RAY_OUTPUTS))
-        torch.cuda.current_stream(dev).synchronize()
-        self._check(self.lib.se_hip_cast_rays(self._h, rays.data_ptr() if n else None, n, mu, C.byref(out)))
-        self.sync()
+            rays[:, j] = v.astype(np.float32) if torch is None else v.to(device=origins.device, dtype=torch.float32)
+        res, out = self._batch_outputs(torch, rays, n, self._RAY_OUTPUTS, want, _RayOut)
+        if torch is None:
+            self._check(self.lib.se_hip_cast_rays_host(self._h, rays.ctypes.data if n else None, n, mu, C.byref(out)))
+        else:
+            self._device_call(torch, rays.device, self.lib.se_hip_cast_rays, rays.data_ptr() if n else None, n, mu, C.byref(out))
         return res
 
     def _mesh_select(self, region, views, skip_empty):
@@ -826,31 +793,27 @@ class DenseSLAMPipeline:
         listed with count 0 unless skip_empty.  numpy arrays through the host entry (a sizing call, then the real one); device=True: torch
         tensors on this handle's GPU through the device entry.  Bad input raises TypeError / ValueError before any library call."""
         sel, keep = self._mesh_select(region, views, bool(skip_empty))
-        head = np.zeros(4, np.int64)
         if not device:
-            self._check(self.lib.se_hip_mesh_blocks_host(self._h, C.byref(sel), C.byref(_MeshOut(None, 0, None, None, 0, head.ctypes.data))))
-            nb, nt = int(head[0]), int(head[1])
-            coords, ranges, tris = np.empty((nb, 3), np.int32), np.empty((nb, 2), np.int64), np.empty((nt, 3, 3), np.float32)
-            if nb:
-                out = _MeshOut(tris.ctypes.data if nt else None, nt, coords.ctypes.data, ranges.ctypes.data, nb, head.ctypes.data)
-                self._check(self.lib.se_hip_mesh_blocks_host(self._h, C.byref(sel), C.byref(out)))
-                assert (head == (nb, nt, nb, nt)).all(), head
-            return {"coords": coords, "ranges": ranges, "triangles": tris}
-        import torch
-        dev = torch.device("cuda", self._device or 0)
-        torch.cuda.current_stream(dev).synchronize()
-        hd = torch.zeros(4, dtype=torch.int64, device=dev)
-        self._check(self.lib.se_hip_mesh_blocks(self._h, C.byref(sel), C.byref(_MeshOut(None, 0, None, None, 0, hd.data_ptr()))))
-        self.sync()
-        nb, nt = (int(v) for v in hd[:2].tolist())
-        coords = torch.empty((nb, 3), dtype=torch.int32, device=dev)
-        ranges = torch.empty((nb, 2), dtype=torch.int64, device=dev)
-        tris = torch.empty((nt, 3, 3), dtype=torch.float32, device=dev)
+            fn, sync = self.lib.se_hip_mesh_blocks_host, lambda: None      # (the host entry synchronises itself)
+            head = np.zeros(4, np.int64)
+            alloc, addr = (lambda shape, dt: np.empty(shape, dt)), (lambda a: a.ctypes.data)
+        else:
+            import torch
+            dev = torch.device("cuda", self._device or 0)
+            head = torch.zeros(4, dtype=torch.int64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            fn, sync = self.lib.se_hip_mesh_blocks, self.sync
+            alloc, addr = (lambda shape, dt: torch.empty(shape, dtype=getattr(torch, np.dtype(dt).name), device=dev)), (lambda a: a.data_ptr())
+        # a sizing call (no capacity: the header alone), then the real one into arrays of exactly that size
+        self._check(fn(self._h, C.byref(sel), C.byref(_MeshOut(None, 0, None, None, 0, addr(head)))))
+        sync()
+        nb, nt = (int(v) for v in head[:2].tolist())
+        coords, ranges, tris = alloc((nb, 3), np.int32), alloc((nb, 2), np.int64), alloc((nt, 3, 3), np.float32)
         if nb:
-            out = _MeshOut(tris.data_ptr() if nt else None, nt, coords.data_ptr(), ranges.data_ptr(), nb, hd.data_ptr())
-            self._check(self.lib.se_hip_mesh_blocks(self._h, C.byref(sel), C.byref(out)))
-            self.sync()
-            assert hd.tolist() == [nb, nt, nb, nt], hd.tolist()
+            out = _MeshOut(addr(tris) if nt else None, nt, addr(coords), addr(ranges), nb, addr(head))
+            self._check(fn(self._h, C.byref(sel), C.byref(out)))
+            sync()
+            assert head.tolist() == [nb, nt, nb, nt], head.tolist()
         return {"coords": coords, "ranges": ranges, "triangles": tris}
 
     def save(self, filename: str):

@@ -14,36 +14,15 @@ box's voxels in present blocks, estimated on a sample of each set.  Kernel durat
 rocprofv3 --kernel-trace --stats (k_collide_boxes in its kernel_stats.csv)."""
 import argparse
 import ctypes as C
-import json
 import os
-import sys
 import time
 
 import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import torch  # noqa: E402
-
-from supereight_amd.pipeline import _COLLIDE_MODES, OFUSION, SDF, DenseSLAMPipeline, _CollideTest  # noqa: E402
-from supereight_amd.synthetic import SyntheticStream  # noqa: E402
-
-W, H, DIM = 640, 480, 4.8
+from query_bench_common import DIM, ROOT, JsonLines, build_map, hit_vertices, map_tag   # (puts the repository root on sys.path)
+from supereight_amd.pipeline import _COLLIDE_MODES, OFUSION, SDF, _CollideTest
 PEAK = 8e12   # HBM bytes/s of the part
-
-
-def build_map(res, field, pooled, frames):
-    mu = 0.1 if field == SDF else 0.02
-    s = SyntheticStream(W, H, DIM, holes=False)
-    p = DenseSLAMPipeline((W, H), res, DIM, field_type=field, max_blocks=24 * (res // 8) ** 2 if pooled else 0)
-    for f in range(frames):
-        p.set_depth(s.depth(f))
-        p.setPose(s.pose(f))
-        p.integration(s.k, 1, mu, f)
-        p.raycasting(s.k, mu, f)
-    v, n = p.vertex_normal()
-    return p, v[n[..., 0] != -2]
 
 
 def box_sets(res, hits, rng):
@@ -100,11 +79,12 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(1)
-    lines = []
+    log = JsonLines()
     for res in args.res:
         for field in (SDF, OFUSION):
             for pooled in (False, True):
-                p, hits = build_map(res, field, pooled, args.frames)
+                p, _, _ = build_map(res, field, pooled, args.frames)
+                hits = hit_vertices(p)
                 sets = box_sets(res, hits, rng)
                 for name, boxes in sets.items():
                     ab = None if args.quick else algorithmic_bytes(p, res, field, boxes, rng)
@@ -129,21 +109,18 @@ def main():
                         torch.cuda.synchronize()
                         wall = (time.perf_counter() - t0) / args.reps
                         us = e0.elapsed_time(e1) * 1e3 / args.reps
-                        rec = {"res": res, "field": "sdf" if field == SDF else "ofusion", "layout": "pooled" if pooled else "dense", "set": name,
+                        rec = {**map_tag(res, field, pooled), "set": name,
                                "mode": mode, "boxes": len(boxes), "us_per_batch": round(us, 2), "wall_us_per_batch": round(wall * 1e6, 2),
                                "boxes_per_s": round(len(boxes) / (us * 1e-6), 1),
                                "status_counts": {str(k): int((st == k).sum()) for k in (0, 1, 2)}}
                         if ab is not None:
                             rec["alg_bytes_per_box_strict_upper"] = round(ab, 1)
                             rec["frac_of_8TBps"] = round(ab * len(boxes) / (us * 1e-6) / PEAK, 5)
-                        lines.append(rec)
-                        print(json.dumps(rec), flush=True)
+                        log.emit(rec)
                 p.close()
     if not args.quick:
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
-        with open(args.out, "w") as f:
-            for r in lines:
-                f.write(json.dumps(r) + "\n")
+        log.write(args.out)
 
 
 if __name__ == "__main__":

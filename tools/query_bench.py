@@ -10,21 +10,12 @@ and two output selections: interp + grad (the planner's case) and all five outpu
 Kernel durations come from a separate run under rocprofv3 --kernel-trace --stats (k_query_points in its kernel_stats.csv)."""
 import argparse
 import ctypes as C
-import json
-import os
-import sys
 
 import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import torch  # noqa: E402
-
-from supereight_amd.pipeline import OFUSION, SDF, DenseSLAMPipeline, _QueryOut  # noqa: E402
-from supereight_amd.synthetic import SyntheticStream  # noqa: E402
-
-W, H, DIM = 640, 480, 4.8
+from query_bench_common import DIM, JsonLines, build_map, hit_vertices, map_tag, timed   # (puts the repository root on sys.path)
+from supereight_amd.pipeline import OFUSION, SDF, _QueryOut
 
 
 def algorithmic_bytes(field, pooled, outputs):
@@ -43,19 +34,6 @@ def algorithmic_bytes(field, pooled, outputs):
     return b
 
 
-def build_map(res, field, pooled, frames):
-    mu = 0.1 if field == SDF else 0.02
-    s = SyntheticStream(W, H, DIM, holes=False)
-    p = DenseSLAMPipeline((W, H), res, DIM, field_type=field, max_blocks=24 * (res // 8) ** 2 if pooled else 0)
-    for f in range(frames):
-        p.set_depth(s.depth(f))
-        p.setPose(s.pose(f))
-        p.integration(s.k, 1, mu, f)
-        p.raycasting(s.k, mu, f)
-    v, n = p.vertex_normal()
-    return p, v[n[..., 0] != -2]
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--res", type=str, default="512,1024")
@@ -66,13 +44,14 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     stream = torch.cuda.current_stream(dev)
-    lines = []
+    log = JsonLines()
     gen = torch.Generator(device=dev)
     for res in [int(r) for r in args.res.split(",")]:
         vox = DIM / res
         for field in (SDF, OFUSION):
             for pooled in (False, True):
-                p, hits = build_map(res, field, pooled, args.frames)
+                p, _, _ = build_map(res, field, pooled, args.frames)
+                hits = hit_vertices(p)
                 p.sync()
                 p.set_stream(stream.cuda_stream)       # the queries run on torch's stream, timed by its events
                 nb, _ = p.counts()
@@ -87,28 +66,16 @@ def main():
                     for sel in (("interp", "grad"), ("fine", "coarse", "interp", "grad", "status")):
                         q = _QueryOut(*(outs[k].data_ptr() if k in sel else None for k in ("fine", "coarse", "interp", "grad", "status")))
                         for name, x in pts.items():
-                            p._check(p.lib.se_hip_query_points(p._h, x.data_ptr(), n, C.byref(q)))     # warm-up
-                            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                            a.record(stream)
-                            for _ in range(args.reps):
-                                p._check(p.lib.se_hip_query_points(p._h, x.data_ptr(), n, C.byref(q)))
-                            b.record(stream)
-                            b.synchronize()
-                            us = a.elapsed_time(b) * 1e3 / args.reps
+                            us = timed(stream, args.reps, lambda: p._check(p.lib.se_hip_query_points(p._h, x.data_ptr(), n, C.byref(q))))
                             bpp = algorithmic_bytes(field, pooled, sel)
-                            rec = {"res": res, "field": "sdf" if field == SDF else "ofusion", "layout": "pooled" if pooled else "dense", "blocks": nb,
-                                   "points": n, "set": name, "outputs": "+".join(sel), "us_per_batch": round(us, 2),
-                                   "mpoints_per_s": round(n / us, 1), "alg_bytes_per_point": bpp, "alg_gb_per_s": round(n * bpp / us / 1e3, 1)}
-                            print(json.dumps(rec), flush=True)
-                            lines.append(rec)
+                            log.emit(dict(map_tag(res, field, pooled), blocks=nb, points=n, set=name, outputs="+".join(sel), us_per_batch=round(us, 2),
+                                          mpoints_per_s=round(n / us, 1), alg_bytes_per_point=bpp, alg_gb_per_s=round(n * bpp / us / 1e3, 1)))
                     del pts, outs, idx
                 p.sync()
                 p.close()
                 torch.cuda.empty_cache()
     if args.out:
-        with open(args.out, "w") as f:
-            for rec in lines:
-                f.write(json.dumps(rec) + "\n")
+        log.write(args.out)
 
 
 if __name__ == "__main__":

@@ -11,33 +11,12 @@ and, once per map, the camera raycast of the same pose (se_hip_raycast: k_raycas
 coherent rays.  One JSON line per measurement.  Kernel durations come from a separate run under rocprofv3 --kernel-trace --stats."""
 import argparse
 import ctypes as C
-import json
-import os
-import sys
 
 import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import torch  # noqa: E402
-
-from supereight_amd.pipeline import OFUSION, SDF, DenseSLAMPipeline, _RayOut  # noqa: E402
-from supereight_amd.synthetic import SyntheticStream  # noqa: E402
-
-W, H, DIM = 640, 480, 4.8
-
-
-def build_map(res, field, pooled, frames):
-    mu = 0.1 if field == SDF else 0.02
-    s = SyntheticStream(W, H, DIM, holes=False)
-    p = DenseSLAMPipeline((W, H), res, DIM, field_type=field, max_blocks=24 * (res // 8) ** 2 if pooled else 0)
-    for f in range(frames):
-        p.set_depth(s.depth(f))
-        p.setPose(s.pose(f))
-        p.integration(s.k, 1, mu, f)
-        p.raycasting(s.k, mu, f)
-    return p, s, mu
+from query_bench_common import DIM, H, W, JsonLines, build_map, map_tag, timed   # (puts the repository root on sys.path)
+from supereight_amd.pipeline import OFUSION, SDF, _RayOut
 
 
 def camera_rays(pose, k, dev):
@@ -64,17 +43,6 @@ def random_rays(n, gen, dev):
     return r
 
 
-def timed(stream, reps, fn):
-    fn()   # warm-up
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record(stream)
-    for _ in range(reps):
-        fn()
-    b.record(stream)
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3 / reps
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--res", type=str, default="512,1024")
@@ -85,13 +53,9 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     stream = torch.cuda.current_stream(dev)
-    lines = []
+    log = JsonLines()
+    emit = log.emit
     gen = torch.Generator(device=dev)
-
-    def emit(rec):
-        print(json.dumps(rec), flush=True)
-        lines.append(rec)
-
     for res in [int(r) for r in args.res.split(",")]:
         for field in (SDF, OFUSION):
             for pooled in (False, True):
@@ -100,7 +64,7 @@ def main():
                 p.set_stream(stream.cuda_stream)       # the batches run on torch's stream, timed by its events
                 nb, _ = p.counts()
                 pose = s.pose(args.frames - 1)
-                tag = {"res": res, "field": "sdf" if field == SDF else "ofusion", "layout": "pooled" if pooled else "dense", "blocks": nb}
+                tag = dict(map_tag(res, field, pooled), blocks=nb)
                 p.setPose(pose)
                 us_cam = timed(stream, args.reps, lambda: p.raycasting(s.k, mu, args.frames))
                 emit(dict(tag, kernel="k_raycast", rays=W * H, set="camera", us_per_batch=round(us_cam, 2), mrays_per_s=round(W * H / us_cam, 1)))
@@ -124,9 +88,7 @@ def main():
                 p.close()
                 torch.cuda.empty_cache()
     if args.out:
-        with open(args.out, "w") as f:
-            for rec in lines:
-                f.write(json.dumps(rec) + "\n")
+        log.write(args.out)
 
 
 if __name__ == "__main__":
