@@ -199,6 +199,14 @@ class DenseSLAMSystem {
   bool collidesWith(const int32_t* host_boxes, size_t n, const se_hip_collide_test& test, int32_t mode, uint8_t* host_status) {
     return ok(se_hip_collide_boxes_host(h_, host_boxes, (int64_t)n, &test, mode, host_status));
   }
+  /* Not in the reference's class (an addition of this mirror): se::functor::axis_aligned_map(map, f, min, max) for a list of n boxes with
+   * f = "assign x and / or y where the current value has one of these classes", applied to the device map in list order without save / load --
+   * se_hip_edit_boxes_host, definitions in se_hip.h.  The map afterwards is what se::apply_edits (include/se/axis_aligned.hpp) makes of the
+   * getMap() snapshot taken before.  test may be null when every edit has only == 7; counts[4] (optional): voxel applications, node-value
+   * applications, blocks touched, invalid edits. */
+  bool editMap(const se_hip_edit* host_edits, size_t n, const se_hip_collide_test* test, int32_t mode, int64_t* counts = nullptr) {
+    return ok(se_hip_edit_boxes_host(h_, host_edits, (int64_t)n, test, mode, counts));
+  }
   /* Not in the reference's class (an addition of this mirror): the per-pixel body of raycastKernel for n rays of the caller's
    * (host_rays[n][8]: origin xyz, direction xyz, near, far in metres) answered on the device map without getMap() --
    * se_hip_cast_rays_host, definitions in se_hip.h.  host_out.hit[n][4], .normal[n][3], .status[n]; a null pointer: not wanted. */

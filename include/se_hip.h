@@ -504,6 +504,59 @@ typedef struct se_hip_mesh_out {
 int se_hip_mesh_blocks(se_hip_pipeline* p, const se_hip_mesh_select* select, const se_hip_mesh_out* device_out);
 int se_hip_mesh_blocks_host(se_hip_pipeline* p, const se_hip_mesh_select* select, const se_hip_mesh_out* host_out);
 
+/* ---- batched axis-aligned region edits of the resident map: the reference's map write algorithm se::functor::axis_aligned_map(map, f, min, max)
+ *      (se_core/include/se/functors/axis_aligned_functor.hpp) for N boxes at once, f = "assign x and / or y where the current value has one of
+ *      these classes", without save / load.  The host restatement is include/se/axis_aligned.hpp (se::apply_edits is the executable definition).
+ * An edit visits EXISTING blocks and nodes only and writes voxel / node VALUES only: nothing is allocated or freed, VoxelBlock::active_, the
+ *   block and node counts and everything the raycast and the allocation scan derive from the set of blocks stay as they are.
+ * A call applies the n edits as if one after another in list order (overlapping boxes: the later edit wins).
+ *   lo, hi    the voxel box, half open [lo, hi) per axis -- the reference's (min, max).  An empty or inverted box is valid and selects no voxel
+ *             (and no node value, except through the inclusive test of SE_HIP_EDIT_REFERENCE below when lo == hi).
+ *   flags     SE_HIP_EDIT_SET_X: assign x; SE_HIP_EDIT_SET_Y: assign y (neither: nothing is written, the visits are still counted);
+ *             SE_HIP_EDIT_BLOCKS: visit voxels; SE_HIP_EDIT_NODES: visit node values.
+ *   only      the classes the CURRENT value may have for the edit to apply to it: bit 0 occupied, bit 1 unseen, bit 2 empty (1 << SE_HIP_COLLISION_*),
+ *             7 = any.  The value (x, y), y as float as se_hip_download_blocks returns it, is classified with the call's `test` exactly as
+ *             se_hip_collide_boxes classifies it.  `test` may be null when every edit has only == 7.
+ *   Blocks    every voxel v of an allocated block with lo <= v < hi per axis (update_block).
+ *   Nodes     SE_HIP_EDIT_REFERENCE  exactly update_node, quirks included (deliberate parity): the tested position starts at
+ *                                    unpack_morton(code_) WITH the level bits still in the code and is advanced cumulatively by dir(i) * side / 2,
+ *                                    i.e. with h = side / 2 the eight positions are c0 + (0,0,0), (h,0,0), (h,h,0), (2h,2h,0), (2h,2h,h),
+ *                                    (3h,2h,2h), (3h,3h,3h), (4h,4h,4h); the box test is inclusive at both ends (lo <= v <= hi); value_[i] is
+ *                                    written whether or not child i exists.
+ *             SE_HIP_EDIT_STRICT     value_[i] is written iff the child octant [c + dir(i) * h, c + dir(i) * h + h)^3, c the node's corner,
+ *                                    lies wholly inside [lo, hi).  Blocks are treated identically in both modes.
+ * Invalid edits are skipped whole and counted, never applied in part, and read no map memory: a coordinate of lo or hi outside
+ *   [-2^30, 2^30]; unknown flag bits; only outside 1 .. 7; only != 7 with a null test, a non-finite threshold or occupied_above other than
+ *   0 / 1; a non-finite x with SET_X or y with SET_Y; for SDF a y (with SET_Y) that is not an integer in 0 .. 255 -- the device keeps the
+ *   weight in a byte, the rule by which se_hip_load_map refuses a file.
+ * counts (optional, int64[4], zeroed by the call): [0] (edit, voxel) applications that passed box and predicate, [1] the same for node
+ *   values, [2] blocks with at least one application, [3] invalid edits.
+ * Ordering: the call answers for, and modifies, the map after everything enqueued before it (a scan that ran on the side stream included; a
+ *   later scan on the side stream waits for it).  An outstanding deferred raycast is launched FIRST: frame f's images show the map before the
+ *   edit, as the eager schedule gives them.  The next sweep / raycast / query on the handle sees the edit.  The images and the image ring, the
+ *   launch counters (SE_HIP_K_*) and the timing sums are left alone.  Row-sharded replicas and sharded-sweep handles each hold the whole map:
+ *   the call edits the replica it is given, and keeping replicas equal is the caller's job (the same edits on every replica).
+ * Both entries refuse n < 0, null edits with n > 0 and an unknown mode with SE_HIP_E_INVALID before any launch (n == 0 only zeroes counts),
+ *   and report a sticky SE_HIP_E_CAPACITY like the other batched calls.
+ *   se_hip_edit_boxes       device arrays; enqueued on the handle's stream, asynchronous like the stage calls.
+ *   se_hip_edit_boxes_host  host arrays; staged through a device buffer the handle keeps (and grows); synchronises before it returns. */
+#define SE_HIP_EDIT_SET_X 1u
+#define SE_HIP_EDIT_SET_Y 2u
+#define SE_HIP_EDIT_BLOCKS 4u
+#define SE_HIP_EDIT_NODES 8u
+#define SE_HIP_EDIT_STRICT 0
+#define SE_HIP_EDIT_REFERENCE 1
+typedef struct se_hip_edit {
+  int32_t lo[3], hi[3];   /* voxel box, half open [lo, hi) -- the reference's (min, max) */
+  float x, y;             /* the values to assign */
+  uint32_t flags;         /* SE_HIP_EDIT_SET_X | SET_Y | BLOCKS | NODES */
+  uint32_t only;          /* classes the CURRENT value must have: bit 0 occupied, bit 1 unseen, bit 2 empty; 7 = any */
+} se_hip_edit;            /* 40 bytes */
+int se_hip_edit_boxes(se_hip_pipeline* p, const se_hip_edit* device_edits, int64_t n, const se_hip_collide_test* test,
+                      int32_t mode, int64_t* device_counts);
+int se_hip_edit_boxes_host(se_hip_pipeline* p, const se_hip_edit* host_edits, int64_t n, const se_hip_collide_test* test,
+                           int32_t mode, int64_t* host_counts);
+
 /* ---- measurement (replaces TICK()/TOCK() + PerfStats, se_shared/timings.h:7-15) */
 #define SE_HIP_K_ALLOC_SCAN 0
 #define SE_HIP_K_ALLOC_COMMIT 1

@@ -24,6 +24,7 @@
 #include "se_mesh_kernels.h"
 #include "se_query_kernels.h"
 #include "se_collide_kernels.h"
+#include "se_edit_kernels.h"
 #include "se_ray_kernels.h"
 
 int flush_pending_raycast(se_hip_pipeline* p);   // (defined next to se_hip_frame)
@@ -105,6 +106,7 @@ struct se_hip_pipeline {
   hipStream_t side = nullptr;
   bool own_side = false;       // false after se_hip_set_scan_stream handed one in
   hipEvent_t ev_sweep = nullptr, ev_scan = nullptr;
+  hipEvent_t ev_edit = nullptr;   // se_hip_edit_boxes: recorded behind an edit so that a later scan on the side stream waits for it; created on first use
   bool overlap = false;
   // host gate (see RayArgs::gate): replaces the event between the sweep and the next frame's scan for unsharded replicas
   bool host_gate = false;
@@ -521,8 +523,9 @@ template <typename Check> int query_prologue(se_hip_pipeline* p, Check args_ok) 
   if (int r = args_ok()) return r;
   return join_scan(p);
 }
-// The outputs of an array-in / array-out family (points, boxes, rays): per output the caller's array (null: not asked for) and its bytes per item.
-struct BatchOut { void* ptr; size_t item_bytes; };
+// The outputs of an array-in / array-out family (points, boxes, rays, edits): per output the caller's array (null: not asked for) and its bytes per item
+// -- or, per_call, its bytes whatever n is (the edits' counts).
+struct BatchOut { void* ptr; size_t item_bytes; bool per_call = false; };
 struct BatchOuts { int count; BatchOut o[5]; };
 // Device form: the caller's arrays are device memory and go to `launch(in, out pointers)` as they are; nothing is waited for.
 template <typename Check, typename Launch>
@@ -537,6 +540,7 @@ int batch_device(se_hip_pipeline* p, const void* in, int64_t n, const BatchOuts&
   return SE_HIP_OK;
 }
 // Host form: staging = [input n x in_item_bytes][the outputs asked for, in the order given]; upload, launch on the staged arrays, download.
+// (An input item that is not a multiple of 8 bytes must not be followed by an 8-byte output: the edits' 40-byte records are.)
 template <typename Check, typename Launch>
 int batch_host(se_hip_pipeline* p, const void* in, size_t in_item_bytes, int64_t n, const BatchOuts& out, Check args_ok, Launch launch) {
   if (int r = query_prologue(p, args_ok)) return r;
@@ -544,7 +548,7 @@ int batch_host(se_hip_pipeline* p, const void* in, size_t in_item_bytes, int64_t
   const size_t un = (size_t)n;
   size_t bytes[6], off[6];
   bytes[0] = un * in_item_bytes;
-  for (int k = 0; k < out.count; ++k) bytes[k + 1] = out.o[k].ptr ? un * out.o[k].item_bytes : 0;
+  for (int k = 0; k < out.count; ++k) bytes[k + 1] = out.o[k].ptr ? (out.o[k].per_call ? 1 : un) * out.o[k].item_bytes : 0;
   if (int r = reserve_staging(p, staging_layout(bytes, out.count + 1, off))) return r;
   unsigned char* b = p->staging;
   HIP_TRY(hipMemcpyAsync(b, in, bytes[0], hipMemcpyHostToDevice, p->stream));
@@ -821,6 +825,7 @@ int se_hip_destroy(se_hip_pipeline* p) {
   if (p->own_side && p->side) hipStreamDestroy(p->side);
   if (p->ev_sweep) hipEventDestroy(p->ev_sweep);
   if (p->ev_scan) hipEventDestroy(p->ev_scan);
+  if (p->ev_edit) hipEventDestroy(p->ev_edit);
   if (p->own_stream && p->stream) hipStreamDestroy(p->stream);
   delete p;
   return SE_HIP_OK;
@@ -2192,6 +2197,63 @@ int se_hip_collide_boxes_host(se_hip_pipeline* p, const int32_t* host_boxes, int
   const BatchOuts out{1, {{host_status, 1}}};
   return batch_host(p, host_boxes, 6 * sizeof(int32_t), n, out, [&] { return collide_args(host_boxes, n, test, mode, host_status); },
                     [&](const void* boxes, void* const* o) { launch_collide(p, (const int32_t*)boxes, n, test, mode, (uint8_t*)o[0]); });
+}
+
+
+// ------------------------------------------------------------------------------------ region edits
+static_assert(sizeof(se_hip_edit) == sizeof(EditRec) && sizeof(se_hip_edit) == 40, "se_hip_edit");
+static_assert(SE_HIP_EDIT_SET_X == SE_EDIT_SET_X && SE_HIP_EDIT_SET_Y == SE_EDIT_SET_Y && SE_HIP_EDIT_BLOCKS == SE_EDIT_BLOCKS && SE_HIP_EDIT_NODES == SE_EDIT_NODES,
+              "flags of se_hip_edit");
+namespace {
+int edit_args(const se_hip_edit* edits, int64_t n, int32_t mode) {
+  if (n < 0) return fail(SE_HIP_E_INVALID, "se_hip_edit_boxes: n < 0");
+  if (n > 0 && !edits) return fail(SE_HIP_E_INVALID, "se_hip_edit_boxes: null edits");
+  if (mode != SE_HIP_EDIT_STRICT && mode != SE_HIP_EDIT_REFERENCE) return fail(SE_HIP_E_INVALID, "se_hip_edit_boxes: unknown mode");
+  return SE_HIP_OK;
+}
+// Zeroes the counts, then the block kernel and the node kernel on the handle's stream; a scan that a later frame puts on the side stream
+// (it appends to the block list the edit walks) is made to wait for them.
+int launch_edit(se_hip_pipeline* p, const se_hip_edit* edits, int64_t n, const se_hip_collide_test* test, int32_t mode, int64_t* counts) {
+  const DevMap& m = p->map;
+  const bool test_ok = test && std::isfinite(test->threshold) && (test->occupied_above == 0 || test->occupied_above == 1);
+  const EditArgs a{(const EditRec*)edits, (long long)n, test_ok ? test->threshold : 0.f, test_ok ? test->occupied_above : 0, test_ok ? 1 : 0,
+                   mode == SE_HIP_EDIT_REFERENCE ? 1 : 0, (unsigned long long*)counts};
+  if (counts) HIP_TRY(hipMemsetAsync(counts, 0, 4 * sizeof(int64_t), p->stream));
+  // one wave per block / per eight nodes, grid-stride beyond 4 096 workgroups (the counts live on the device: the grids are sized by the capacities)
+  hipLaunchKernelGGL(k_edit_blocks, dim3(grid_for((size_t)m.cap_blocks * 64, SE_WG, 4096)), dim3(SE_WG), 0, p->stream, m, a);
+  hipLaunchKernelGGL(k_edit_nodes, dim3(grid_for((size_t)m.cap_nodes * 8, SE_WG, 4096)), dim3(SE_WG), 0, p->stream, m, a);
+  if (p->side && p->side != p->stream) {
+    if (!p->ev_edit) HIP_TRY(hipEventCreateWithFlags(&p->ev_edit, hipEventDisableTiming | hipEventDisableSystemFence));
+    HIP_TRY(hipEventRecord(p->ev_edit, p->stream));
+    HIP_TRY(hipStreamWaitEvent(p->side, p->ev_edit, 0));
+  }
+  return SE_HIP_OK;
+}
+}  // namespace
+
+// (no InFrame: a deferred raycast is launched first -- its images must show the map before the edit)
+int se_hip_edit_boxes(se_hip_pipeline* p, const se_hip_edit* device_edits, int64_t n, const se_hip_collide_test* test, int32_t mode,
+                      int64_t* device_counts) {
+  BatchOuts out{1, {}};
+  out.o[0] = BatchOut{device_counts, 4 * sizeof(int64_t), true};
+  int launched = SE_HIP_OK;
+  if (int r = batch_device(p, device_edits, n, out, [&] { return edit_args(device_edits, n, mode); },
+                           [&](const void* e, void* const* o) { launched = launch_edit(p, (const se_hip_edit*)e, n, test, mode, (int64_t*)o[0]); })) return r;
+  if (launched) return launched;
+  if (n == 0 && device_counts) HIP_TRY(hipMemsetAsync(device_counts, 0, 4 * sizeof(int64_t), p->stream));
+  return SE_HIP_OK;
+}
+
+int se_hip_edit_boxes_host(se_hip_pipeline* p, const se_hip_edit* host_edits, int64_t n, const se_hip_collide_test* test, int32_t mode,
+                           int64_t* host_counts) {
+  BatchOuts out{1, {}};
+  out.o[0] = BatchOut{host_counts, 4 * sizeof(int64_t), true};
+  int launched = SE_HIP_OK;
+  if (int r = batch_host(p, host_edits, sizeof(se_hip_edit), n, out, [&] { return edit_args(host_edits, n, mode); },
+                         [&](const void* e, void* const* o) { launched = launch_edit(p, (const se_hip_edit*)e, n, test, mode, (int64_t*)o[0]); })) return r;
+  if (launched) return launched;
+  if (n == 0 && host_counts) std::memset(host_counts, 0, 4 * sizeof(int64_t));
+  return SE_HIP_OK;
 }
 
 

@@ -18,7 +18,9 @@ class LiveMesh:
     def update(self, source, views=None, region=None) -> int:
         """Brings the blocks up to date that `views` (the views integrated since the last update: (pose, k) or (pose, k, width, height)) may
         have touched within `region`.  `source` has mesh_blocks(region=, views=, skip_empty=) as DenseSLAMPipeline has.  With no views, or
-        more than 64 of them, the region alone decides.  Returns the number of blocks replaced or deleted."""
+        more than 64 of them, the region alone decides.  Returns the number of blocks replaced or deleted.
+        After DenseSLAMPipeline.edit / reset the blocks of the edited box changed without any view: update(source, region=(lo - 1, hi)) --
+        no views; lo - 1 because a block's cells also read the first voxel layer of the next block."""
         views = None if views is None else list(views)
         if views is not None and (len(views) == 0 or len(views) > MAX_VIEWS):
             views = None

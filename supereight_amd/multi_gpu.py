@@ -322,5 +322,9 @@ class ShardedPipeline:
             self.p.raycasting(k, mu, frame)
         self._images_full = self.world == 1
 
+    def edit(self, boxes, x=None, y=None, **kw):
+        """DenseSLAMPipeline.edit on this rank's replica.  Every replica holds the whole map: call it with the same arguments on every rank."""
+        return self.p.edit(boxes, x, y, **kw)
+
     def close(self):
         self.p.close()

@@ -75,6 +75,20 @@ COLLISION_OCCUPIED, COLLISION_UNSEEN, COLLISION_EMPTY, COLLISION_INVALID = 0, 1,
 _COLLIDE_MODES = {"strict": 0, "reference": 1}
 
 
+class _Edit(C.Structure):
+    """se_hip_edit of include/se_hip.h (40 bytes)."""
+    _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("x", C.c_float), ("y", C.c_float), ("flags", C.c_uint32), ("only", C.c_uint32)]
+
+
+# se_hip_edit as a numpy record (the host entry's input) -- on the device the same 40 bytes are a torch int32 [N, 10] tensor whose
+# columns 6 and 7 hold the bits of the two floats
+EDIT_DTYPE = np.dtype([("lo", np.int32, 3), ("hi", np.int32, 3), ("x", np.float32), ("y", np.float32), ("flags", np.uint32), ("only", np.uint32)])
+EDIT_SET_X, EDIT_SET_Y, EDIT_BLOCKS, EDIT_NODES = 1, 2, 4, 8
+EDIT_OCCUPIED, EDIT_UNSEEN, EDIT_EMPTY, EDIT_ANY = 1, 2, 4, 7      # bits of se_hip_edit.only: 1 << COLLISION_*
+_EDIT_MODES = {"strict": 0, "reference": 1}
+_EDIT_CLASSES = {"occupied": EDIT_OCCUPIED, "unseen": EDIT_UNSEEN, "empty": EDIT_EMPTY, "any": EDIT_ANY}
+
+
 class _Config(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("volume_resolution", C.c_int32),
                 ("volume_dimension", C.c_float), ("field_type", C.c_int32), ("device", C.c_int32),
@@ -147,6 +161,8 @@ EXPORTS = {
     "se_hip_query_points_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_QueryOut)]),
     "se_hip_collide_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
     "se_hip_collide_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
+    "se_hip_edit_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
+    "se_hip_edit_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
     "se_hip_cast_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.POINTER(_RayOut)]),
     "se_hip_cast_rays_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.POINTER(_RayOut)]),
     "se_hip_mesh_blocks": (C.c_int, [C.c_void_p, C.POINTER(_MeshSelect), C.POINTER(_MeshOut)]),
@@ -680,6 +696,119 @@ class DenseSLAMPipeline:
             self._device_call(torch, b.device, self.lib.se_hip_collide_boxes, b.data_ptr() if n else None, n, C.byref(test), m,
                               out.data_ptr() if n else None)
         return out
+
+    @staticmethod
+    def _edit_only(only) -> int:
+        """se_hip_edit.only from "any", a class name, an iterable of class names or the bit mask itself (1 .. 7)."""
+        if isinstance(only, (bool, np.bool_)):
+            raise TypeError("edit: only must be a class name, an iterable of class names or an int in 1 .. 7, got bool")
+        if isinstance(only, (int, np.integer)):
+            if not 1 <= int(only) <= 7:
+                raise ValueError(f"edit: only must lie in 1 .. 7, got {only}")
+            return int(only)
+        names = [only] if isinstance(only, str) else list(only)
+        bits = 0
+        for nm in names:
+            if nm not in _EDIT_CLASSES:
+                raise ValueError(f"edit: only names must be among {sorted(_EDIT_CLASSES)}, got {nm!r}")
+            bits |= _EDIT_CLASSES[nm]
+        if not bits:
+            raise ValueError("edit: only selects no class")
+        return bits
+
+    def edit_records(self, records, *, test=None, mode: str = "strict", counts: bool = True):
+        """se_hip_edit_boxes on a ready list of se_hip_edit records, applied in list order: a numpy array of EDIT_DTYPE [N] (host entry) or a
+        torch int32 [N, 10] tensor on this handle's GPU (device entry; columns lo xyz, hi xyz, the bits of x and y, flags, only).  test: None
+        or (threshold, occupied_above) for the class predicates.  Invalid records are skipped and counted by the library, not refused here.
+        Returns int64 [4] -- voxel applications, node-value applications, blocks touched, invalid edits -- as a numpy array or a torch tensor
+        (None with counts=False)."""
+        if mode not in _EDIT_MODES:
+            raise ValueError(f"edit: mode must be one of {sorted(_EDIT_MODES)}, got {mode!r}")
+        ctest = None
+        if test is not None:
+            thr, above = test
+            if not isinstance(above, (bool, np.bool_)):
+                raise TypeError(f"edit: occupied_above must be a bool, got {type(above).__name__}")
+            ctest = C.byref(_CollideTest(float(thr), int(bool(above))))
+        m = _EDIT_MODES[mode]
+        if type(records) is np.ndarray and records.dtype == EDIT_DTYPE:
+            if records.ndim != 1:
+                raise ValueError(f"edit: records must have shape [N], got {list(records.shape)}")
+            rec, n = np.ascontiguousarray(records), records.shape[0]
+            out = np.zeros(4, np.int64) if counts else None
+            self._check(self.lib.se_hip_edit_boxes_host(self._h, rec.ctypes.data if n else None, n, ctest, m, out.ctypes.data if counts else None))
+            return out
+        torch, rec, n = self._batch_input("edit", "records", records, np.int32, 10)
+        if torch is None:
+            raise TypeError("edit: records must be a numpy array of EDIT_DTYPE or a torch int32 [N, 10] tensor on the GPU")
+        out = torch.zeros(4, dtype=torch.int64, device=rec.device) if counts else None
+        self._device_call(torch, rec.device, self.lib.se_hip_edit_boxes, rec.data_ptr() if n else None, n, ctest, m, out.data_ptr() if counts else None)
+        return out
+
+    def edit(self, boxes, x=None, y=None, *, only="any", threshold: float = 0.0, occupied_above=None, mode: str = "strict", blocks: bool = True,
+             nodes: bool = True, counts: bool = True):
+        """Batched axis-aligned region edits of the resident map (se_hip_edit_boxes, include/se_hip.h): boxes [N, 6] int32 = lo xyz, hi xyz in
+        voxels, half open, applied in list order (where boxes overlap the later one wins).  x, y: the value to assign -- None (leave it), a
+        scalar or one value per box.  Only existing blocks (blocks=True: their voxels) and nodes (nodes=True: their value_[8]) are written;
+        nothing is allocated.  only: the classes the current value may have -- "any", "occupied", "unseen", "empty", an iterable of these or
+        the bit mask -- judged with threshold / occupied_above exactly as collides() judges (occupied_above defaults by field).  mode "strict":
+        a node value is written iff its child octant lies wholly inside the box; "reference": the reference's update_node, quirks included.
+          - numpy int32 [N, 6]: through the host entry; numpy counts out.
+          - a torch int32 tensor on this handle's GPU (contiguous, [N, 6]): through the device entry; the caller's current torch stream is
+            synchronised first, and the handle before the counts are returned.
+        Returns int64 [4]: voxel applications, node-value applications, blocks touched, invalid edits (None with counts=False).  A box or value
+        the library calls invalid (a coordinate beyond +-2^30, a non-finite value, for SDF a y that is not an integer in 0 .. 255) is skipped
+        and counted there; wrong types and shapes raise TypeError / ValueError before any library call.  After an edit, a LiveMesh is brought
+        up to date with update(pipe, region=(lo - 1, hi))."""
+        if mode not in _EDIT_MODES:
+            raise ValueError(f"edit: mode must be one of {sorted(_EDIT_MODES)}, got {mode!r}")
+        bits = self._edit_only(only)
+        if occupied_above is None:
+            occupied_above = self.field == OFUSION
+        if not isinstance(occupied_above, (bool, np.bool_)):
+            raise TypeError(f"edit: occupied_above must be a bool, got {type(occupied_above).__name__}")
+        thr = float(threshold)
+        if not np.isfinite(np.float32(thr)):
+            raise ValueError(f"edit: threshold must be finite as a float32, got {threshold!r}")
+        for nm, v in (("blocks", blocks), ("nodes", nodes)):
+            if not isinstance(v, (bool, np.bool_)):
+                raise TypeError(f"edit: {nm} must be a bool, got {type(v).__name__}")
+        torch, b, n = self._batch_input("edit", "boxes", boxes, np.int32, 6)
+        flags = (EDIT_SET_X if x is not None else 0) | (EDIT_SET_Y if y is not None else 0) | (EDIT_BLOCKS if blocks else 0) | (EDIT_NODES if nodes else 0)
+        vals = []
+        for nm, v in (("x", x), ("y", y)):
+            if v is None:
+                v = 0.0
+            if torch is not None and _torch_module(v) is not None:
+                v = v.to(device=b.device, dtype=torch.float32)
+            else:
+                v = np.asarray(v, np.float32)
+            if v.ndim != 0 and tuple(v.shape) != (n,):
+                raise ValueError(f"edit: {nm} must be a scalar or have shape [{n}], got {list(v.shape)}")
+            vals.append(v)
+        if torch is None:
+            rec = np.zeros(n, EDIT_DTYPE)
+            rec["lo"], rec["hi"] = b[:, 0:3], b[:, 3:6]
+            rec["x"], rec["y"] = vals
+            rec["flags"], rec["only"] = flags, bits
+        else:
+            rec = torch.empty((n, 10), dtype=torch.int32, device=b.device)
+            rec[:, 0:6] = b
+            fl = rec[:, 6:8].view(torch.float32)
+            for j, v in enumerate(vals):
+                fl[:, j] = v if _torch_module(v) is not None else torch.as_tensor(v).to(b.device)
+            rec[:, 8], rec[:, 9] = flags, bits
+        return self.edit_records(rec, test=(thr, bool(occupied_above)), mode=mode, counts=counts)
+
+    def init_value(self):
+        """initValue() of the handle's field type as (x, y): what a voxel holds before anything is fused into it."""
+        return (0.0, 0.0) if self.field == OFUSION else (1.0, 0.0)
+
+    def reset(self, boxes, **kw):
+        """Forget regions: every voxel and node value the boxes select back to initValue(), so that the next frames re-fuse them
+        (edit(boxes, x, y) with both values of initValue(); the keywords of edit apply)."""
+        ix, iy = self.init_value()
+        return self.edit(boxes, ix, iy, **kw)
 
     _RAY_OUTPUTS = (("hit", (4,), np.float32), ("normal", (3,), np.float32), ("status", (), np.uint8))
 
