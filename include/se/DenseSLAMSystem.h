@@ -207,6 +207,13 @@ class DenseSLAMSystem {
   bool editMap(const se_hip_edit* host_edits, size_t n, const se_hip_collide_test* test, int32_t mode, int64_t* counts = nullptr) {
     return ok(se_hip_edit_boxes_host(h_, host_edits, (int64_t)n, test, mode, counts));
   }
+  /* Not in the reference's class (an addition of this mirror): Octree::allocate over the keys of every octant of a level that n voxel boxes touch,
+   * on the device map without save / load -- se_hip_allocate_boxes_host, definitions in se_hip.h.  The map afterwards is what se::allocate_boxes
+   * (include/se/allocate_region.hpp) makes of the getMap() snapshot taken before.  counts[4] (optional): blocks created, nodes created, requested
+   * (box, octant) pairs, invalid boxes; new_keys (optional, capacity_words words): [count, key ...] of the octants created on request. */
+  bool allocateRegion(const se_hip_alloc_box* host_boxes, size_t n, int64_t* counts = nullptr, uint64_t* new_keys = nullptr, int64_t capacity_words = 0) {
+    return ok(se_hip_allocate_boxes_host(h_, host_boxes, (int64_t)n, counts, new_keys, capacity_words));
+  }
   /* Not in the reference's class (an addition of this mirror): the per-pixel body of raycastKernel for n rays of the caller's
    * (host_rays[n][8]: origin xyz, direction xyz, near, far in metres) answered on the device map without getMap() --
    * se_hip_cast_rays_host, definitions in se_hip.h.  host_out.hit[n][4], .normal[n][3], .status[n]; a null pointer: not wanted. */

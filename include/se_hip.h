@@ -557,6 +557,56 @@ int se_hip_edit_boxes(se_hip_pipeline* p, const se_hip_edit* device_edits, int64
 int se_hip_edit_boxes_host(se_hip_pipeline* p, const se_hip_edit* host_edits, int64_t n, const se_hip_collide_test* test,
                            int32_t mode, int64_t* host_counts);
 
+/* ---- batched region allocation of the resident map: the reference's Octree::allocate(key_t*, int) (se_core/include/se/octree.hpp:792-856; also
+ *      reachable as Octree::insert, both exercised by multiscale_unittest.cpp) over the keys of every octant of a level that a list of voxel boxes
+ *      touches, without fusing depth and without save / load.  It is what makes se_hip_edit_boxes usable on a fresh map or in a region the camera has
+ *      not seen: allocate the region, then edit it.  The host restatement is include/se/allocate_region.hpp (se::allocate_boxes is the executable
+ *      definition).
+ *   lo, hi    the voxel box, half open [lo, hi) per axis.  An empty or inverted box is valid and requests nothing.
+ *   level     0 = leaf level: the 8^3 voxel blocks; 1 .. leaf_level (log2(size) - 3) = the octants of that tree level (side size >> level), created as
+ *             nodes without children below them (leaf_level names the blocks again).
+ *   reserved  must be 0.
+ * Box i requests every octant of its level whose cube intersects [lo, hi) clipped to the volume [0, size)^3.  After the call every requested octant
+ *   and all its ancestors exist, and nothing else was created.  Created blocks hold initValue() in every voxel and have VoxelBlock::active_ = true,
+ *   as allocate_level sets them (octree.hpp:841); created nodes hold initValue() in value_[8], as a node the allocation scan creates.  Octants that
+ *   existed before, their values and their active flags are untouched.  The result does not depend on list order or on overlaps between boxes.
+ * Relation to the reference: this equals Octree::allocate over the same key list EXCEPT for the keys[0] rule of unique_multiscale
+ *   (algorithms/unique.hpp:64-79), which keeps the list's smallest key whatever its level and so walks it down along child 0 to a leaf when it is
+ *   coarser than leaf level -- the quirk the OFusion allocation scan restates; this entry does not apply it.  Leaf-level lists (duplicates or not)
+ *   give exactly the reference's blocks and nodes; coarse or mixed lists do once the list also holds the leaf block at (0, 0, 0); a purely coarse
+ *   list differs by exactly that child-0 chain.
+ * Invalid boxes are skipped whole and counted, and read no map memory: a coordinate of lo or hi outside [-2^30, 2^30]; level outside
+ *   0 .. leaf_level; reserved != 0.
+ * counts (optional, int64[4], zeroed by the call): [0] blocks created, [1] nodes created (ancestors included), [2] requested (box, octant) pairs
+ *   after clipping -- the sum over the valid boxes of the cells of their clipped octant range, overlaps counted per box --, [3] invalid boxes.
+ * new_keys (optional, capacity_words >= 1 words): the allocation scan's list format [count, key ...], keys in the reference's format (Morton code |
+ *   level): one key per octant this call created BECAUSE IT WAS REQUESTED.  A requested octant that came into being within the call as the ancestor of
+ *   a finer request is implied by that request's key and need not be listed; which of the two comes first is unspecified.  In any order: every key
+ *   names a requested octant that did not exist before, none appears twice, and the ancestor closure of the keys together with the map before is the
+ *   map after.  count is the number wanted; only capacity_words - 1 keys are written.  The list is fit to hand to se_hip_alloc_commit of a peer
+ *   replica, whose block and node sets are then equal.  The order of the keys is unspecified.
+ * Ordering, exactly as for se_hip_edit_boxes: an outstanding deferred raycast is launched FIRST (frame f's images show the map before the
+ *   allocation); a scan on the side stream is joined; a later scan on the side stream waits for the call.  The next sweep / raycast / query on the
+ *   handle sees the new octants, occupancy bits and beam-start marks included.  The launch counters (SE_HIP_K_*), the timing sums, the images and the
+ *   image ring are left alone.
+ * Capacity: a block or node pool that runs out raises the usual sticky SE_HIP_E_CAPACITY (the octants that did not fit are absent; reported by this
+ *   call's host form and by the next stage call; acknowledged with se_hip_clear_overflow).  A dense grid cannot run out of blocks.
+ * Row-sharded replicas and sharded-sweep handles each hold the whole map: the caller issues the same call on every replica, or hands new_keys to
+ *   se_hip_alloc_commit of the peers.
+ * Both entries refuse n < 0, null boxes with n > 0 and capacity_words < 1 with a non-null key list with SE_HIP_E_INVALID before any launch;
+ *   n == 0 only zeroes the outputs (counts and the list's count word).
+ *   se_hip_allocate_boxes       device arrays; enqueued on the handle's stream, asynchronous like the stage calls.
+ *   se_hip_allocate_boxes_host  host arrays; staged through a device buffer the handle keeps (and grows); synchronises before it returns. */
+typedef struct se_hip_alloc_box {
+  int32_t lo[3], hi[3];   /* voxel box, half open [lo, hi) */
+  int32_t level;          /* 0 = leaf level (8^3 blocks); 1 .. leaf_level = octants of that level (nodes without children below them) */
+  uint32_t reserved;      /* must be 0 */
+} se_hip_alloc_box;       /* 32 bytes */
+int se_hip_allocate_boxes(se_hip_pipeline* p, const se_hip_alloc_box* device_boxes, int64_t n, int64_t* device_counts,
+                          uint64_t* device_new_keys, int64_t capacity_words);
+int se_hip_allocate_boxes_host(se_hip_pipeline* p, const se_hip_alloc_box* host_boxes, int64_t n, int64_t* host_counts,
+                               uint64_t* host_new_keys, int64_t capacity_words);
+
 /* ---- measurement (replaces TICK()/TOCK() + PerfStats, se_shared/timings.h:7-15) */
 #define SE_HIP_K_ALLOC_SCAN 0
 #define SE_HIP_K_ALLOC_COMMIT 1

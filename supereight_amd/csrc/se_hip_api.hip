@@ -25,6 +25,7 @@
 #include "se_query_kernels.h"
 #include "se_collide_kernels.h"
 #include "se_edit_kernels.h"
+#include "se_alloc_kernels.h"
 #include "se_ray_kernels.h"
 
 int flush_pending_raycast(se_hip_pipeline* p);   // (defined next to se_hip_frame)
@@ -106,7 +107,7 @@ struct se_hip_pipeline {
   hipStream_t side = nullptr;
   bool own_side = false;       // false after se_hip_set_scan_stream handed one in
   hipEvent_t ev_sweep = nullptr, ev_scan = nullptr;
-  hipEvent_t ev_edit = nullptr;   // se_hip_edit_boxes: recorded behind an edit so that a later scan on the side stream waits for it; created on first use
+  hipEvent_t ev_edit = nullptr;   // se_hip_edit_boxes, se_hip_allocate_boxes: recorded behind the call so that a later scan on the side stream waits for it; created on first use
   bool overlap = false;
   // host gate (see RayArgs::gate): replaces the event between the sweep and the next frame's scan for unsharded replicas
   bool host_gate = false;
@@ -524,7 +525,7 @@ template <typename Check> int query_prologue(se_hip_pipeline* p, Check args_ok) 
   return join_scan(p);
 }
 // The outputs of an array-in / array-out family (points, boxes, rays, edits): per output the caller's array (null: not asked for) and its bytes per item
-// -- or, per_call, its bytes whatever n is (the edits' counts).
+// -- or, per_call, its bytes whatever n is (the edits' counts; the allocations' counts and key list).
 struct BatchOut { void* ptr; size_t item_bytes; bool per_call = false; };
 struct BatchOuts { int count; BatchOut o[5]; };
 // Device form: the caller's arrays are device memory and go to `launch(in, out pointers)` as they are; nothing is waited for.
@@ -2256,6 +2257,69 @@ int se_hip_edit_boxes_host(se_hip_pipeline* p, const se_hip_edit* host_edits, in
   return SE_HIP_OK;
 }
 
+
+// ------------------------------------------------------------------------------------ region allocation
+static_assert(sizeof(se_hip_alloc_box) == sizeof(AllocBox) && sizeof(se_hip_alloc_box) == 32, "se_hip_alloc_box");
+namespace {
+int alloc_boxes_args(const se_hip_alloc_box* boxes, int64_t n, const uint64_t* keys, int64_t capacity_words) {
+  if (n < 0) return fail(SE_HIP_E_INVALID, "se_hip_allocate_boxes: n < 0");
+  if (n > 0 && !boxes) return fail(SE_HIP_E_INVALID, "se_hip_allocate_boxes: null boxes");
+  if (keys && capacity_words < 1) return fail(SE_HIP_E_INVALID, "se_hip_allocate_boxes: capacity_words < 1");
+  return SE_HIP_OK;
+}
+// The counter snapshot (which also zeroes the outputs), the box kernel, the counter difference -- on the handle's stream, inserting in place
+// (p->map has defer_occ = defer_mark = 0: no raycast runs beside it, and the next one finds occ[] and the beam-start marks complete; the handle's
+// own key lists and occ_commit_due are not involved).  A scan that a later frame puts on the side stream is made to wait, and the host's copy of
+// the counters (launch geometry of the next sweep, a pool overflow) is refreshed in stream order.
+int launch_alloc_boxes(se_hip_pipeline* p, const se_hip_alloc_box* boxes, int64_t n, int64_t* counts, uint64_t* keys, int64_t capacity_words) {
+  const DevMap& m = p->map;
+  const AllocBoxArgs a{(const AllocBox*)boxes, (long long)n, (unsigned long long*)counts, (unsigned long long*)keys,
+                       keys ? (unsigned long long)(capacity_words - 1) : 0ull};
+  if (counts || keys) hipLaunchKernelGGL(k_alloc_boxes_begin, dim3(1), dim3(64), 0, p->stream, m, a);
+  // 2 048 waves whatever the list holds (it lives on the device): eight per compute unit, 16 chunks each for the whole volume at 1024^3
+  hipLaunchKernelGGL(k_alloc_boxes, dim3(512), dim3(SE_WG), 0, p->stream, m, a);
+  if (counts) hipLaunchKernelGGL(k_alloc_boxes_end, dim3(1), dim3(64), 0, p->stream, m, a);
+  HIP_TRY(hipMemcpyAsync(p->ctr_host, m.ctr, C_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
+  if (p->side && p->side != p->stream) {
+    if (!p->ev_edit) HIP_TRY(hipEventCreateWithFlags(&p->ev_edit, hipEventDisableTiming | hipEventDisableSystemFence));
+    HIP_TRY(hipEventRecord(p->ev_edit, p->stream));
+    HIP_TRY(hipStreamWaitEvent(p->side, p->ev_edit, 0));
+  }
+  return SE_HIP_OK;
+}
+BatchOuts alloc_boxes_outs(int64_t* counts, uint64_t* keys, int64_t capacity_words) {
+  BatchOuts out{2, {}};
+  out.o[0] = BatchOut{counts, 4 * sizeof(int64_t), true};
+  out.o[1] = BatchOut{keys, (size_t)std::max<int64_t>(capacity_words, 1) * sizeof(uint64_t), true};
+  return out;
+}
+}  // namespace
+
+// (no InFrame: a deferred raycast is launched first -- its images must show the map before the allocation)
+int se_hip_allocate_boxes(se_hip_pipeline* p, const se_hip_alloc_box* device_boxes, int64_t n, int64_t* device_counts, uint64_t* device_new_keys,
+                          int64_t capacity_words) {
+  int launched = SE_HIP_OK;
+  if (int r = batch_device(p, device_boxes, n, alloc_boxes_outs(device_counts, device_new_keys, capacity_words),
+                           [&] { return alloc_boxes_args(device_boxes, n, device_new_keys, capacity_words); },
+                           [&](const void* b, void* const* o) { launched = launch_alloc_boxes(p, (const se_hip_alloc_box*)b, n, (int64_t*)o[0], (uint64_t*)o[1], capacity_words); })) return r;
+  if (launched) return launched;
+  if (n == 0 && device_counts) HIP_TRY(hipMemsetAsync(device_counts, 0, 4 * sizeof(int64_t), p->stream));
+  if (n == 0 && device_new_keys) HIP_TRY(hipMemsetAsync(device_new_keys, 0, sizeof(uint64_t), p->stream));
+  return SE_HIP_OK;
+}
+
+int se_hip_allocate_boxes_host(se_hip_pipeline* p, const se_hip_alloc_box* host_boxes, int64_t n, int64_t* host_counts, uint64_t* host_new_keys,
+                               int64_t capacity_words) {
+  int launched = SE_HIP_OK;
+  // (a pool that ran out: SE_HIP_E_CAPACITY from the read-back behind the downloads -- counts and keys say what fitted)
+  if (int r = batch_host(p, host_boxes, sizeof(se_hip_alloc_box), n, alloc_boxes_outs(host_counts, host_new_keys, capacity_words),
+                         [&] { return alloc_boxes_args(host_boxes, n, host_new_keys, capacity_words); },
+                         [&](const void* b, void* const* o) { launched = launch_alloc_boxes(p, (const se_hip_alloc_box*)b, n, (int64_t*)o[0], (uint64_t*)o[1], capacity_words); })) return r;
+  if (launched) return launched;
+  if (n == 0 && host_counts) std::memset(host_counts, 0, 4 * sizeof(int64_t));
+  if (n == 0 && host_new_keys) host_new_keys[0] = 0;
+  return SE_HIP_OK;
+}
 
 // ------------------------------------------------------------------------------------ batched ray casts
 static_assert(SE_HIP_RAY_VALID == SE_R_VALID && SE_HIP_RAY_ENTERED == SE_R_ENTERED && SE_HIP_RAY_HIT == SE_R_HIT && SE_HIP_RAY_NORMAL == SE_R_NORMAL,

@@ -89,6 +89,15 @@ _EDIT_MODES = {"strict": 0, "reference": 1}
 _EDIT_CLASSES = {"occupied": EDIT_OCCUPIED, "unseen": EDIT_UNSEEN, "empty": EDIT_EMPTY, "any": EDIT_ANY}
 
 
+class _AllocBox(C.Structure):
+    """se_hip_alloc_box of include/se_hip.h (32 bytes)."""
+    _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("level", C.c_int32), ("reserved", C.c_uint32)]
+
+
+# se_hip_alloc_box as a numpy record (the host entry's input) -- on the device the same 32 bytes are a torch int32 [N, 8] tensor
+ALLOC_DTYPE = np.dtype([("lo", np.int32, 3), ("hi", np.int32, 3), ("level", np.int32), ("reserved", np.uint32)])
+
+
 class _Config(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("volume_resolution", C.c_int32),
                 ("volume_dimension", C.c_float), ("field_type", C.c_int32), ("device", C.c_int32),
@@ -163,6 +172,8 @@ EXPORTS = {
     "se_hip_collide_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
     "se_hip_edit_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
     "se_hip_edit_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
+    "se_hip_allocate_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
+    "se_hip_allocate_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
     "se_hip_cast_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.POINTER(_RayOut)]),
     "se_hip_cast_rays_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.POINTER(_RayOut)]),
     "se_hip_mesh_blocks": (C.c_int, [C.c_void_p, C.POINTER(_MeshSelect), C.POINTER(_MeshOut)]),
@@ -809,6 +820,79 @@ class DenseSLAMPipeline:
         (edit(boxes, x, y) with both values of initValue(); the keywords of edit apply)."""
         ix, iy = self.init_value()
         return self.edit(boxes, ix, iy, **kw)
+
+    def allocate_records(self, records, *, counts: bool = True, key_capacity: int = 0):
+        """se_hip_allocate_boxes on a ready list of se_hip_alloc_box records: a numpy array of ALLOC_DTYPE [N] (host entry) or a torch int32
+        [N, 8] tensor on this handle's GPU (device entry; columns lo xyz, hi xyz, level, reserved).  Invalid records are skipped and counted
+        by the library, not refused here.  key_capacity > 0: also the list [count, key ...] of the octants the call created on request, with
+        room for that many keys (uint64 [key_capacity + 1]; count may exceed what was written).  Returns (counts, keys): int64 [4] -- blocks
+        created, nodes created, requested (box, octant) pairs, invalid boxes -- and the list, numpy arrays or torch tensors; None where not
+        asked for.  A pool that runs out raises SeHipError (SE_HIP_E_CAPACITY; clear_overflow acknowledges it)."""
+        if isinstance(key_capacity, (bool, np.bool_)) or not isinstance(key_capacity, (int, np.integer)) or key_capacity < 0:
+            raise ValueError(f"allocate: key_capacity must be an int >= 0, got {key_capacity!r}")
+        words = int(key_capacity) + 1 if key_capacity else 0
+        if type(records) is np.ndarray and records.dtype == ALLOC_DTYPE:
+            if records.ndim != 1:
+                raise ValueError(f"allocate: records must have shape [N], got {list(records.shape)}")
+            rec, n = np.ascontiguousarray(records), records.shape[0]
+            out = np.zeros(4, np.int64) if counts else None
+            keys = np.zeros(words, np.uint64) if words else None
+            self._check(self.lib.se_hip_allocate_boxes_host(self._h, rec.ctypes.data if n else None, n, out.ctypes.data if counts else None,
+                                                            keys.ctypes.data if words else None, words))
+            return out, keys
+        torch, rec, n = self._batch_input("allocate", "records", records, np.int32, 8)
+        if torch is None:
+            raise TypeError("allocate: records must be a numpy array of ALLOC_DTYPE or a torch int32 [N, 8] tensor on the GPU")
+        out = torch.zeros(4, dtype=torch.int64, device=rec.device) if counts else None
+        keys = torch.zeros(words, dtype=torch.int64, device=rec.device) if words else None      # (torch has no uint64 arithmetic: the bits)
+        self._device_call(torch, rec.device, self.lib.se_hip_allocate_boxes, rec.data_ptr() if n else None, n, out.data_ptr() if counts else None,
+                          keys.data_ptr() if words else None, words)
+        return out, keys
+
+    def allocate(self, boxes, level=0, return_keys: bool = False):
+        """Batched region allocation of the resident map (se_hip_allocate_boxes, include/se_hip.h): boxes [N, 6] int32 = lo xyz, hi xyz in
+        voxels, half open.  Every octant of `level` -- 0: the 8^3 blocks; 1 .. leaf level: the octants of that tree level, as nodes without
+        children; a scalar or one value per box -- that a box touches inside the volume exists afterwards, with all its ancestors; new blocks
+        hold initValue() and are active, what existed is untouched.  It is Octree::allocate over those keys without the keys[0] rule.  Use
+        it in front of edit() for a region the camera has not seen.
+          - numpy int32 [N, 6]: through the host entry; numpy out.
+          - a torch int32 tensor on this handle's GPU (contiguous, [N, 6]): through the device entry; the caller's current torch stream is
+            synchronised first, and the handle before the results are returned.
+        Returns int64 [4]: blocks created, nodes created (ancestors included), requested (box, octant) pairs after clipping, invalid boxes.
+        return_keys=True: (counts, keys) with keys the uint64 keys (torch: their bits as int64) of the octants the call created on request,
+        fit for alloc_commit on a peer replica as [len(keys), *keys].  A box the library calls invalid (a coordinate beyond +-2^30, a level
+        outside 0 .. leaf level) is skipped and counted there; wrong types and shapes raise TypeError / ValueError before any library call."""
+        if not isinstance(return_keys, (bool, np.bool_)):
+            raise TypeError(f"allocate: return_keys must be a bool, got {type(return_keys).__name__}")
+        torch, b, n = self._batch_input("allocate", "boxes", boxes, np.int32, 6)
+        if torch is not None and _torch_module(level) is not None:
+            lv = level.to(device=b.device, dtype=torch.int32)
+        else:
+            lv = np.asarray(level)
+            if lv.dtype.kind not in "iu":
+                raise TypeError(f"allocate: level must be an integer or an integer array, got {lv.dtype}")
+            lv = lv.astype(np.int32)
+        if lv.ndim != 0 and tuple(lv.shape) != (n,):
+            raise ValueError(f"allocate: level must be a scalar or have shape [{n}], got {list(lv.shape)}")
+        if torch is None:
+            rec = np.zeros(n, ALLOC_DTYPE)
+            rec["lo"], rec["hi"], rec["level"] = b[:, 0:3], b[:, 3:6], lv
+        else:
+            rec = torch.zeros((n, 8), dtype=torch.int32, device=b.device)
+            rec[:, 0:6] = b
+            rec[:, 6] = lv if _torch_module(lv) is not None else torch.as_tensor(lv).to(b.device)
+        if not return_keys:
+            return self.allocate_records(rec)[0]
+        # room for every key the call can write: at most one per requested pair (blocks are the finest request), never more than the tree holds
+        cap = 0
+        if n:
+            bb = (b.cpu().numpy() if torch is not None else b).astype(np.int64)
+            lo = np.clip(bb[:, 0:3], 0, self.size) // 8
+            hi = (np.clip(bb[:, 3:6], 0, self.size) + 7) // 8
+            cap = min(int(np.prod(np.maximum(hi - lo, 0), axis=1).sum()), (self.size // 8) ** 3 * 8 // 7 + 1)
+        counts, keys = self.allocate_records(rec, key_capacity=max(cap, 1))
+        k = int(keys[0])
+        return counts, keys[1:1 + k]
 
     _RAY_OUTPUTS = (("hit", (4,), np.float32), ("normal", (3,), np.float32), ("status", (), np.uint8))
 
