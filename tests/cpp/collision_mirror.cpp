@@ -5,65 +5,22 @@
 //   usage: collision_mirror <scene.raw> <poses.bin> <volume_res> <volume_dim> <mu>
 // Prints one line: "checked <n> occupied <n> unseen <n> empty <n> differ <n> bad <n>" (counts of the reference answers; differ = boxes
 // whose two modes disagree).
-#ifndef SE_FIELD_TYPE
-#define SE_FIELD_TYPE SDF
-#endif
-#include <se/DenseSLAMSystem.h>
+#include "mirror_scene.hpp"
 #include <se/octree_collision.hpp>
 
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <random>
-#include <set>
-#include <tuple>
 #include <type_traits>
 #include <vector>
 
-
 int main(int argc, char** argv) {
-  if (argc < 6) { std::fprintf(stderr, "usage: %s scene.raw poses.bin res dim mu\n", argv[0]); return 2; }
-  FILE* raw = std::fopen(argv[1], "rb");
-  FILE* pf = std::fopen(argv[2], "rb");
-  if (!raw || !pf) { std::fprintf(stderr, "cannot open inputs\n"); return 2; }
-  const int res = std::atoi(argv[3]);
-  const float dim = (float)std::atof(argv[4]), mu = (float)std::atof(argv[5]);
-  uint32_t wh[2];
-  if (std::fread(wh, 4, 2, raw) != 2) return 2;
-  std::fseek(raw, 0, SEEK_SET);
-  const int W = (int)wh[0], H = (int)wh[1];
-  const Eigen::Vector4f k(481.2f * W / 640.f, 480.f * W / 640.f, 320.f * W / 640.f, 240.f * W / 640.f);
-  std::vector<int> pyramid = {10, 5, 4};
-  Configuration config;
-  config.compute_size_ratio = 1; config.tracking_rate = 1; config.integration_rate = 1; config.rendering_rate = 4;
-  config.volume_resolution = Eigen::Vector3i(res, res, res); config.volume_size = Eigen::Vector3f(dim, dim, dim);
-  config.initial_pos_factor = Eigen::Vector3f(0.f, 0.f, 0.f); config.pyramid = pyramid;
-  config.dump_volume_file = ""; config.input_file = argv[1]; config.log_file = ""; config.groundtruth_file = argv[2];
-  config.gt_transform = Eigen::Matrix4f::Identity(); config.camera = k; config.camera_overrided = false;
-  config.mu = mu; config.fps = 0; config.blocking_read = false; config.icp_threshold = 1e-5f; config.no_gui = true;
-  config.render_volume_fullsize = false; config.bilateralFilter = false;
-  config.colouredVoxels = false; config.multiResolution = false; config.bayesian = false;
-  DenseSLAMSystem pipeline(Eigen::Vector2i(W, H), Eigen::Vector3i(res, res, res), Eigen::Vector3f(dim, dim, dim),
-                           Eigen::Vector3f(0.f, 0.f, 0.f), pyramid, config);
-  std::vector<unsigned short> depth((size_t)W * H);
-  std::vector<unsigned char> rgb((size_t)W * H * 3);
-  float pose_rm[16];
-  unsigned frame = 0;
-  while (std::fread(wh, 4, 2, raw) == 2) {
-    if (std::fread(depth.data(), 2, depth.size(), raw) != depth.size()) break;
-    if (std::fread(wh, 4, 2, raw) != 2 || std::fread(rgb.data(), 1, rgb.size(), raw) != rgb.size()) break;
-    if (std::fread(pose_rm, 4, 16, pf) != 16) break;
-    Eigen::Matrix4f pose;
-    for (int r = 0; r < 4; ++r)
-      for (int c = 0; c < 4; ++c) pose(r, c) = pose_rm[r * 4 + c];
-    pipeline.preprocessing(depth.data(), Eigen::Vector2i(W, H), false);
-    pipeline.setPose(pose);
-    pipeline.integration(k, 1, mu, frame);
-    pipeline.raycasting(k, mu, frame);
-    ++frame;
-  }
+  MirrorScene scene;
+  if (int rc = scene.replay(argc, argv, 6, "scene.raw poses.bin res dim mu")) return rc;
+  DenseSLAMSystem& pipeline = *scene.pipeline;
+  const int res = scene.res;
   std::shared_ptr<se::Octree<FieldType> > map;
   const auto t_map = std::chrono::steady_clock::now();
   pipeline.getMap(map);

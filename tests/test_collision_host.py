@@ -10,27 +10,9 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.host_util import COLLISION_KATS_EXPECTED, bare_pipeline, build_kats
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KATS_SRC = os.path.join(ROOT, "tests", "cpp", "collision_kats.cpp")
-
-# case -> (reference mode, strict mode); 0 occupied, 1 unseen, 2 empty
-EXPECTED = {
-    "TotallyUnseen": (1, 1), "PartiallyUnseen": (1, 1), "Empty": (2, 2), "Collision": (0, 0), "CollisionFreeLeaf": (2, 2),
-    # an occupied voxel in the block of larger Morton code: the reference's last visited leaf (the smaller one, all empty) replaces it
-    "QuirkLeafOrder": (2, 0),
-    # the absent child's own value_[1] is occupied, the reference reads the parent's value_[0] (empty)
-    "QuirkParentSlot0": (2, 0),
-    # box (2,2,2) side 2: the inclusive test reaches voxel (4,4,4), which is occupied
-    "QuirkInclusive": (0, 2),
-}
-
-
-def build_kats(out_dir) -> str:
-    exe = os.path.join(str(out_dir), "collision_kats")
-    r = subprocess.run(["g++", "-std=c++14", "-O2", "-Wall", "-Werror", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), KATS_SRC, "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
 
 
 def test_header_declares_the_collision_entries():
@@ -62,17 +44,8 @@ def test_build_lists_the_collision_kernel_header():
     assert '#include "se_collide_kernels.h"' in src
 
 
-class _NoLib:
-    """Stands in for libse_hip.so: any call is a test failure (the checks must fire before the library is reached)."""
-    def __getattr__(self, name):
-        raise AssertionError(f"library called: {name}")
-
-
-def _pipeline(field=0):
-    from supereight_amd.pipeline import DenseSLAMPipeline
-    p = DenseSLAMPipeline.__new__(DenseSLAMPipeline)      # (no handle)
-    p.lib, p._h, p.field = _NoLib(), None, field
-    return p
+def _pipeline():
+    return bare_pipeline(field=0)
 
 
 @pytest.mark.parametrize("boxes,exc", [
@@ -116,15 +89,15 @@ def test_collides_refuses_bad_torch_boxes():
 
 
 def test_reference_kats_and_quirk_cases_on_the_host_mirror(tmp_path):
-    exe = build_kats(tmp_path)
+    exe = build_kats("collision_kats", tmp_path)
     r = subprocess.run([exe, "kats"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
     got = {f[0]: (int(f[1]), int(f[2])) for f in (line.split() for line in r.stdout.splitlines())}
-    assert got == EXPECTED
+    assert got == COLLISION_KATS_EXPECTED
 
 
 def test_closed_form_equals_the_literal_traversal(tmp_path):
-    exe = build_kats(tmp_path)
+    exe = build_kats("collision_kats", tmp_path)
     r = subprocess.run([exe, "random", "40", "7"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr + r.stdout
     f = r.stdout.split()

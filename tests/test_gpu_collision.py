@@ -4,7 +4,6 @@ se_hip_query_points(coarse) at every voxel (room and stress streams, SDF and OFu
 against the C++ mirror's getMap() snapshot (tests/cpp/collision_mirror.cpp); invariants; and the schedule (streaming handle, the map, the
 images and the launch counters left alone, the device path, n = 0, one batch of 1 M boxes at 1024^3)."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -12,13 +11,11 @@ import pytest
 
 from supereight_amd.pipeline import (COLLISION_EMPTY, COLLISION_INVALID, COLLISION_OCCUPIED, COLLISION_UNSEEN, OFUSION, SDF,
                                      DenseSLAMPipeline, _CollideTest)
-from supereight_amd.rawio import write_raw
-from supereight_amd.synthetic import SyntheticStream, make_stream, render_depth_mm
-from tests.test_collision_host import EXPECTED, build_kats
+from tests.gpu_state_util import H, W, map_state, run_stream
+from tests.host_util import COLLISION_KATS_EXPECTED, build_kats
+from tests.mirror_util import build_mirror, run_mirror, write_scene
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-W, H = 160, 120
 INIT = {SDF: (1.0, 0.0), OFUSION: (0.0, 0.0)}    # voxel_traits<T>::initValue()
 
 # the KAT / quirk cases of tests/cpp/collision_kats.cpp: map, lo, side
@@ -36,7 +33,7 @@ CASES = {
 
 @pytest.mark.parametrize("max_blocks", [0, 64], ids=["dense", "pooled"])
 def test_kats_and_quirks_on_the_device(tmp_path, max_blocks):
-    exe = build_kats(tmp_path)
+    exe = build_kats("collision_kats", tmp_path)
     r = subprocess.run([exe, "save", str(tmp_path)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
     p = DenseSLAMPipeline((W, H), 256, 5.0, field_type=SDF, max_blocks=max_blocks)
@@ -45,7 +42,7 @@ def test_kats_and_quirks_on_the_device(tmp_path, max_blocks):
             p.load(str(tmp_path / f"{mp}.bin"))
             box = np.array([list(lo) + list(side)], np.int32)
             got = (int(p.collides(box, threshold=5.0, mode="reference")[0]), int(p.collides(box, threshold=5.0, mode="strict")[0]))
-            assert got == EXPECTED[name], name
+            assert got == COLLISION_KATS_EXPECTED[name], name
     finally:
         p.close()
 
@@ -107,23 +104,6 @@ def _boxes(p, n, dim, rng):
     return np.ascontiguousarray(np.concatenate(sets).astype(np.int32))
 
 
-def _run(kind, field, n, dim, max_blocks, frames, streaming=False, check=None):
-    mu = 0.1 if field == SDF else 0.02
-    s = make_stream(kind, W, H, dim, holes=False)
-    p = DenseSLAMPipeline((W, H), n, dim, field_type=field, max_blocks=max_blocks, streaming=streaming)
-    for f in range(frames):
-        p.set_depth(s.depth(f))
-        p.setPose(s.pose(f))
-        p.integration(s.k, 1, mu, f)
-        if streaming:
-            p.raycasting_deferred(s.k, mu, f)
-        else:
-            p.raycasting(s.k, mu, f)
-        if check is not None:
-            check(p, f)
-    return p
-
-
 STRICT = [("room", SDF, 256, 2.4, 0), ("room", SDF, 256, 2.4, 8192), ("room", OFUSION, 256, 2.4, 0), ("room", OFUSION, 256, 2.4, 8192),
           ("stress", SDF, 512, 4.8, 0), ("stress", SDF, 512, 4.8, 16384), ("stress", OFUSION, 512, 4.8, 0), ("stress", OFUSION, 512, 4.8, 16384)]
 
@@ -151,7 +131,7 @@ def test_strict_mode_equals_brute_force(kind, field, n, dim, max_blocks):
         exp1 = grid[torch_idx(v)].cpu().numpy()
         assert (p.collides(one) == exp1).all()
 
-    p = _run(kind, field, n, dim, max_blocks, 4, check=check)
+    p = run_stream(kind, field, n, dim, max_blocks, 4, check=check)
     p.close()
     assert {COLLISION_OCCUPIED, COLLISION_UNSEEN, COLLISION_EMPTY} <= seen
 
@@ -164,26 +144,17 @@ def torch_idx(v):
 
 @pytest.mark.parametrize("tag,mu", [("SDF", 0.1), ("OFusion", 0.02)], ids=["sdf", "ofusion"])
 def test_reference_mode_equals_the_host_mirror(tmp_path, tag, mu):
-    exe = str(tmp_path / f"collision_mirror_{tag}")
-    subprocess.run(["g++", "-std=c++14", "-O2", "-ffp-contract=off", f"-DSE_FIELD_TYPE={tag}", "-I" + os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cpp", "collision_mirror.cpp"), "-o", exe, "-L" + os.path.join(ROOT, "supereight_amd"), "-lse_hip",
-                    "-Wl,-rpath," + os.path.join(ROOT, "supereight_amd")], check=True, capture_output=True)
+    exe = build_mirror(tmp_path, "collision_mirror", tag)
     Wm, Hm, N, dim, frames = 320, 240, 256, 4.8, 3
-    s = SyntheticStream(Wm, Hm, dim, holes=False)
-    raw, pf = str(tmp_path / "scene.raw"), str(tmp_path / "poses.bin")
-    write_raw(raw, [render_depth_mm(f, Wm, Hm, dim) for f in range(frames)])
-    np.stack([s.pose(f) for f in range(frames)]).astype(np.float32).tofile(pf)
-    r = subprocess.run([exe, raw, pf, str(N), str(dim), str(mu)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr
-    f = r.stdout.split()
-    res = {f[i]: int(f[i + 1]) for i in range(0, len(f), 2)}
+    raw, pf, _ = write_scene(tmp_path, Wm, Hm, dim, frames)
+    res, r = run_mirror(exe, [raw, pf, N, dim, mu], timeout=600)
     assert res["bad"] == 0, r.stderr
     assert res["checked"] > 2000 and res["occupied"] > 0 and res["unseen"] > 0 and res["empty"] > 0 and res["differ"] > 0
 
 
 @pytest.mark.parametrize("field,max_blocks", [(SDF, 0), (OFUSION, 4096)], ids=["sdf_dense", "ofusion_pooled"])
 def test_invalid_boxes_and_threshold_direction(field, max_blocks):
-    p = _run("room", field, 256, 2.4, max_blocks, 2)
+    p = run_stream("room", field, 256, 2.4, max_blocks, 2)
     try:
         L = 1 << 30
         bad = np.array([[0, 0, 0, 0, 1, 1], [0, 0, 0, 1, -3, 1], [0, 0, 0, 1, 1, -(1 << 31)], [-L - 1, 0, 0, 1, 1, 1], [0, L + 1, 0, 1, 1, 1],
@@ -206,13 +177,8 @@ def test_invalid_boxes_and_threshold_direction(field, max_blocks):
         p.close()
 
 
-def _state(p):
-    c, x, y, a = p.blocks()
-    nodes = p.nodes()
-    v, nrm = p.vertex_normal()
-    launches = {k: d["launches"] for k, d in p.timings().items()}
-    return [c, x.view(np.uint32), y.view(np.uint32), a] + [u.view(np.uint32) if u.dtype == np.float32 else u for u in nodes] + \
-        [v.view(np.uint32), nrm.view(np.uint32)], launches
+def _launches(p):
+    return {k: d["launches"] for k, d in p.timings().items()}
 
 
 @pytest.mark.parametrize("field", [SDF, OFUSION], ids=["sdf", "ofusion"])
@@ -228,17 +194,17 @@ def test_collide_sees_the_map_of_the_frames_before_it(field):
             ans[streaming].append((p.collides(boxes), p.collides(boxes, mode="reference")))
         return check
 
-    a = _run("room", field, 256, 2.4, 0, 4, streaming=True, check=rec(True))
-    b = _run("room", field, 256, 2.4, 0, 4, streaming=False, check=rec(False))
+    a = run_stream("room", field, 256, 2.4, 0, 4, streaming=True, check=rec(True))
+    b = run_stream("room", field, 256, 2.4, 0, 4, streaming=False, check=rec(False))
     try:
         for (s1, r1), (s2, r2) in zip(ans[True], ans[False]):
             assert (s1 == s2).all() and (r1 == r2).all()
         a.enable_timing(True)
-        before, la = _state(a)
+        before, la = map_state(a), _launches(a)
         for _ in range(3):
             a.collides(boxes)
             a.collides(boxes, mode="reference")
-        after, lb = _state(a)
+        after, lb = map_state(a), _launches(a)
         assert la == lb
         assert all((u == w).all() for u, w in zip(before, after))
     finally:
@@ -248,7 +214,7 @@ def test_collide_sees_the_map_of_the_frames_before_it(field):
 @pytest.mark.parametrize("field,max_blocks", [(SDF, 4096), (OFUSION, 0)], ids=["sdf_pooled", "ofusion_dense"])
 def test_device_path_equals_host_path(field, max_blocks):
     import torch
-    p = _run("room", field, 256, 2.4, max_blocks, 2)
+    p = run_stream("room", field, 256, 2.4, max_blocks, 2)
     try:
         rng = np.random.default_rng(4)
         boxes = np.ascontiguousarray(np.concatenate([rng.integers(-20, 260, (5000, 3)), rng.integers(1, 40, (5000, 3))], 1).astype(np.int32))
@@ -266,7 +232,7 @@ def test_device_path_equals_host_path(field, max_blocks):
 
 def test_collide_entries_refuse_bad_arguments():
     import torch
-    p = _run("room", SDF, 256, 2.4, 0, 1)
+    p = run_stream("room", SDF, 256, 2.4, 0, 1)
     try:
         lib = p.lib
         boxes = np.zeros((4, 6), np.int32)
@@ -287,7 +253,7 @@ def test_collide_entries_refuse_bad_arguments():
 def test_one_million_boxes_at_1024():
     import torch
     n, dim = 1024, 4.8
-    p = _run("room", SDF, n, dim, 0, 3)
+    p = run_stream("room", SDF, n, dim, 0, 3)
     try:
         rng = np.random.default_rng(8)
         m = 1 << 20

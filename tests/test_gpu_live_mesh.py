@@ -5,20 +5,19 @@ Every comparison of triangles is bit for bit.
     every update equal to the export; the device's selection lies within the loosened restatement and leaves blocks out), capacities,
     calls between streamed frames, the entry paths and the refusals."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle.binding import OraclePipeline
 from supereight_amd.livemesh import LiveMesh
-from supereight_amd.pipeline import OFUSION, SDF, DenseSLAMPipeline, SeHipError, _MeshOut, _MeshSelect, _MeshView
+from supereight_amd.pipeline import OFUSION, SDF, DenseSLAMPipeline, _MeshOut, _MeshSelect, _MeshView
 from supereight_amd.synthetic import make_stream
 from tests import live_mesh_util as L
+from tests.gpu_state_util import map_state
+from tests.mirror_util import build_mirror, run_mirror, write_scene
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIM = 4.8
 
 
@@ -287,24 +286,18 @@ def test_calls_between_streamed_frames(field, max_blocks):
         gpu0.close(); gpu1.close(); cpu.close()
 
 
-def _map_state(p):
-    c, x, y, a = p.blocks()
-    v, n = p.vertex_normal()
-    return [c, x.view(np.uint32), y.view(np.uint32), a, v.view(np.uint32), n.view(np.uint32)]
-
-
 def test_calls_disturb_nothing_on_a_synchronous_handle():
     s, gpu, _ = _device("room", SDF, 512, 0, 320, 240, 4)
     try:
         gpu.enable_timing(True)
-        before, t0, n0 = _map_state(gpu), gpu.timings(), gpu.launch_counts()
+        before, t0, n0 = map_state(gpu), gpu.timings(), gpu.launch_counts()
         view = [(np.asarray(s.pose(3), np.float32), s.k)]
         first = L.by_coords(gpu.mesh_blocks(views=view))
         gpu.mesh_blocks(device=True)
         gpu.mesh_blocks(region=((0, 0, 0), (200, 200, 200)), skip_empty=True, device=True)
         assert gpu.launch_counts() == n0
         assert gpu.timings() == t0
-        assert all((u == w).all() for u, w in zip(before, _map_state(gpu)))
+        assert all((u == w).all() for u, w in zip(before, map_state(gpu)))
         assert L.by_coords(gpu.mesh_blocks(views=view)) == first and any(first.values())
     finally:
         gpu.close()
@@ -314,11 +307,10 @@ def test_calls_disturb_nothing_on_a_synchronous_handle():
 def test_entry_paths_agree(tmp_path, field, max_blocks):
     """Host entry (numpy) = device entry through torch = device entry with raw pointers = C++ meshBlocks, byte-identical per block."""
     import torch
-    from supereight_amd.rawio import write_raw
-    from supereight_amd.synthetic import SyntheticStream, render_depth_mm
+    from supereight_amd.synthetic import render_depth_mm
     W, H, N, dim, frames, n_views = 160, 120, 256, 2.4, 5, 2
     mu = _mu(field)
-    s = SyntheticStream(W, H, dim, holes=False)
+    raw, pf, s = write_scene(tmp_path, W, H, dim, frames)
     mm = [render_depth_mm(f, W, H, dim) for f in range(frames)]
     poses = np.stack([s.pose(f) for f in range(frames)]).astype(np.float32)
     p = DenseSLAMPipeline((W, H), N, dim, field_type=field, max_blocks=max_blocks)
@@ -346,17 +338,9 @@ def test_entry_paths_agree(tmp_path, field, max_blocks):
         assert h.tolist() == [nb, nt, nb, nt]
         assert _payload_dict({"coords": c.cpu().numpy(), "ranges": r.cpu().numpy(), "triangles": t.cpu().numpy()}, N, dim) == ref
         # the C++ mirror
-        tmp = str(tmp_path)
-        exe = os.path.join(tmp, "mesh_blocks_mirror")
-        tag = "SDF" if field == SDF else "OFusion"
-        subprocess.run(["g++", "-std=c++14", "-O2", "-ffp-contract=off", f"-DSE_FIELD_TYPE={tag}", "-I" + os.path.join(ROOT, "include"),
-                        os.path.join(ROOT, "tests", "cpp", "mesh_blocks_mirror.cpp"), "-o", exe, "-L" + os.path.join(ROOT, "supereight_amd"), "-lse_hip",
-                        "-Wl,-rpath," + os.path.join(ROOT, "supereight_amd")], check=True, capture_output=True)
-        raw, pf, of = (os.path.join(tmp, f"{x}.bin") for x in ("scene", "poses", "out"))
-        write_raw(raw, mm)
-        poses.tofile(pf)
-        res = subprocess.run([exe, raw, pf, str(N), str(dim), str(mu), str(n_views), str(lo), str(hi), "1", of], capture_output=True, text=True, timeout=300)
-        assert res.returncode == 0, res.stderr
+        exe = build_mirror(tmp_path, "mesh_blocks_mirror", "SDF" if field == SDF else "OFusion")
+        of = str(tmp_path / "out.bin")
+        _, res = run_mirror(exe, [raw, pf, N, dim, mu, n_views, lo, hi, 1, of], timeout=300)
         data = np.fromfile(of, np.uint8)
         hd = data[:32].view(np.int64)
         assert hd.tolist() == [nb, nt, nb, nt]

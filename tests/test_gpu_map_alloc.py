@@ -9,17 +9,12 @@ import pytest
 from oracle.binding import OraclePipeline
 from supereight_amd.pipeline import ALLOC_DTYPE, COLLISION_EMPTY, COLLISION_UNSEEN, OFUSION, SDF, DenseSLAMPipeline, SeHipError
 from supereight_amd.synthetic import make_stream
+from tests.gpu_state_util import H, W, bits, run_stream, streamed_with
+from tests.host_util import LIMIT, box_records, closure_truth, make_keys
 from tests.parity_util import compare_maps, compare_raycast
-from tests.test_gpu_collision import _run
-from tests.test_map_alloc_host import LIMIT, box_records, closure_truth, make_keys
 
 pytestmark = pytest.mark.gpu
-W, H = 160, 120
 INIT = {SDF: (1.0, 0.0), OFUSION: (0.0, 0.0)}    # voxel_traits<T>::initValue()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _sets(p):
@@ -245,7 +240,7 @@ def test_a_start_volume_can_be_declared_free_on_a_fresh_map(field, max_blocks):
 # ------------------------------------------------------------------ what existed stays
 @pytest.mark.parametrize("kind,field,n,dim,max_blocks", [("room", SDF, 256, 2.4, 0), ("stress", OFUSION, 512, 4.8, 65536)], ids=["room_sdf_dense", "stress_ofusion_pooled"])
 def test_an_overlapping_allocation_leaves_what_existed_untouched(kind, field, n, dim, max_blocks):
-    p = _run(kind, field, n, dim, max_blocks, 5)
+    p = run_stream(kind, field, n, dim, max_blocks, 5)
     try:
         c0, x0, y0, a0 = p.blocks()
         code0, side0, nx0, ny0 = p.nodes()
@@ -265,8 +260,8 @@ def test_an_overlapping_allocation_leaves_what_existed_untouched(kind, field, n,
         oldn = np.isin(code1, code0)
         assert old.sum() == len(k0) and oldn.sum() == len(code0)           # both downloads are in key order: the old rows keep their order
         assert (k1[old] == k0).all() and (code1[oldn] == code0).all() and (side1[oldn] == side0).all()
-        assert (_bits(x1[old]) == _bits(x0)).all() and (_bits(y1[old]) == _bits(y0)).all() and (a1[old] == a0).all()
-        assert (_bits(nx1[oldn]) == _bits(nx0)).all() and (_bits(ny1[oldn]) == _bits(ny0)).all()
+        assert (bits(x1[old]) == bits(x0)).all() and (bits(y1[old]) == bits(y0)).all() and (a1[old] == a0).all()
+        assert (bits(nx1[oldn]) == bits(nx0)).all() and (bits(ny1[oldn]) == bits(ny0)).all()
         ix, iy = np.float32(INIT[field][0]), np.float32(INIT[field][1])
         assert (x1[~old] == ix).all() and (y1[~old] == iy).all() and (a1[~old] == 1).all() and (nx1[~oldn] == ix).all() and (ny1[~oldn] == iy).all()
         assert (x0 != ix).any()                                              # the map held fused values
@@ -329,43 +324,19 @@ def test_a_small_pool_reports_capacity():
 
 
 # ------------------------------------------------------------------ schedule
-def _streamed(alloc_after, frames=8, slots=8):
-    import torch
-    n, dim, mu = 256, 2.4, 0.1
-    s = make_stream("room", W, H, dim, holes=False)
-    p = DenseSLAMPipeline((W, H), n, dim, field_type=SDF, streaming=True)
-    ring = torch.zeros((slots, 2, W * H * 3), dtype=torch.float32, device="cuda:0")
-    p.set_image_ring(ring.data_ptr(), slots, keepalive=ring)
-    box = np.array([[0, 0, 0, n, n, 200]], np.int32)       # most of the room
-    log = {}
-    for f in range(frames):
-        p.set_depth(s.depth(f)); p.setPose(s.pose(f))
-        p.integration(s.k, 1, mu, f)
-        p.raycasting_deferred(s.k, mu, f)
-        if f == alloc_after:
-            log["fused"] = p.frame_is_fused()
-            log["before"] = p.launch_counts()
-            log["counts"] = p.allocate(box)
-            log["after"] = p.launch_counts()
-            p.allocate(box)
-            log["again"] = p.launch_counts()
-    p.sync()
-    out = ring.cpu().numpy().copy()
-    log["blocks"] = p.counts()[0]
-    p.close()
-    return out, log
-
-
 def test_allocation_flushes_a_deferred_raycast_first():
     """A streaming handle with an image ring and a twin without the allocation: the slot of frame f is the same on both when the allocation
     is issued between frame f and f + 1 (new blocks hold initValue(): the later images are the same too), the launch counters show that
     raycast as a launch of its own, and the allocation itself moves no counter."""
     f = 5
-    alloc, log = _streamed(f)
-    twin, tlog = _streamed(-1)
+    def blocks(p, log):
+        log["blocks"] = p.counts()[0]
+
+    alloc, log = streamed_with(lambda p, box: p.allocate(box), f, at_end=blocks)
+    twin, tlog = streamed_with(lambda p, box: p.allocate(box), -1, at_end=blocks)
     assert log["fused"]
     for g in range(f + 1):
-        assert (_bits(alloc[g]) == _bits(twin[g])).all(), g
+        assert (bits(alloc[g]) == bits(twin[g])).all(), g
     b, a, again = log["before"], log["after"], log["again"]
     assert b["pending"] and not a["pending"]
     assert a["raycast"] == b["raycast"] + 1 and a["fused"] == b["fused"]   # launched alone, not with a scan
@@ -411,7 +382,7 @@ def test_device_allocation_without_host_synchronisation():
             for h in (p, q):
                 h.set_depth(depth); h.setPose(s.pose(g)); h.integration(s.k, 1, mu, g); h.raycasting(s.k, mu, g)
         for u, w in zip(p.blocks() + p.nodes() + p.vertex_normal(), q.blocks() + q.nodes() + q.vertex_normal()):
-            assert (_bits(u) == _bits(w)).all() if u.dtype == np.float32 else (u == w).all()
+            assert (bits(u) == bits(w)).all() if u.dtype == np.float32 else (u == w).all()
         q.close()
         # n == 0: nothing but the outputs, zeroed
         c0, k0 = p.allocate_records(np.zeros(0, ALLOC_DTYPE), key_capacity=3)

@@ -12,11 +12,10 @@ import pytest
 from supereight_amd.pipeline import (COLLISION_EMPTY, EDIT_BLOCKS, EDIT_DTYPE, EDIT_NODES, EDIT_SET_X, EDIT_SET_Y, OFUSION, SDF,
                                      DenseSLAMPipeline, _CollideTest)
 from supereight_amd.synthetic import make_stream
-from tests.test_gpu_collision import _run
-from tests.test_map_edit_host import build_kats
+from tests.gpu_state_util import H, W, bits, map_state, run_stream, streamed_with
+from tests.host_util import build_kats, unpack
 
 pytestmark = pytest.mark.gpu
-W, H = 160, 120
 INIT = {SDF: (1.0, 0.0), OFUSION: (0.0, 0.0)}    # voxel_traits<T>::initValue()
 LIMIT = 1 << 30
 OFF = np.stack([np.arange(512) & 7, (np.arange(512) >> 3) & 7, np.arange(512) >> 6], 1).astype(np.int64)   # voxel index -> (x, y, z)
@@ -26,16 +25,6 @@ DIR = np.stack([np.arange(8) & 1, (np.arange(8) >> 1) & 1, np.arange(8) >> 2], 1
 
 
 # ------------------------------------------------------------------ the truth, in numpy, from the definitions of include/se_hip.h
-def _unpack(code):
-    """unpack_morton of uint64 codes: [n, 3]."""
-    code = code.astype(np.uint64)
-    out = np.zeros((len(code), 3), np.int64)
-    for b in range(21):
-        for k in range(3):
-            out[:, k] |= ((code >> np.uint64(3 * b + k)) & np.uint64(1)).astype(np.int64) << b
-    return out
-
-
 def _valid(e, field, test):
     for v in list(e["lo"]) + list(e["hi"]):
         if not -LIMIT <= int(v) <= LIMIT:
@@ -72,8 +61,8 @@ def truth(field, coords, X, Y, code, side, NX, NY, rec, test, mode):
     writes = np.zeros(X.shape, np.int32)
     suppressed = 0
     c64 = coords.astype(np.int64)
-    corner = _unpack(code & ~np.uint64(0xFFF))
-    ref0 = _unpack(code)                      # the level bits still in the code
+    corner = unpack(code & ~np.uint64(0xFFF))
+    ref0 = unpack(code)                      # the level bits still in the code
     h = (side.astype(np.int64) // 2)[:, None, None]
     strict_lo = corner[:, None, :] + DIR[None] * h           # [nn, 8, 3]
     ref_pos = ref0[:, None, :] + CUM[None] * h
@@ -166,19 +155,9 @@ def make_edits(rng, field, n, dim, coords, hits):
     return np.ascontiguousarray(rec[order]), n_invalid
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _download(p):
-    c, x, y, a = p.blocks()
-    code, side, nx, ny = p.nodes()
-    return c, x, y, a, code, side, nx, ny
-
-
 def _check_list(p, field, n, dim, rng, mode, device):
     import torch
-    c, x, y, a, code, side, nx, ny = _download(p)
+    c, x, y, a, code, side, nx, ny = p.blocks() + p.nodes()
     v, nrm = p.vertex_normal()
     hits = v[nrm[..., 0] != -2].reshape(-1, 3)
     assert len(hits) > 100
@@ -193,14 +172,14 @@ def _check_list(p, field, n, dim, rng, mode, device):
         got = p.edit_records(drec, test=test, mode=mode).cpu().numpy()
     else:
         got = p.edit_records(rec, test=test, mode=mode)
-    c2, x2, y2, a2, code2, side2, nx2, ny2 = _download(p)
+    c2, x2, y2, a2, code2, side2, nx2, ny2 = p.blocks() + p.nodes()
     print(f"{mode} device={device}: counts {got.tolist()} expected {ecounts.tolist()} {info}")
     assert (c2 == c).all() and (a2 == a).all() and (code2 == code).all() and (side2 == side).all()      # block set, node set, active flags
     assert (got == ecounts).all(), (got, ecounts)
     for nm, g, e in (("x", x2, ex), ("y", y2, ey), ("node x", nx2, enx), ("node y", ny2, eny)):
-        bad = np.argwhere(_bits(g) != _bits(e))
+        bad = np.argwhere(bits(g) != bits(e))
         assert len(bad) == 0, (nm, len(bad), bad[:5].tolist(), g[tuple(bad[0])], e[tuple(bad[0])])
-    assert (_bits(x2) != _bits(x)).any() and ((_bits(nx2) != _bits(nx)).any() or (_bits(ny2) != _bits(ny)).any())
+    assert (bits(x2) != bits(x)).any() and ((bits(nx2) != bits(nx)).any() or (bits(ny2) != bits(ny)).any())
 
 
 LISTS = [("room", SDF, 256, 2.4, 0), ("room", SDF, 256, 2.4, 8192), ("room", OFUSION, 256, 2.4, 0), ("room", OFUSION, 256, 2.4, 8192),
@@ -220,14 +199,14 @@ def test_edit_lists_equal_the_numpy_truth(kind, field, n, dim, max_blocks):
         if f == 4:
             _check_list(p, field, n, dim, rng, "reference", device=True)
 
-    p = _run(kind, field, n, dim, max_blocks, 5, check=check)
+    p = run_stream(kind, field, n, dim, max_blocks, 5, check=check)
     p.close()
 
 
 # ------------------------------------------------------------------ the reference's known answers
 @pytest.mark.parametrize("max_blocks", [0, 1024], ids=["dense", "pooled"])
 def test_reference_known_answers_on_the_device(tmp_path, max_blocks):
-    exe = build_kats(tmp_path)
+    exe = build_kats("edit_kats", tmp_path)
     path = str(tmp_path / "band.bin")
     r = subprocess.run([exe, "save", path], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
@@ -259,7 +238,7 @@ def test_readers_see_the_edit():
     from tests import ray_cast_util as U
     n, dim, mu, frames = 256, 2.4, 0.1, 5
     s = make_stream("room", W, H, dim, holes=False)
-    p = _run("room", SDF, n, dim, 0, frames)
+    p = run_stream("room", SDF, n, dim, 0, frames)
     try:
         lib = U.load()
         pose = s.pose(frames - 1)
@@ -318,42 +297,17 @@ def test_readers_see_the_edit():
 
 
 # ------------------------------------------------------------------ schedule
-def _streamed(edit_after, frames=8, slots=8):
-    import torch
-    n, dim, mu = 256, 2.4, 0.1
-    s = make_stream("room", W, H, dim, holes=False)
-    p = DenseSLAMPipeline((W, H), n, dim, field_type=SDF, streaming=True)
-    ring = torch.zeros((slots, 2, W * H * 3), dtype=torch.float32, device="cuda:0")
-    p.set_image_ring(ring.data_ptr(), slots, keepalive=ring)
-    box = np.array([[0, 0, 0, n, n, 200]], np.int32)       # most of the room, the visible surfaces included
-    log = {}
-    for f in range(frames):
-        p.set_depth(s.depth(f)); p.setPose(s.pose(f))
-        p.integration(s.k, 1, mu, f)
-        p.raycasting_deferred(s.k, mu, f)
-        if f == edit_after:
-            log["fused"] = p.frame_is_fused()
-            log["before"] = p.launch_counts()
-            log["counts"] = p.reset(box)
-            log["after"] = p.launch_counts()
-            p.reset(box, counts=False)
-            log["again"] = p.launch_counts()
-    p.sync()
-    out = ring.cpu().numpy().copy()
-    p.close()
-    return out, log
-
-
 def test_edit_flushes_a_deferred_raycast_first():
     """A streaming handle with an image ring and a twin without edits: the slot of frame f is the same on both when the edit is issued
     between frame f and f + 1, and the launch counters show that raycast as a launch of its own."""
     f = 5
-    edited, log = _streamed(f)
-    twin, _ = _streamed(-1)
+    reset, quiet = (lambda p, box: p.reset(box)), (lambda p, box: p.reset(box, counts=False))
+    edited, log = streamed_with(reset, f, again=quiet)
+    twin, _ = streamed_with(reset, -1, again=quiet)
     assert log["fused"]
     for g in range(f + 1):
-        assert (_bits(edited[g]) == _bits(twin[g])).all(), g
-    assert (_bits(edited[f + 1]) != _bits(twin[f + 1])).any()           # the next frame's raycast saw the edit
+        assert (bits(edited[g]) == bits(twin[g])).all(), g
+    assert (bits(edited[f + 1]) != bits(twin[f + 1])).any()           # the next frame's raycast saw the edit
     b, a, again = log["before"], log["after"], log["again"]
     assert b["pending"] and not a["pending"]
     assert a["raycast"] == b["raycast"] + 1 and a["fused"] == b["fused"]   # launched alone, not with a scan
@@ -391,17 +345,17 @@ def test_device_edits_without_host_synchronisation():
         assert p.edit(np.zeros((0, 6), np.int32), 1.0).tolist() == [0, 0, 0, 0]
         assert p.edit(torch.zeros((0, 6), dtype=torch.int32, device="cuda:0"), 1.0).cpu().tolist() == [0, 0, 0, 0]
         # the same unconditional list twice = once
-        once = _download(p)
+        once = map_state(p)
         p.edit_records(rec)
-        twice = _download(p)
-        assert all((_bits(u) == _bits(w)).all() if u.dtype == np.float32 else (u == w).all() for u, w in zip(once, twice))
+        twice = map_state(p)
+        assert all((u == w).all() for u, w in zip(once, twice))
         # refusals, before any launch
         good = _CollideTest(0.0, 0)
         for fn, addr in ((p.lib.se_hip_edit_boxes_host, rec.ctypes.data), (p.lib.se_hip_edit_boxes, drec.data_ptr())):
             for args in ((addr, -1, C.byref(good), 0, None), (None, 4, C.byref(good), 0, None), (addr, 4, C.byref(good), 2, None), (addr, 4, None, -1, None)):
                 assert fn(p._h, *args) == -1
             assert fn(p._h, None, 0, None, 0, None) == 0
-        assert all((_bits(u) == _bits(w)).all() if u.dtype == np.float32 else (u == w).all() for u, w in zip(twice, _download(p)))
+        assert all((u == w).all() for u, w in zip(twice, map_state(p)))
     finally:
         p.close()
 
@@ -409,7 +363,7 @@ def test_device_edits_without_host_synchronisation():
 def test_one_million_edits_at_1024():
     import torch
     n, dim = 1024, 4.8
-    p = _run("room", SDF, n, dim, 0, 4)            # (the camera raycast runs from frame 3 on)
+    p = run_stream("room", SDF, n, dim, 0, 4)            # (the camera raycast runs from frame 3 on)
     try:
         rng = np.random.default_rng(8)
         m = 1 << 20
@@ -454,22 +408,22 @@ def test_one_million_edits_at_1024():
 
 # ------------------------------------------------------------------ the SDF weight rule
 def test_sdf_weight_is_a_byte(tmp_path):
-    p = _run("room", SDF, 256, 2.4, 0, 3)
+    p = run_stream("room", SDF, 256, 2.4, 0, 3)
     q = DenseSLAMPipeline((W, H), 256, 2.4, field_type=SDF)
     try:
-        before = _download(p)
+        before = map_state(p)
         box = np.array([[0, 0, 0, 256, 256, 256]] * 2, np.int32)
         counts = p.edit(box, 0.25, np.float32([100.5, 256.0]))
         assert counts.tolist() == [0, 0, 0, 2]
-        assert all((_bits(u) == _bits(w)).all() if u.dtype == np.float32 else (u == w).all() for u, w in zip(before, _download(p)))
+        assert all((u == w).all() for u, w in zip(before, map_state(p)))
         counts = p.edit(box[:1], None, 255.0, nodes=False)
         assert counts[0] == before[1].size and counts[3] == 0
         _, x, y, _ = p.blocks()
-        assert (y == 255).all() and (_bits(x) == _bits(before[1])).all()
+        assert (y == 255).all() and (bits(x) == before[1]).all()
         path = str(tmp_path / "w255.bin")
         p.save(path)
         q.load(path)
         c2, x2, y2, _ = q.blocks()
-        assert (c2 == before[0]).all() and (y2 == 255).all() and (_bits(x2) == _bits(x)).all()
+        assert (c2 == before[0]).all() and (y2 == 255).all() and (bits(x2) == bits(x)).all()
     finally:
         p.close(); q.close()

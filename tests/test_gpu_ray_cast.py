@@ -8,8 +8,6 @@ raycast by tests/test_ray_cast_host.py.  Device and oracle integrate the same st
   - invalid rays, the schedule (a batch between frames sees exactly the frames before it and disturbs nothing), the four entry paths, a
     batch of 2^25 rays (several launches), n == 0 and the refusals."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,10 +16,11 @@ from supereight_amd.pipeline import OFUSION, SDF, DenseSLAMPipeline, SeHipError,
 from supereight_amd.synthetic import make_stream
 from tests import ray_cast_util as U
 from tests.edge_frames import SHAPE_CASES, edge_stream
+from tests.gpu_state_util import map_state
+from tests.mirror_util import build_mirror, run_mirror, write_scene
 from tests.parity_util import compare_raycast, outside_view
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIM = 4.8
 MISS_NORMAL = np.float32([-2, 0, 0])
 
@@ -244,12 +243,6 @@ def test_invalid_rays_and_mixing(field, max_blocks):
         gpu.close(); cpu.close()
 
 
-def _map_state(p):
-    c, x, y, a = p.blocks()
-    v, n = p.vertex_normal()
-    return [c, x.view(np.uint32), y.view(np.uint32) if y.dtype == np.float32 else y, a, v.view(np.uint32), n.view(np.uint32)]
-
-
 def test_batches_disturb_nothing_on_a_synchronous_handle():
     W, H, N, mu = 320, 240, 512, 0.1
     s = make_stream("room", W, H, DIM, holes=False)
@@ -257,7 +250,7 @@ def test_batches_disturb_nothing_on_a_synchronous_handle():
     try:
         rays = arbitrary_rays(np.random.default_rng(1), N, DIM, n_each=200)
         gpu.enable_timing(True)
-        before, t0 = _map_state(gpu), gpu.timings()
+        before, t0 = map_state(gpu), gpu.timings()
         n0 = gpu.launch_counts()
         first = _cast_dev(gpu, rays, mu)
         import torch
@@ -265,7 +258,7 @@ def test_batches_disturb_nothing_on_a_synchronous_handle():
         gpu.cast_rays(t[:, 0:3].contiguous(), t[:, 3:6].contiguous(), t[:, 6], t[:, 7], mu=mu)
         assert gpu.launch_counts() == n0
         assert gpu.timings() == t0
-        after = _map_state(gpu)
+        after = map_state(gpu)
         assert all((u == w).all() for u, w in zip(before, after))
         again = _cast_dev(gpu, rays, mu)
         for k in first:
@@ -329,11 +322,10 @@ def test_batches_between_streamed_frames(field, max_blocks):
 def test_entry_paths_agree(tmp_path, field, max_blocks):
     """Host entry (numpy) = device entry (raw pointers) = torch path (packed on the device, normalize=True on unit vectors) = C++ castRays."""
     import torch
-    from supereight_amd.rawio import write_raw
-    from supereight_amd.synthetic import SyntheticStream, render_depth_mm
+    from supereight_amd.synthetic import render_depth_mm
     W, H, N, dim, frames = 160, 120, 256, 2.4, 4
     mu = 0.1 if field == SDF else 0.02
-    s = SyntheticStream(W, H, dim, holes=False)
+    raw, pf, s = write_scene(tmp_path, W, H, dim, frames)
     mm = [render_depth_mm(f, W, H, dim) for f in range(frames)]
     poses = np.stack([s.pose(f) for f in range(frames)]).astype(np.float32)
     p = DenseSLAMPipeline((W, H), N, dim, field_type=field, max_blocks=max_blocks)
@@ -365,18 +357,10 @@ def test_entry_paths_agree(tmp_path, field, max_blocks):
         for k in host:
             assert U.bits_equal(nrm[k], ref[k]), k
         # the C++ mirror
-        tmp = str(tmp_path)
-        exe = os.path.join(tmp, "ray_cast_mirror")
-        tag = "SDF" if field == SDF else "OFusion"
-        subprocess.run(["g++", "-std=c++14", "-O2", "-ffp-contract=off", f"-DSE_FIELD_TYPE={tag}", "-I" + os.path.join(ROOT, "include"),
-                        os.path.join(ROOT, "tests", "cpp", "ray_cast_mirror.cpp"), "-o", exe, "-L" + os.path.join(ROOT, "supereight_amd"), "-lse_hip",
-                        "-Wl,-rpath," + os.path.join(ROOT, "supereight_amd")], check=True, capture_output=True)
-        raw, pf, rf, of = (os.path.join(tmp, f"{x}.bin") for x in ("scene", "poses", "rays", "out"))
-        write_raw(raw, mm)
-        poses.tofile(pf)
+        exe = build_mirror(tmp_path, "ray_cast_mirror", "SDF" if field == SDF else "OFusion")
+        rf, of = str(tmp_path / "rays.bin"), str(tmp_path / "out.bin")
         rays.tofile(rf)
-        r = subprocess.run([exe, raw, pf, str(N), str(dim), str(mu), rf, of], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr
+        _, r = run_mirror(exe, [raw, pf, N, dim, mu, rf, of], timeout=300)
         data = np.fromfile(of, np.uint8)
         n = len(rays)
         cpp = {"hit": data[: 16 * n].view(np.float32).reshape(n, 4), "normal": data[16 * n: 28 * n].view(np.float32).reshape(n, 3), "status": data[28 * n:]}

@@ -6,15 +6,9 @@ import os
 import subprocess
 
 from supereight_amd.mapio import load_octree
+from tests.host_util import morton
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _morton(x, y, z):
-    k = 0
-    for i in range(21):
-        k |= ((x >> i) & 1) << (3 * i) | ((y >> i) & 1) << (3 * i + 1) | ((z >> i) & 1) << (3 * i + 2)
-    return k
 
 
 def test_host_octree_read_interface_and_save_layout(tmp_path):
@@ -31,10 +25,10 @@ def test_host_octree_read_interface_and_save_layout(tmp_path):
         assert len(nodes) == 6 and len(blocks) == 1
         for l, n in enumerate(nodes):
             mask = ~((512 >> l) - 1) & 511
-            assert int(n["code"]) == (_morton(40 & mask, 48 & mask, 56 & mask) | l) and int(n["side"]) == 512 >> l
+            assert int(n["code"]) == (morton(40 & mask, 48 & mask, 56 & mask) | l) and int(n["side"]) == 512 >> l
             assert (n["value"]["x"] == 3.0).all() and (n["value"]["y"] == 4.0).all()
         b = blocks[0]
-        assert int(b["code"]) == (_morton(40, 48, 56) | 6) and b["coords"].tolist() == [40, 48, 56]
+        assert int(b["code"]) == (morton(40, 48, 56) | 6) and b["coords"].tolist() == [40, 48, 56]
         assert (b["voxels"]["x"] == 5.0).all() and (b["voxels"]["y"] == 2.0).all()
         # record sizes of the reference's build: 8 + 4 + 8 * sizeof(value) per node, 8 + 12 + 512 * sizeof(value) per block
         vs = 4 + (4 if field == "sdf" else 4 + 8)

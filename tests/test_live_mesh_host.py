@@ -14,6 +14,7 @@ from supereight_amd import pipeline as P
 from supereight_amd.livemesh import LiveMesh
 from supereight_amd.synthetic import StressStream
 from tests import live_mesh_util as L
+from tests.host_util import bare_pipeline
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -35,19 +36,8 @@ def test_header_and_ctypes_declare_the_entries():
     assert [f[0] for f in P._MeshSelect._fields_] == ["lo", "hi", "n_views", "flags", "views"]
 
 
-class _NoLibrary:
-    def __getattr__(self, name):
-        raise AssertionError(f"library call {name} after bad input")
-
-
-def _bare(size=256, W=160, H=120):
-    p = P.DenseSLAMPipeline.__new__(P.DenseSLAMPipeline)
-    p.lib, p._h, p.size, p.dim, p.W, p.H, p._device = _NoLibrary(), None, size, 4.8, W, H, 0
-    return p
-
-
 def test_mesh_blocks_refuses_bad_input_before_any_library_call():
-    p = _bare()
+    p = bare_pipeline(size=256, dim=4.8, W=160, H=120, _device=0)
     pose, k = np.eye(4, dtype=np.float32), np.float32([100, 100, 80, 60])
     bad_pose = pose.copy(); bad_pose[0, 3] = np.nan
     cases = [

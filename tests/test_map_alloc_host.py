@@ -11,72 +11,9 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.host_util import LIMIT, bare_pipeline, box_records, build_kats, closure_truth, make_keys
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KATS_SRC = os.path.join(ROOT, "tests", "cpp", "alloc_kats.cpp")
-LIMIT = 1 << 30
-
-
-def build_kats(out_dir) -> str:
-    exe = os.path.join(str(out_dir), "alloc_kats")
-    r = subprocess.run(["g++", "-std=c++14", "-O2", "-Wall", "-Werror", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), KATS_SRC, "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
-
-
-# ------------------------------------------------------------------ the truth, in numpy, from the definitions of include/se_hip.h
-def spread(v):
-    v = np.asarray(v, np.uint64)
-    r = np.zeros_like(v)
-    for i in range(21):
-        r |= ((v >> np.uint64(i)) & np.uint64(1)) << np.uint64(3 * i)
-    return r
-
-
-def make_keys(corner, level):
-    """Morton code of the voxel corners [n, 3] | level."""
-    c = np.asarray(corner, np.int64).reshape(-1, 3)
-    return spread(c[:, 0]) | (spread(c[:, 1]) << np.uint64(1)) | (spread(c[:, 2]) << np.uint64(2)) | np.uint64(level)
-
-
-def box_records(rows):
-    """[(lo, hi, level[, reserved])] -> ALLOC_DTYPE records."""
-    from supereight_amd.pipeline import ALLOC_DTYPE
-    rec = np.zeros(len(rows), ALLOC_DTYPE)
-    for i, r in enumerate(rows):
-        rec[i]["lo"], rec[i]["hi"], rec[i]["level"] = r[0], r[1], r[2]
-        rec[i]["reserved"] = r[3] if len(r) > 3 else 0
-    return rec
-
-
-def valid(r, leaf):
-    return (all(-LIMIT <= int(v) <= LIMIT for v in list(r["lo"]) + list(r["hi"])) and 0 <= int(r["level"]) <= leaf and int(r["reserved"]) == 0)
-
-
-def closure_truth(size, rec):
-    """The definition, literally: per valid box every octant of its level whose cube meets the box inside the volume; the requested keys,
-    their ancestor closure (the root left out), the number of (box, octant) pairs and of invalid boxes."""
-    max_level = int(np.log2(size))
-    leaf = max_level - 3
-    requested, closure, pairs, invalid = set(), set(), 0, 0
-    for r in rec:
-        if not valid(r, leaf):
-            invalid += 1
-            continue
-        level = leaf if int(r["level"]) == 0 else int(r["level"])
-        side = size >> level
-        lo = np.maximum(r["lo"].astype(np.int64), 0)
-        hi = np.minimum(r["hi"].astype(np.int64), size)
-        if (lo >= hi).any():
-            continue
-        ax = [np.arange(lo[k] // side, (hi[k] - 1) // side + 1) for k in range(3)]
-        g = np.stack(np.meshgrid(*ax, indexing="ij"), -1).reshape(-1, 3) * side
-        pairs += len(g)
-        requested.update(make_keys(g, level).tolist())
-        for l in range(level, 0, -1):
-            s = size >> l
-            closure.update(np.unique(make_keys(g // s * s, l)).tolist())
-    return requested, closure, pairs, invalid
 
 
 def run_dump(exe, tmp_path, size, rec):
@@ -110,7 +47,7 @@ CASES = {
 @pytest.mark.parametrize("case", sorted(CASES))
 @pytest.mark.parametrize("size", [64, 512])
 def test_host_restatement_equals_the_closure_truth(tmp_path, case, size):
-    exe = build_kats(tmp_path)
+    exe = build_kats("alloc_kats", tmp_path)
     rec = box_records(CASES[case](size))
     requested, closure, pairs, invalid = closure_truth(size, rec)
     counts, bk, nk, keys = run_dump(exe, tmp_path, size, rec)
@@ -129,7 +66,7 @@ def test_host_restatement_equals_the_closure_truth(tmp_path, case, size):
 
 
 def test_host_restatement_on_random_maps_and_lists(tmp_path):
-    exe = build_kats(tmp_path)
+    exe = build_kats("alloc_kats", tmp_path)
     r = subprocess.run([exe, "random", "20", "7"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr + r.stdout
     f = r.stdout.split()
@@ -155,7 +92,7 @@ def _oracle_sets(field, size, keys):
 def test_host_restatement_against_the_oracle(tmp_path, field):
     """Octree::allocate of the CPU oracle over the same keys, 512^3: equal on leaf lists, on lists with duplicates and on coarse or mixed
     lists that hold the leaf block at the origin; a purely coarse list differs by exactly the chain along child 0 below its smallest key."""
-    exe = build_kats(tmp_path)
+    exe = build_kats("alloc_kats", tmp_path)
     size, leaf = 512, 6
     origin = ((0, 0, 0), (8, 8, 8), 0)
     lists = {
@@ -221,17 +158,8 @@ def test_cpp_mirror_allocation_program_compiles(tmp_path):
         assert r.returncode == 0, r.stderr
 
 
-class _NoLib:
-    """Stands in for libse_hip.so: any call is a test failure (the checks must fire before the library is reached)."""
-    def __getattr__(self, name):
-        raise AssertionError(f"library called: {name}")
-
-
 def _pipeline():
-    from supereight_amd.pipeline import DenseSLAMPipeline
-    p = DenseSLAMPipeline.__new__(DenseSLAMPipeline)      # (no handle)
-    p.lib, p._h, p.field, p.size = _NoLib(), None, 0, 256
-    return p
+    return bare_pipeline(field=0, size=256)
 
 
 @pytest.mark.parametrize("boxes,exc", [

@@ -10,16 +10,9 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.host_util import bare_pipeline, build_kats
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KATS_SRC = os.path.join(ROOT, "tests", "cpp", "edit_kats.cpp")
-
-
-def build_kats(out_dir) -> str:
-    exe = os.path.join(str(out_dir), "edit_kats")
-    r = subprocess.run(["g++", "-std=c++14", "-O2", "-Wall", "-Werror", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), KATS_SRC, "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
 
 
 def test_header_declares_the_edit_entries():
@@ -58,14 +51,14 @@ def test_build_lists_the_edit_kernel_header():
 def test_reference_known_answers_on_the_host_octree(tmp_path):
     """AxisAlignedTest.Init and .BBoxTest: 512 blocks; whole-map assignment reads back everywhere; box [100, 151): 10 inside 100 .. 150
     (51^3 voxels, all allocated), untouched elsewhere in every allocated block of [50, 200)^3."""
-    exe = build_kats(tmp_path)
+    exe = build_kats("edit_kats", tmp_path)
     r = subprocess.run([exe, "kats"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
     assert r.stdout.split() == ["blocks", "512", "Init", "0", "BBoxTest", str(51 ** 3), "0"]
 
 
 def test_reference_node_positions(tmp_path):
-    exe = build_kats(tmp_path)
+    exe = build_kats("edit_kats", tmp_path)
     r = subprocess.run([exe, "positions"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr + r.stdout
     f = r.stdout.split()
@@ -73,7 +66,7 @@ def test_reference_node_positions(tmp_path):
 
 
 def test_edit_list_equals_the_literal_loop(tmp_path):
-    exe = build_kats(tmp_path)
+    exe = build_kats("edit_kats", tmp_path)
     r = subprocess.run([exe, "random", "30", "11"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr + r.stdout
     f = r.stdout.split()
@@ -89,17 +82,8 @@ def test_cpp_mirror_edit_program_compiles(tmp_path):
         assert r.returncode == 0, r.stderr
 
 
-class _NoLib:
-    """Stands in for libse_hip.so: any call is a test failure (the checks must fire before the library is reached)."""
-    def __getattr__(self, name):
-        raise AssertionError(f"library called: {name}")
-
-
-def _pipeline(field=0):
-    from supereight_amd.pipeline import DenseSLAMPipeline
-    p = DenseSLAMPipeline.__new__(DenseSLAMPipeline)      # (no handle)
-    p.lib, p._h, p.field = _NoLib(), None, field
-    return p
+def _pipeline():
+    return bare_pipeline(field=0)
 
 
 @pytest.mark.parametrize("boxes,exc", [

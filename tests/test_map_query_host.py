@@ -8,6 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.host_util import bare_pipeline
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -27,19 +29,6 @@ def test_header_declares_the_query_entries():
         assert res is C.c_int and args[2] is C.c_int64 and len(args) == 4
 
 
-class _NoLib:
-    """Stands in for libse_hip.so: any call is a test failure (the checks must fire before the library is reached)."""
-    def __getattr__(self, name):
-        raise AssertionError(f"library called: {name}")
-
-
-def _pipeline():
-    from supereight_amd.pipeline import DenseSLAMPipeline
-    p = DenseSLAMPipeline.__new__(DenseSLAMPipeline)      # (no handle)
-    p.lib, p._h = _NoLib(), None
-    return p
-
-
 @pytest.mark.parametrize("points,exc", [
     (np.zeros((4, 3), np.float64), TypeError),
     (np.zeros((4, 3), np.int32), TypeError),
@@ -51,12 +40,12 @@ def _pipeline():
 ], ids=["float64", "int32", "n_by_2", "flat", "3d", "list", "none"])
 def test_query_refuses_bad_points_before_any_library_call(points, exc):
     with pytest.raises(exc):
-        _pipeline().query(points)
+        bare_pipeline().query(points)
 
 
 def test_query_refuses_bad_torch_points_and_empty_requests():
     torch = pytest.importorskip("torch")
-    p = _pipeline()
+    p = bare_pipeline()
     with pytest.raises(ValueError):
         p.query(np.zeros((4, 3), np.float32), fine=False, coarse=False, interp=False, grad=False, status=False)
     with pytest.raises(TypeError):

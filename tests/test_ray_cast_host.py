@@ -15,6 +15,7 @@ from oracle.binding import OFUSION, SDF
 from supereight_amd.synthetic import make_stream
 from tests import ray_cast_util as U
 from tests.edge_frames import SHAPE_CASES, edge_stream
+from tests.host_util import bare_pipeline
 from tests.parity_util import OUTSIDE_VIEWS, outside_view
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -105,16 +106,8 @@ def test_header_declares_the_ray_entries():
         assert res is C.c_int and args[2] is C.c_int64 and args[3] is C.c_float and len(args) == 5
 
 
-class _NoLib:
-    def __getattr__(self, name):
-        raise AssertionError(f"library called: {name}")
-
-
 def _pipeline():
-    from supereight_amd.pipeline import DenseSLAMPipeline
-    p = DenseSLAMPipeline.__new__(DenseSLAMPipeline)
-    p.lib, p._h, p._device = _NoLib(), None, None
-    return p
+    return bare_pipeline(_device=None)
 
 
 O = np.zeros((4, 3), np.float32)
