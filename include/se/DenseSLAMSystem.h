@@ -199,6 +199,13 @@ class DenseSLAMSystem {
   bool collidesWith(const int32_t* host_boxes, size_t n, const se_hip_collide_test& test, int32_t mode, uint8_t* host_status) {
     return ok(se_hip_collide_boxes_host(h_, host_boxes, (int64_t)n, &test, mode, host_status));
   }
+  /* Not in the reference's class: collision queries for n boxes moved along straight segments (host_motions[n][9]: lo xyz, side xyz, d xyz in
+   * voxels), exact for the continuous motion -- se_hip_collide_motions_host, definitions in se_hip.h.  host_out.status is required; a null
+   * host_out.t_first means "not wanted".  stop_at is SE_HIP_COLLISION_OCCUPIED or SE_HIP_COLLISION_UNSEEN.  The answers are those of
+   * se::geometry::motion_status_and_entry (include/se/motion_collision.hpp) on the getMap() snapshot. */
+  bool collidesMoving(const int32_t* host_motions, size_t n, const se_hip_collide_test& test, int32_t stop_at, se_hip_motion_out& host_out) {
+    return ok(se_hip_collide_motions_host(h_, host_motions, (int64_t)n, &test, stop_at, &host_out));
+  }
   /* Not in the reference's class (an addition of this mirror): se::functor::axis_aligned_map(map, f, min, max) for a list of n boxes with
    * f = "assign x and / or y where the current value has one of these classes", applied to the device map in list order without save / load --
    * se_hip_edit_boxes_host, definitions in se_hip.h.  The map afterwards is what se::apply_edits (include/se/axis_aligned.hpp) makes of the

@@ -381,6 +381,43 @@ int se_hip_collide_boxes(se_hip_pipeline* p, const int32_t* device_boxes, int64_
 int se_hip_collide_boxes_host(se_hip_pipeline* p, const int32_t* host_boxes, int64_t n, const se_hip_collide_test* test, int32_t mode,
                               uint8_t* host_status);
 
+/* ---- batched collision queries for boxes moved along straight segments: "may this robot move from A to B, and if not, how far?" for N
+ *      motions at once, without getMap().  Not in the reference; built on its Octree::get and on the classification above.  The host
+ *      restatement and the literal definition are include/se/motion_collision.hpp.
+ * Motion: nine int32, lo xyz, side xyz, d xyz, in voxels (motions [n][9]).  The box [lo, lo + side) is translated by t * d for t in [0, 1].
+ * Touched: a cube with integer corner c and side s (a voxel: s = 1) is touched iff some t in [0, 1] has, on every axis k,
+ *     lo_k + t d_k < c_k + s   and   lo_k + side_k + t d_k > c_k.
+ *   The inequalities are open: a face sliding exactly along a voxel face touches nothing; for d = 0 the touched voxels are exactly those of the
+ *   half-open box of SE_HIP_COLLIDE_STRICT.  An axis with d_k = 0 gives a static condition, every other axis an open interval with rational ends
+ *   over |d_k|; with L the largest lower end and U the smallest upper end the cube is touched iff L < U, L < 1 and U > 0, and its entry
+ *   parameter is t_in = max(0, L).  Every comparison is exact (cross-multiplication in 64-bit integers): nothing depends on a step or a rounding.
+ * Classification: exactly that of se_hip_collide_boxes in strict mode -- `test` applied to Octree::get(v) (the voxel, or value_[child] of the
+ *   deepest existing node); voxels outside [0, size)^3 are unseen.
+ * A motion with side < 1 on any axis, or with any coordinate of lo, lo + side, lo + d or lo + side + d outside [-2^20, 2^20], is invalid and
+ *   reads no map memory.  (The bound keeps every numerator and denominator of the intervals below 2^24 -- exactly representable as floats --
+ *   and every cross product inside int64.)
+ * Outputs (se_hip_motion_out; a null t_first means "not wanted", status is required):
+ *   status[n]   (uint8) the min over all touched voxels of their class, SE_HIP_COLLISION_*; SE_HIP_COLLISION_INVALID for an invalid motion.
+ *   t_first[n]  (float) with stop_at in {SE_HIP_COLLISION_OCCUPIED, SE_HIP_COLLISION_UNSEEN}, a voxel blocks when its class is <= stop_at;
+ *               t_first is the smallest t_in over the touched blocking voxels, those outside the volume included, returned as
+ *               (float)num / (float)den of the exact rational (both terms are exactly representable, so the quotient depends on the value
+ *               only): 0 when the motion is blocked at its start, SE_HIP_MOTION_FREE (2.0f) when nothing blocks, -1.0f for an invalid motion.
+ * Both entries answer for the map after everything enqueued before them (a scan that ran on the side stream included), refuse n < 0, a null
+ * out, a null motions or status pointer with n > 0, a null test, a non-finite threshold, occupied_above other than 0 / 1 and a stop_at other
+ * than the two above with SE_HIP_E_INVALID (n == 0 is a no-op), report a sticky SE_HIP_E_CAPACITY like the other read-back calls, and leave the
+ * map, the images and the launch counters (SE_HIP_K_*) alone.
+ *   se_hip_collide_motions       device arrays; enqueued on the handle's stream, asynchronous like the stage calls.
+ *   se_hip_collide_motions_host  host arrays; staged through a device buffer the handle keeps (and grows); synchronises before it returns. */
+#define SE_HIP_MOTION_FREE 2.0f
+typedef struct se_hip_motion_out {
+  uint8_t* status;  /* [n] */
+  float* t_first;   /* [n] */
+} se_hip_motion_out;
+int se_hip_collide_motions(se_hip_pipeline* p, const int32_t* device_motions, int64_t n, const se_hip_collide_test* test, int32_t stop_at,
+                           const se_hip_motion_out* device_out);
+int se_hip_collide_motions_host(se_hip_pipeline* p, const int32_t* host_motions, int64_t n, const se_hip_collide_test* test, int32_t stop_at,
+                                const se_hip_motion_out* host_out);
+
 /* ---- batched ray casts against the resident map: the per-pixel body of the reference's raycastKernel (se_denseslam/src/rendering.cpp:51-90)
  *      for N rays of the caller's at once, without getMap() -- simulated range sensors, line-of-sight checks, views from poses that are not
  *      the tracked camera's.

@@ -24,6 +24,7 @@
 #include "se_mesh_kernels.h"
 #include "se_query_kernels.h"
 #include "se_collide_kernels.h"
+#include "se_motion_kernels.h"
 #include "se_edit_kernels.h"
 #include "se_alloc_kernels.h"
 #include "se_ray_kernels.h"
@@ -2198,6 +2199,46 @@ int se_hip_collide_boxes_host(se_hip_pipeline* p, const int32_t* host_boxes, int
   const BatchOuts out{1, {{host_status, 1}}};
   return batch_host(p, host_boxes, 6 * sizeof(int32_t), n, out, [&] { return collide_args(host_boxes, n, test, mode, host_status); },
                     [&](const void* boxes, void* const* o) { launch_collide(p, (const int32_t*)boxes, n, test, mode, (uint8_t*)o[0]); });
+}
+
+
+// ------------------------------------------------------------------------------------ motion collision queries
+static_assert(SE_HIP_COLLISION_OCCUPIED == SE_COLLIDE_OCC && SE_HIP_COLLISION_UNSEEN == SE_COLLIDE_UNSEEN, "stop_at of se_hip_collide_motions");
+namespace {
+int motion_args(const int32_t* motions, int64_t n, const se_hip_collide_test* test, int32_t stop_at, const se_hip_motion_out* out) {
+  if (n < 0) return fail(SE_HIP_E_INVALID, "se_hip_collide_motions: n < 0");
+  if (!out) return fail(SE_HIP_E_INVALID, "se_hip_collide_motions: null out");
+  if (n > 0 && (!motions || !out->status)) return fail(SE_HIP_E_INVALID, "se_hip_collide_motions: null motions or status");
+  if (!test) return fail(SE_HIP_E_INVALID, "se_hip_collide_motions: null test");
+  if (!std::isfinite(test->threshold)) return fail(SE_HIP_E_INVALID, "se_hip_collide_motions: non-finite threshold");
+  if (test->occupied_above != 0 && test->occupied_above != 1) return fail(SE_HIP_E_INVALID, "se_hip_collide_motions: occupied_above must be 0 or 1");
+  if (stop_at != SE_HIP_COLLISION_OCCUPIED && stop_at != SE_HIP_COLLISION_UNSEEN) return fail(SE_HIP_E_INVALID, "se_hip_collide_motions: stop_at must be occupied or unseen");
+  return SE_HIP_OK;
+}
+// t_first (4-byte items) before status (bytes): the order the staging layout asks for (static: see query_outs)
+static BatchOuts motion_outs(const se_hip_motion_out* out) {
+  if (!out) return {2, {}};
+  return {2, {{out->t_first, sizeof(float)}, {out->status, 1}}};
+}
+void launch_motions(se_hip_pipeline* p, const int32_t* motions, int64_t n, const se_hip_collide_test* test, int32_t stop_at, void* const* out) {
+  const DevMap& m = p->map;
+  const MotionArgs a{motions, (long long)n, (uint8_t*)out[1], (float*)out[0], test->threshold, test->occupied_above, (uint32_t)stop_at};
+  const int grid = (int)std::min<int64_t>(n, 1 << 20);   // one wave per motion, grid-stride beyond
+  if (m.dense) hipLaunchKernelGGL((k_collide_motions<true>), dim3(grid), dim3(SE_WG_COLLIDE), 0, p->stream, m, a);
+  else hipLaunchKernelGGL((k_collide_motions<false>), dim3(grid), dim3(SE_WG_COLLIDE), 0, p->stream, m, a);
+}
+}  // namespace
+
+int se_hip_collide_motions(se_hip_pipeline* p, const int32_t* device_motions, int64_t n, const se_hip_collide_test* test, int32_t stop_at,
+                           const se_hip_motion_out* device_out) {
+  return batch_device(p, device_motions, n, motion_outs(device_out), [&] { return motion_args(device_motions, n, test, stop_at, device_out); },
+                      [&](const void* mo, void* const* o) { launch_motions(p, (const int32_t*)mo, n, test, stop_at, o); });
+}
+
+int se_hip_collide_motions_host(se_hip_pipeline* p, const int32_t* host_motions, int64_t n, const se_hip_collide_test* test, int32_t stop_at,
+                                const se_hip_motion_out* host_out) {
+  return batch_host(p, host_motions, 9 * sizeof(int32_t), n, motion_outs(host_out), [&] { return motion_args(host_motions, n, test, stop_at, host_out); },
+                    [&](const void* mo, void* const* o) { launch_motions(p, (const int32_t*)mo, n, test, stop_at, o); });
 }
 
 

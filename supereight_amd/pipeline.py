@@ -75,6 +75,16 @@ COLLISION_OCCUPIED, COLLISION_UNSEEN, COLLISION_EMPTY, COLLISION_INVALID = 0, 1,
 _COLLIDE_MODES = {"strict": 0, "reference": 1}
 
 
+class _MotionOut(C.Structure):
+    """se_hip_motion_out of include/se_hip.h: output addresses, t_first 0 = not wanted."""
+    _fields_ = [("status", C.c_void_p), ("t_first", C.c_void_p)]
+
+
+# t_first of se_hip_collide_motions when nothing blocks the motion; what stop_at may name
+MOTION_FREE = 2.0
+_MOTION_STOPS = {"occupied": COLLISION_OCCUPIED, "unseen": COLLISION_UNSEEN}
+
+
 class _Edit(C.Structure):
     """se_hip_edit of include/se_hip.h (40 bytes)."""
     _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("x", C.c_float), ("y", C.c_float), ("flags", C.c_uint32), ("only", C.c_uint32)]
@@ -170,6 +180,8 @@ EXPORTS = {
     "se_hip_query_points_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_QueryOut)]),
     "se_hip_collide_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
     "se_hip_collide_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
+    "se_hip_collide_motions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_MotionOut)]),
+    "se_hip_collide_motions_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_MotionOut)]),
     "se_hip_edit_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
     "se_hip_edit_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
     "se_hip_allocate_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
@@ -707,6 +719,39 @@ class DenseSLAMPipeline:
             self._device_call(torch, b.device, self.lib.se_hip_collide_boxes, b.data_ptr() if n else None, n, C.byref(test), m,
                               out.data_ptr() if n else None)
         return out
+
+    _MOTION_OUTPUTS = (("status", (), np.uint8), ("t_first", (), np.float32))
+
+    def collides_moving(self, motions, threshold: float = 0.0, occupied_above=None, stop_at: str = "occupied", t_first: bool = True):
+        """Batched collision queries for boxes moved along straight segments (se_hip_collide_motions, include/se_hip.h): motions [N, 9] int32 =
+        lo xyz, side xyz, d xyz in voxels; the box [lo, lo + side) is translated by t * d, t in [0, 1].  Exact for the continuous motion: a
+        voxel counts iff the moving box touches it (open inequalities), and is classified as collides() classifies it in strict mode
+        (threshold / occupied_above as there; outside the volume is unseen).  Returns the status per motion -- the min class over the touched
+        voxels, COLLISION_INVALID for side < 1 or coordinates beyond +-2^20 -- or, with t_first, (status, t_first): the parameter at which the
+        motion first touches a voxel that blocks (stop_at "occupied": occupied voxels; "unseen": unseen ones too), 0 when it is blocked at its
+        start, MOTION_FREE (2.0) when nothing blocks, -1 for an invalid motion.
+          - numpy int32 [N, 9]: through the host entry; numpy arrays out.
+          - a torch int32 tensor on this handle's GPU (contiguous, [N, 9]): through the device entry; torch tensors on the same device out.
+            The caller's current torch stream is synchronised first, and the handle before the tensors are returned.
+        Anything else raises TypeError / ValueError before any library call."""
+        if stop_at not in _MOTION_STOPS:
+            raise ValueError(f"collides_moving: stop_at must be one of {sorted(_MOTION_STOPS)}, got {stop_at!r}")
+        if occupied_above is None:
+            occupied_above = self.field == OFUSION
+        if not isinstance(occupied_above, (bool, np.bool_)):
+            raise TypeError(f"collides_moving: occupied_above must be a bool, got {type(occupied_above).__name__}")
+        thr = float(threshold)
+        if not np.isfinite(np.float32(thr)):
+            raise ValueError(f"collides_moving: threshold must be finite as a float32, got {threshold!r}")
+        test = _CollideTest(thr, int(bool(occupied_above)))
+        torch, mo, n = self._batch_input("collides_moving", "motions", motions, np.int32, 9)
+        res, out = self._batch_outputs(torch, mo, n, self._MOTION_OUTPUTS, {"status": True, "t_first": bool(t_first)}, _MotionOut)
+        if torch is None:
+            self._check(self.lib.se_hip_collide_motions_host(self._h, mo.ctypes.data if n else None, n, C.byref(test), _MOTION_STOPS[stop_at], C.byref(out)))
+        else:
+            self._device_call(torch, mo.device, self.lib.se_hip_collide_motions, mo.data_ptr() if n else None, n, C.byref(test), _MOTION_STOPS[stop_at],
+                              C.byref(out))
+        return (res["status"], res["t_first"]) if t_first else res["status"]
 
     @staticmethod
     def _edit_only(only) -> int:
