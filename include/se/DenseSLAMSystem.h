@@ -206,6 +206,13 @@ class DenseSLAMSystem {
   bool collidesMoving(const int32_t* host_motions, size_t n, const se_hip_collide_test& test, int32_t stop_at, se_hip_motion_out& host_out) {
     return ok(se_hip_collide_motions_host(h_, host_motions, (int64_t)n, &test, stop_at, &host_out));
   }
+  /* Not in the reference's class: clearance queries for n boxes (host_queries[n][7]: lo xyz, side xyz, r_max in voxels) -- the squared
+   * distance to the nearest blocking voxel within r_max and that voxel -- se_hip_clearance_boxes_host, definitions in se_hip.h.  host_out.d2 is
+   * required; a null host_out.nearest means "not wanted".  stop_at is SE_HIP_COLLISION_OCCUPIED or SE_HIP_COLLISION_UNSEEN.  The answers are
+   * those of se::geometry::clearance (include/se/clearance.hpp) on the getMap() snapshot. */
+  bool clearanceOf(const int32_t* host_queries, size_t n, const se_hip_collide_test& test, int32_t stop_at, se_hip_clearance_out& host_out) {
+    return ok(se_hip_clearance_boxes_host(h_, host_queries, (int64_t)n, &test, stop_at, &host_out));
+  }
   /* Not in the reference's class (an addition of this mirror): se::functor::axis_aligned_map(map, f, min, max) for a list of n boxes with
    * f = "assign x and / or y where the current value has one of these classes", applied to the device map in list order without save / load --
    * se_hip_edit_boxes_host, definitions in se_hip.h.  The map afterwards is what se::apply_edits (include/se/axis_aligned.hpp) makes of the

@@ -418,6 +418,43 @@ int se_hip_collide_motions(se_hip_pipeline* p, const int32_t* device_motions, in
 int se_hip_collide_motions_host(se_hip_pipeline* p, const int32_t* host_motions, int64_t n, const se_hip_collide_test* test, int32_t stop_at,
                                 const se_hip_motion_out* host_out);
 
+/* ---- batched clearance queries: "how far is this box from the nearest obstacle, and where is that obstacle?" for N boxes at once, without
+ *      getMap().  Not in the reference; built on its Octree::get and on the classification above.  The host restatement and the literal
+ *      definition are include/se/clearance.hpp.
+ * Query: seven int32, lo xyz, side xyz, r_max, in voxels (queries [n][7]).  The box is [lo, lo + side) per axis.
+ * Distance: for a cube with integer corner c and side s (a voxel: s = 1) the gap on axis k is
+ *     g_k = max(0, c_k - (lo_k + side_k), lo_k - (c_k + s))   and   d2 = g_x^2 + g_y^2 + g_z^2,
+ *   the squared Euclidean distance between the two closed sets: 0 when they overlap or touch.  Everything is integer arithmetic; nothing
+ *   depends on a rounding.
+ * Classification: exactly that of se_hip_collide_boxes in strict mode -- `test` applied to Octree::get(v) (the voxel, or value_[child] of the
+ *   deepest existing node; a pending entry counts as absent); every voxel of Z^3 outside [0, size)^3 is unseen.  With stop_at in
+ *   {SE_HIP_COLLISION_OCCUPIED, SE_HIP_COLLISION_UNSEEN}, a voxel blocks when its class is <= stop_at, as in se_hip_collide_motions.
+ * A query with side < 1 on any axis, with r_max outside [0, 32767], or with any coordinate of lo or lo + side outside [-2^19, 2^19], is
+ *   invalid and reads no map memory.  (The bounds keep d2 below 2^30 and every witness coordinate below 2^20 in magnitude: the pair
+ *   (d2, z, y, x) packs into 32 + 63 bits.)
+ * Outputs (se_hip_clearance_out; a null nearest means "not wanted", d2 is required):
+ *   d2[n]          (int32) the smallest d2 over all blocking voxels with d2 <= r_max^2, those outside the volume included;
+ *                  SE_HIP_CLEARANCE_NONE if there is none, SE_HIP_CLEARANCE_INVALID for an invalid query.
+ *   nearest[n][3]  (int32, x y z) among the blocking voxels that attain that d2 (a finite set), the smallest in (z, y, x) lexicographic
+ *                  order; (INT32_MIN, INT32_MIN, INT32_MIN) for NONE and for INVALID.
+ *   The definition is per voxel: it does not depend on how the tree happens to be subdivided.
+ * Both entries answer for the map after everything enqueued before them (a scan that ran on the side stream included), refuse n < 0, a null
+ * out, a null queries or d2 pointer with n > 0, a null test, a non-finite threshold, occupied_above other than 0 / 1 and a stop_at other
+ * than the two above with SE_HIP_E_INVALID (n == 0 is a no-op), report a sticky SE_HIP_E_CAPACITY like the other read-back calls, and leave the
+ * map, the images and the launch counters (SE_HIP_K_*) alone.
+ *   se_hip_clearance_boxes       device arrays; enqueued on the handle's stream, asynchronous like the stage calls.
+ *   se_hip_clearance_boxes_host  host arrays; staged through a device buffer the handle keeps (and grows); synchronises before it returns. */
+#define SE_HIP_CLEARANCE_NONE (-1)
+#define SE_HIP_CLEARANCE_INVALID (-2)
+typedef struct se_hip_clearance_out {
+  int32_t* d2;       /* [n]    */
+  int32_t* nearest;  /* [n][3] */
+} se_hip_clearance_out;
+int se_hip_clearance_boxes(se_hip_pipeline* p, const int32_t* device_queries, int64_t n, const se_hip_collide_test* test, int32_t stop_at,
+                           const se_hip_clearance_out* device_out);
+int se_hip_clearance_boxes_host(se_hip_pipeline* p, const int32_t* host_queries, int64_t n, const se_hip_collide_test* test, int32_t stop_at,
+                                const se_hip_clearance_out* host_out);
+
 /* ---- batched ray casts against the resident map: the per-pixel body of the reference's raycastKernel (se_denseslam/src/rendering.cpp:51-90)
  *      for N rays of the caller's at once, without getMap() -- simulated range sensors, line-of-sight checks, views from poses that are not
  *      the tracked camera's.

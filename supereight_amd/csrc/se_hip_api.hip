@@ -25,6 +25,7 @@
 #include "se_query_kernels.h"
 #include "se_collide_kernels.h"
 #include "se_motion_kernels.h"
+#include "se_clearance_kernels.h"
 #include "se_edit_kernels.h"
 #include "se_alloc_kernels.h"
 #include "se_ray_kernels.h"
@@ -2239,6 +2240,46 @@ int se_hip_collide_motions_host(se_hip_pipeline* p, const int32_t* host_motions,
                                 const se_hip_motion_out* host_out) {
   return batch_host(p, host_motions, 9 * sizeof(int32_t), n, motion_outs(host_out), [&] { return motion_args(host_motions, n, test, stop_at, host_out); },
                     [&](const void* mo, void* const* o) { launch_motions(p, (const int32_t*)mo, n, test, stop_at, o); });
+}
+
+
+// ------------------------------------------------------------------------------------ clearance queries
+static_assert(SE_HIP_CLEARANCE_NONE == SE_CLEAR_NONE && SE_HIP_CLEARANCE_INVALID == SE_CLEAR_INVALID, "d2 codes of se_hip_clearance_boxes");
+namespace {
+int clearance_args(const int32_t* queries, int64_t n, const se_hip_collide_test* test, int32_t stop_at, const se_hip_clearance_out* out) {
+  if (n < 0) return fail(SE_HIP_E_INVALID, "se_hip_clearance_boxes: n < 0");
+  if (!out) return fail(SE_HIP_E_INVALID, "se_hip_clearance_boxes: null out");
+  if (n > 0 && (!queries || !out->d2)) return fail(SE_HIP_E_INVALID, "se_hip_clearance_boxes: null queries or d2");
+  if (!test) return fail(SE_HIP_E_INVALID, "se_hip_clearance_boxes: null test");
+  if (!std::isfinite(test->threshold)) return fail(SE_HIP_E_INVALID, "se_hip_clearance_boxes: non-finite threshold");
+  if (test->occupied_above != 0 && test->occupied_above != 1) return fail(SE_HIP_E_INVALID, "se_hip_clearance_boxes: occupied_above must be 0 or 1");
+  if (stop_at != SE_HIP_COLLISION_OCCUPIED && stop_at != SE_HIP_COLLISION_UNSEEN) return fail(SE_HIP_E_INVALID, "se_hip_clearance_boxes: stop_at must be occupied or unseen");
+  return SE_HIP_OK;
+}
+// (static: see query_outs)
+static BatchOuts clearance_outs(const se_hip_clearance_out* out) {
+  if (!out) return {2, {}};
+  return {2, {{out->d2, sizeof(int32_t)}, {out->nearest, 3 * sizeof(int32_t)}}};
+}
+void launch_clearance(se_hip_pipeline* p, const int32_t* queries, int64_t n, const se_hip_collide_test* test, int32_t stop_at, void* const* out) {
+  const DevMap& m = p->map;
+  const ClearanceArgs a{queries, (long long)n, (int32_t*)out[0], (int32_t*)out[1], test->threshold, test->occupied_above, (uint32_t)stop_at};
+  const int grid = (int)std::min<int64_t>(n, 1 << 20);   // one wave per query, grid-stride beyond
+  if (m.dense) hipLaunchKernelGGL((k_clearance_boxes<true>), dim3(grid), dim3(SE_WG_COLLIDE), 0, p->stream, m, a);
+  else hipLaunchKernelGGL((k_clearance_boxes<false>), dim3(grid), dim3(SE_WG_COLLIDE), 0, p->stream, m, a);
+}
+}  // namespace
+
+int se_hip_clearance_boxes(se_hip_pipeline* p, const int32_t* device_queries, int64_t n, const se_hip_collide_test* test, int32_t stop_at,
+                           const se_hip_clearance_out* device_out) {
+  return batch_device(p, device_queries, n, clearance_outs(device_out), [&] { return clearance_args(device_queries, n, test, stop_at, device_out); },
+                      [&](const void* q, void* const* o) { launch_clearance(p, (const int32_t*)q, n, test, stop_at, o); });
+}
+
+int se_hip_clearance_boxes_host(se_hip_pipeline* p, const int32_t* host_queries, int64_t n, const se_hip_collide_test* test, int32_t stop_at,
+                                const se_hip_clearance_out* host_out) {
+  return batch_host(p, host_queries, 7 * sizeof(int32_t), n, clearance_outs(host_out), [&] { return clearance_args(host_queries, n, test, stop_at, host_out); },
+                    [&](const void* q, void* const* o) { launch_clearance(p, (const int32_t*)q, n, test, stop_at, o); });
 }
 
 

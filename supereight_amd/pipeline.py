@@ -85,6 +85,16 @@ MOTION_FREE = 2.0
 _MOTION_STOPS = {"occupied": COLLISION_OCCUPIED, "unseen": COLLISION_UNSEEN}
 
 
+class _ClearanceOut(C.Structure):
+    """se_hip_clearance_out of include/se_hip.h: output addresses, nearest 0 = not wanted."""
+    _fields_ = [("d2", C.c_void_p), ("nearest", C.c_void_p)]
+
+
+# d2 of se_hip_clearance_boxes when nothing blocks within r_max, and for an invalid query
+CLEARANCE_NONE, CLEARANCE_INVALID = -1, -2
+_CLEARANCE_R_CLAMP = 32768   # an r_max above 32767 is invalid: larger ones are passed as this one, so that they fit the int32 column
+
+
 class _Edit(C.Structure):
     """se_hip_edit of include/se_hip.h (40 bytes)."""
     _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("x", C.c_float), ("y", C.c_float), ("flags", C.c_uint32), ("only", C.c_uint32)]
@@ -182,6 +192,8 @@ EXPORTS = {
     "se_hip_collide_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
     "se_hip_collide_motions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_MotionOut)]),
     "se_hip_collide_motions_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_MotionOut)]),
+    "se_hip_clearance_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_ClearanceOut)]),
+    "se_hip_clearance_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_ClearanceOut)]),
     "se_hip_edit_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
     "se_hip_edit_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
     "se_hip_allocate_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
@@ -752,6 +764,59 @@ class DenseSLAMPipeline:
             self._device_call(torch, mo.device, self.lib.se_hip_collide_motions, mo.data_ptr() if n else None, n, C.byref(test), _MOTION_STOPS[stop_at],
                               C.byref(out))
         return (res["status"], res["t_first"]) if t_first else res["status"]
+
+    _CLEARANCE_OUTPUTS = (("d2", (), np.int32), ("nearest", (3,), np.int32))
+
+    def clearance(self, boxes, r_max, threshold: float = 0.0, occupied_above=None, stop_at: str = "occupied", nearest: bool = True):
+        """Batched clearance queries (se_hip_clearance_boxes, include/se_hip.h): boxes [N, 6] int32 = lo xyz, side xyz in voxels; r_max the
+        search radius in voxels, an integer or one per box ([N], any integer dtype; with device boxes a torch tensor or a scalar).  For each
+        box the squared Euclidean distance d2 (int32, voxels^2; 0 when they touch) to the nearest voxel that blocks -- classified as
+        collides() classifies it in strict mode (threshold / occupied_above as there; outside the volume is unseen); stop_at "occupied":
+        occupied voxels block; "unseen": unseen ones too -- among those with d2 <= r_max^2: CLEARANCE_NONE (-1) if there is none,
+        CLEARANCE_INVALID (-2) for side < 1, r_max outside 0 .. 32767 or coordinates beyond +-2^19.  With nearest, (d2, nearest): that voxel
+        [N, 3] int32 x y z, among equally near ones the smallest in (z, y, x) order; INT32_MIN where d2 is negative.
+          - numpy int32 [N, 6]: through the host entry; numpy arrays out.
+          - a torch int32 tensor on this handle's GPU (contiguous, [N, 6]): through the device entry; torch tensors on the same device out.
+            The caller's current torch stream is synchronised first, and the handle before the tensors are returned.
+        Anything else raises TypeError / ValueError before any library call."""
+        if stop_at not in _MOTION_STOPS:
+            raise ValueError(f"clearance: stop_at must be one of {sorted(_MOTION_STOPS)}, got {stop_at!r}")
+        if occupied_above is None:
+            occupied_above = self.field == OFUSION
+        if not isinstance(occupied_above, (bool, np.bool_)):
+            raise TypeError(f"clearance: occupied_above must be a bool, got {type(occupied_above).__name__}")
+        thr = float(threshold)
+        if not np.isfinite(np.float32(thr)):
+            raise ValueError(f"clearance: threshold must be finite as a float32, got {threshold!r}")
+        test = _CollideTest(thr, int(bool(occupied_above)))
+        torch, b, n = self._batch_input("clearance", "boxes", boxes, np.int32, 6)
+        i32 = np.iinfo(np.int32)
+        if torch is not None and _torch_module(r_max) is not None:
+            if r_max.dtype not in (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64):
+                raise TypeError(f"clearance: r_max must be an integer or an integer array, got {r_max.dtype}")
+            if tuple(r_max.shape) not in ((), (n,)):
+                raise ValueError(f"clearance: r_max must be a scalar or have shape [{n}], got {list(r_max.shape)}")
+            # (out of int32 range: invalid whatever it is, kept invalid by the clamp)
+            r = r_max.to(device=b.device).clamp(-1, _CLEARANCE_R_CLAMP).to(torch.int32).expand(n)
+            q = torch.cat([b, r.reshape(n, 1)], 1).contiguous()
+        else:
+            r = np.asarray(r_max)
+            if isinstance(r_max, (bool, np.bool_)) or r.dtype.kind not in "iu":
+                raise TypeError(f"clearance: r_max must be an integer or an integer array, got {r.dtype}")
+            if r.shape not in ((), (n,)):
+                raise ValueError(f"clearance: r_max must be a scalar or have shape [{n}], got {list(r.shape)}")
+            r = np.broadcast_to(np.clip(r.astype(np.int64), -1, _CLEARANCE_R_CLAMP).astype(np.int32), (n,))
+            if torch is None:
+                q = np.ascontiguousarray(np.concatenate([b, r.reshape(n, 1)], 1))
+            else:
+                q = torch.cat([b, torch.from_numpy(r.copy()).to(b.device).reshape(n, 1)], 1).contiguous()
+        res, out = self._batch_outputs(torch, q, n, self._CLEARANCE_OUTPUTS, {"d2": True, "nearest": bool(nearest)}, _ClearanceOut)
+        if torch is None:
+            self._check(self.lib.se_hip_clearance_boxes_host(self._h, q.ctypes.data if n else None, n, C.byref(test), _MOTION_STOPS[stop_at], C.byref(out)))
+        else:
+            self._device_call(torch, q.device, self.lib.se_hip_clearance_boxes, q.data_ptr() if n else None, n, C.byref(test), _MOTION_STOPS[stop_at],
+                              C.byref(out))
+        return (res["d2"], res["nearest"]) if nearest else res["d2"]
 
     @staticmethod
     def _edit_only(only) -> int:
