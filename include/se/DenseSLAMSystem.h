@@ -228,6 +228,23 @@ class DenseSLAMSystem {
   bool allocateRegion(const se_hip_alloc_box* host_boxes, size_t n, int64_t* counts = nullptr, uint64_t* new_keys = nullptr, int64_t capacity_words = 0) {
     return ok(se_hip_allocate_boxes_host(h_, host_boxes, (int64_t)n, counts, new_keys, capacity_words));
   }
+  /* Not in the reference's class (an addition of this mirror): a rolling volume -- the map content translated by shift_voxels (multiples of 8,
+   * the block side) on the device without save / load: content at voxel c is at c + s afterwards, what leaves the cube is forgotten, the vacated
+   * side is unseen -- se_hip_shift_map, definitions in se_hip.h.  The map afterwards is what se::shift_map (include/se/shift_map.hpp) makes of the
+   * getMap() snapshot taken before.  counts[4] (optional): blocks kept, blocks dropped, nodes kept, nodes dropped.  The camera moves with the
+   * content: on success float(s[k]) * (volume_dimension / volume_resolution) is added to the translation of pose_ and to init_pose_, so
+   * getPosition() is continuous across a shift up to the rounding of that addition (three float roundings) and setPose() keeps taking poses relative to the start.  raycast_pose_ and the vertex / normal
+   * images stay in the old frame of reference: tracking() fails until raycasting() has run. */
+  bool shiftMap(const Eigen::Vector3i& shift_voxels, int64_t* counts = nullptr) {
+    const int32_t s[3] = {shift_voxels.x(), shift_voxels.y(), shift_voxels.z()};
+    if (!ok(se_hip_shift_map(h_, s, counts))) return false;
+    for (int k = 0; k < 3; ++k) {
+      const float d = float(s[k]) * (volume_dimension_(k) / volume_resolution_(k));
+      pose_(k, 3) += d;
+      init_pose_(k) += d;
+    }
+    return true;
+  }
   /* Not in the reference's class (an addition of this mirror): the per-pixel body of raycastKernel for n rays of the caller's
    * (host_rays[n][8]: origin xyz, direction xyz, near, far in metres) answered on the device map without getMap() --
    * se_hip_cast_rays_host, definitions in se_hip.h.  host_out.hit[n][4], .normal[n][3], .status[n]; a null pointer: not wanted. */

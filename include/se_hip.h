@@ -513,6 +513,36 @@ int se_hip_save_map(se_hip_pipeline* p, const char* filename);
  * this one reads the float and restores all 512.  Blocks come back active, as Octree::insert leaves them. */
 int se_hip_load_map(se_hip_pipeline* p, const char* filename);
 
+/* ---- rolling volume: the map content translated by a whole number of blocks, on the device (no reference counterpart: the reference's volume is
+ *      a fixed cube and nothing in it is ever freed).  The executable definition is se::shift_map of include/se/shift_map.hpp on the getMap()
+ *      snapshot.  s = shift_voxels: content at voxel c before the call is at c + s after it; what leaves the cube is forgotten, the vacated side
+ *      is unseen.  A robot that walks towards +x passes a negative s[0].
+ *        arguments  every component a multiple of 8 (the block side) within [-2^30, 2^30], else SE_HIP_E_INVALID and the map is untouched
+ *                   (as with every other entry, a raycast that was held back has been launched by then: the images may have advanced);
+ *                   s = 0 is valid and changes nothing
+ *        blocks     the block with corner c survives iff c + s lies in [0, size - 8] on every axis; it keeps its 512 x and y values bit for bit
+ *                   and its active flag
+ *        nodes      the node with side d and corner c survives iff every component of s is a multiple of d and c + s lies in [0, size - d]; it
+ *                   keeps value_[8].  A node the shift is not aligned to is dropped (its children would no longer be its children).  The root
+ *                   always exists afterwards and keeps its values only for s = 0
+ *        closure    every missing ancestor of a survivor is created with initValue(), as Octree::allocate creates it (without the keys[0] rule of
+ *                   unique_multiscale); nothing else exists afterwards; surviving childless nodes stay
+ *        counts     (optional, host, int64[4]) blocks kept, blocks dropped, nodes kept, nodes dropped (the root counts as kept only for s = 0);
+ *                   the nodes created follow from se_hip_counts
+ *        pools      dense grid: every vacated brick and every dropped block's brick reads initValue() again.  Pooled: the pools are compact
+ *                   afterwards (used slots = survivors), every free slot holds initValue()
+ *      Everything derived from the block set -- index, occupancy and beam-start bitmaps, lists, counters -- is rebuilt for the new set; the
+ *      count words of the new-key lists and the statistics counters of se_hip_get_stats are zeroed, as se_hip_load_map zeroes them.  A deferred
+ *      raycast is launched first (it belongs to the old frame of reference), a scan on the side stream is joined, and the call returns when the
+ *      map is shifted (it synchronises the handle, as se_hip_load_map does).  The work is per block, not per cell of the volume; the survivors
+ *      pass through a staging buffer of 4 KiB per block, which is released again when it is larger than 64 MiB.
+ *      vertex_ / normal_ are not touched: they stay in the frame of reference before the shift, and after a nonzero shift se_hip_track and
+ *      se_hip_frame_tracked return SE_HIP_E_INVALID ("vertex / normal images predate a map shift") until a raycast has run; se_hip_render_volume
+ *      casts its own rays until then.  Poses are the caller's: after the call it passes poses translated by s * dim / size.
+ *      A node pool that runs out while the ancestors are rebuilt raises the usual sticky SE_HIP_E_CAPACITY.  Replicas (row-sharded,
+ *      sharded sweep) each hold the whole map: the same call goes to every one of them. */
+int se_hip_shift_map(se_hip_pipeline* p, const int32_t shift_voxels[3], int64_t* host_counts);
+
 /* ---- map export, second half: marching cubes over the allocated blocks
  * DenseSLAMSystem::dump_mesh (DenseSLAMSystem.cpp:302-322) = se::algorithms::marching_cube
  * (se_core/include/se/algorithms/meshing.hpp:161-208) with inside(v) = v.x < 0, select(v) = v.x, then writeVtkMesh

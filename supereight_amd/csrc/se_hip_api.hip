@@ -29,6 +29,7 @@
 #include "se_edit_kernels.h"
 #include "se_alloc_kernels.h"
 #include "se_ray_kernels.h"
+#include "se_shift_kernels.h"
 
 int flush_pending_raycast(se_hip_pipeline* p);   // (defined next to se_hip_frame)
 
@@ -137,6 +138,7 @@ struct se_hip_pipeline {
   bool ptrs_exposed = false;   // sticky: se_hip_vertex_normal_device handed out vertex_ / normal_ of a handle without an image ring
   float pend_pose[16] = {0}, pend_k[4] = {0}, pend_mu = 0.f;
   uint32_t pend_frame = 0;
+  bool images_shifted = false; // se_hip_shift_map moved the map under vertex_ / normal_ (they stay in the frame of reference before the shift): no tracking until the next raycast
   bool images_complete = true; // vertex_ / normal_ hold every row of the last raycast (a row-sharded replica: only after se_hip_apply_image_tiles / se_hip_gather_images)
   bool scan_pending = false;   // a scan was enqueued on `side` and not yet joined by `stream`
   bool scan_on_side = false;   // stream the LAST allocation scan ran on: se_hip_alloc_exchange / se_hip_alloc_commit follow it
@@ -222,6 +224,7 @@ struct se_hip_pipeline {
   int64_t launches[SE_HIP_K_COUNT] = {0};
   int row_begin = 0, row_end = 0;
   int integ_grid = 0;  // > 0: fixed number of workgroups for the integration sweep (tuning knob)
+  size_t shift_keep_bytes = (size_t)64 << 20;   // se_hip_shift_map releases a staging buffer larger than this when it returns; SE_HIP_SHIFT_KEEP_MIB (A/B knob)
   bool ieee_sweep = false;   // SE_HIP_IEEE_SWEEP=1: never select the shared-reciprocal sweep (k_integrate<.., FAST = false, ..>)
   unsigned short* tile_cost = nullptr;   // raycast scheduling hint: per wave tile, cost in the previous launch (see RayArgs)
   int* prio_thr = nullptr;               // its three priority thresholds (device; written by the integration sweep)
@@ -591,17 +594,17 @@ bool stage_runs_integration(uint32_t frame, uint32_t rate) { return ((frame % ra
 
 // Octree::init (se_core/include/se/octree.hpp:425-437) on the device: empty index, root node, every brick and node value
 // at initValue().  Enqueued on the main stream.
-void reset_map_state(se_hip_pipeline* p) {
+// The index structures of an empty map (everything but the brick and node value pools); nb / nn: the list entries that may hold something.
+void clear_map_index(se_hip_pipeline* p, size_t nb, size_t nn) {
   DevMap& m = p->map;
   hipMemsetAsync(m.tab, 0, p->tab_entries * sizeof(uint32_t), p->stream);
   hipMemsetAsync(m.occ, 0, p->occ_words * sizeof(uint32_t), p->stream);
   hipMemsetAsync(m.lbits, 0, p->lbits_words * sizeof(uint32_t), p->stream);
   hipMemsetAsync(m.cbits, 0, 2 * p->cbits_words * sizeof(uint32_t), p->stream);   // (dilated bits + the cells' own "has a block" bits)
   if (m.fbits) hipMemsetAsync(m.fbits, 0, p->fbits_words * sizeof(uint32_t), p->stream);
-  hipMemsetAsync(m.bpos, 0, p->cap_blocks * sizeof(uint32_t), p->stream);
-  hipMemsetAsync(m.bactive, 0, p->slots, p->stream);
-  hipMemsetAsync(m.npos, 0, p->cap_nodes * sizeof(uint32_t), p->stream);
-  hipMemsetAsync(m.nlevel, 0, p->cap_nodes, p->stream);
+  hipMemsetAsync(m.bpos, 0, nb * sizeof(uint32_t), p->stream);
+  hipMemsetAsync(m.npos, 0, nn * sizeof(uint32_t), p->stream);
+  hipMemsetAsync(m.nlevel, 0, nn, p->stream);
   hipMemsetAsync(m.stats, 0, S_COUNT * sizeof(unsigned long long), p->stream);
   hipMemsetAsync(m.newkeys, 0, sizeof(unsigned long long), p->stream);
   if (p->newkeys_own) hipMemsetAsync(p->newkeys_own, 0, sizeof(unsigned long long), p->stream);
@@ -613,6 +616,11 @@ void reset_map_state(se_hip_pipeline* p) {
   std::memset(p->ctr_host, 0, C_COUNT * sizeof(uint32_t));
   p->ctr_host[C_NODES] = 1u;
   p->sorted_n = 0; p->sweeps_since_sort = 0;
+}
+void reset_map_state(se_hip_pipeline* p) {
+  DevMap& m = p->map;
+  clear_map_index(p, p->cap_blocks, p->cap_nodes);
+  hipMemsetAsync(m.bactive, 0, p->slots, p->stream);
   hipLaunchKernelGGL(k_fill_bricks, dim3(16384), dim3(256), 0, p->stream, m.vx, m.init_x, m.init_y, p->slots * 1024);
   hipLaunchKernelGGL(k_fill, dim3(256), dim3(256), 0, p->stream, m.nx, m.init_x, p->cap_nodes * 8);
   hipLaunchKernelGGL(k_fill, dim3(256), dim3(256), 0, p->stream, m.ny, m.init_y, p->cap_nodes * 8);
@@ -654,6 +662,7 @@ int se_hip_create(const se_hip_config* cfg, se_hip_pipeline** out) {
   if (const char* ev = std::getenv("SE_HIP_INTEG_GRID")) p->integ_grid = std::atoi(ev);            // tuning knob
   if (const char* ev = std::getenv("SE_HIP_BEAM")) p->beam = std::max(0, std::min(2, std::atoi(ev)));   // A/B + test knob
   if (const char* ev = std::getenv("SE_HIP_OF_LEAP")) p->of_leap = std::atoi(ev) != 0;
+  if (const char* ev = std::getenv("SE_HIP_SHIFT_KEEP_MIB")) p->shift_keep_bytes = (size_t)std::max(0, std::atoi(ev)) << 20;   // A/B knob
   if (const char* ev = std::getenv("SE_HIP_IEEE_SWEEP")) p->ieee_sweep = std::atoi(ev) != 0;       // A/B + test knob: the sweep instantiation with the compiler's divisions
   if (const char* ev = std::getenv("SE_HIP_PRIO")) p->prio_hint = std::atoi(ev) != 0;              // tuning knob
   if (const char* ev = std::getenv("SE_HIP_PRIO_SHARE")) {                                         // tuning knob
@@ -976,7 +985,7 @@ int launch_raycast_scan(se_hip_pipeline* p, const DevMap& ms, const AllocArgs& s
   p->has_pending = false;
   p->flush_streak = 0;
   std::memcpy(p->raycast_pose, p->pend_pose, sizeof p->raycast_pose);   // raycast_pose_ = pose_ (DenseSLAMSystem.cpp:196)
-  p->images_complete = !p->sharded;
+  p->images_complete = !p->sharded; p->images_shifted = false;
   select_image_target(p, p->pend_frame);
   p->n_launch[SE_HIP_K_ALLOC_SCAN]++; p->n_launch[SE_HIP_K_COUNT]++;   // (the raycast half is counted by the timer scope below)
   RayLaunchArgs L = make_ray_args(p, p->pend_pose, p->pend_k, p->pend_mu);
@@ -1490,6 +1499,7 @@ int se_hip_raycast(se_hip_pipeline* p, const float pose_cm[16], const float k[4]
   if (int r = join_scan(p)) return r;
   std::memcpy(p->raycast_pose, pose_cm, sizeof p->raycast_pose);   // raycast_pose_ = pose_ (DenseSLAMSystem.cpp:196)
   p->images_complete = !p->sharded;   // a row-sharded replica has just overwritten its own rows only
+  p->images_shifted = false;
   select_image_target(p, frame);
   const DevMap& m = p->map;
   RayLaunchArgs L = make_ray_args(p, pose_cm, k, mu);
@@ -1592,6 +1602,7 @@ int se_hip_track(se_hip_pipeline* p, const float k[4], float icp_threshold, uint
   // the ICP reads the WHOLE of vertex_ / normal_; a row-sharded replica holds only its own rows of the last raycast until
   // the peers' tiles have been applied -- tracking against the stale rows of an earlier frame would be silent garbage
   if (p->sharded && !p->images_complete) return fail(SE_HIP_E_INVALID, "row-sharded handle: se_hip_gather_images / se_hip_apply_image_tiles must follow the raycast before se_hip_track");
+  if (p->images_shifted) return fail(SE_HIP_E_INVALID, "vertex / normal images predate a map shift");
   if (int r = join_scan(p)) return r;
   const int W = p->cfg.width, H = p->cfg.height;
   if ((W >> (n_levels - 1)) < 1 || (H >> (n_levels - 1)) < 1) return fail(SE_HIP_E_INVALID, "too many pyramid levels");
@@ -1798,7 +1809,7 @@ int se_hip_render_volume(se_hip_pipeline* p, uint8_t* host_rgbw, const float vie
   // !viewPose_->isApprox(raycast_pose_): Eigen's fuzzy compare, ||a-b||^2 <= 1e-10 * min(||a||^2, ||b||^2)
   float d2 = 0, na = 0, nb = 0;
   for (int i = 0; i < 16; ++i) { const float d = view_cm[i] - p->raycast_pose[i]; d2 += d * d; na += view_cm[i] * view_cm[i]; nb += p->raycast_pose[i] * p->raycast_pose[i]; }
-  sh.render = !(d2 <= 1e-5f * 1e-5f * std::min(na, nb)) ? 1 : 0;
+  sh.render = (p->images_shifted || !(d2 <= 1e-5f * 1e-5f * std::min(na, nb))) ? 1 : 0;   // (images from before a map shift are not this map's)
   const int tiles = ((L.a.W + 7) / 8) * ((L.a.H + 7) / 8);
   const dim3 grid((tiles + SE_WG_RAY / 64 - 1) / (SE_WG_RAY / 64)), block(SE_WG_RAY);
   const bool sdf = p->cfg.field_type == SE_HIP_FIELD_SDF;
@@ -1926,6 +1937,7 @@ int se_hip_memory_info(se_hip_pipeline* p, int64_t out[4]) {
   size_t all = bricks + p->tab_entries * 4 + (p->occ_words + p->lbits_words + 2 * p->cbits_words + p->fbits_words) * 4 + p->cap_blocks * 4 + ((p->slots + 3) & ~(size_t)3) +
                p->cap_nodes * (2 * 8 * 4 + 4 + 1) + 2 * (m.cap_keys + 1) * 8 + se_hip_pipeline::kIn * px * 4 + 2 * px * 3 * 4;
   all += p->sort_cap * sizeof(uint32_t) + p->sort_tmp_bytes;   // (sort_block_list: allocated at the first sort)
+  all += p->staging_cap;                                       // (the _host entries and se_hip_shift_map: grown on demand)
   out[0] = m.dense ? 1 : 0; out[1] = (int64_t)p->slots; out[2] = (int64_t)bricks; out[3] = (int64_t)all;
   return SE_HIP_OK;
 }
@@ -2610,6 +2622,61 @@ int se_hip_load_map(se_hip_pipeline* p, const char* filename) {
   if (int r = se_hip_counts(p, &gb, &gn)) return r;
   if ((uint64_t)gb != nb || (uint64_t)gn != nn) return fail(SE_HIP_E_INVALID, "map file is not ancestor-closed (octants without parents) or holds duplicates");
   return SE_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------ map shift
+// The steps of se_shift_kernels.h on the main stream, between two synchronisations: the map is quiescent when the first kernel starts (scan joined,
+// deferred raycast launched by check(), both streams idle) and complete when the call returns.
+int se_hip_shift_map(se_hip_pipeline* p, const int32_t shift_voxels[3], int64_t* host_counts) {
+  if (int r = check(p)) return r;
+  if (!shift_voxels) return fail(SE_HIP_E_INVALID, "se_hip_shift_map: null shift");
+  for (int k = 0; k < 3; ++k) {
+    if (shift_voxels[k] < -SE_SHIFT_LIMIT || shift_voxels[k] > SE_SHIFT_LIMIT) return fail(SE_HIP_E_INVALID, "se_hip_shift_map: a component outside [-2^30, 2^30]");
+    if (shift_voxels[k] & 7) return fail(SE_HIP_E_INVALID, "se_hip_shift_map: a component is not a multiple of 8 (the block side)");
+  }
+  if (int r = fetch_counters(p)) return r;   // (joins a scan on the side stream, synchronises the main stream, reports a sticky overflow)
+  if (p->side) HIP_TRY(hipStreamSynchronize(p->side));
+  p->gate_armed = false;
+  const DevMap& m = p->map;
+  const size_t nb = std::min<size_t>(p->ctr_host[C_BLOCKS], p->cap_blocks), nn = std::min<size_t>(p->ctr_host[C_NODES], p->cap_nodes);
+  if (shift_voxels[0] == 0 && shift_voxels[1] == 0 && shift_voxels[2] == 0) {
+    if (host_counts) { host_counts[0] = (int64_t)nb; host_counts[1] = 0; host_counts[2] = (int64_t)nn; host_counts[3] = 0; }
+    return SE_HIP_OK;
+  }
+  // staging: [bricks 4 KiB each][node values 64 B each][block keys][node keys][destinations][active flags]
+  const size_t bytes[6] = {nb * 4096, nn * 16 * sizeof(float), (nb + 1) * 8, (nn + 1) * 8, nb * sizeof(uint32_t), nb};
+  size_t off[6];
+  if (int r = reserve_staging(p, staging_layout(bytes, 6, off))) return r;
+  unsigned char* b = p->staging;
+  ShiftArgs a{};
+  for (int k = 0; k < 3; ++k) a.s[k] = shift_voxels[k];
+  a.nb = (uint32_t)nb; a.nn = (uint32_t)nn;
+  a.bricks = (uint4*)(b + off[0]); a.nval = (float*)(b + off[1]);
+  a.blist = (unsigned long long*)(b + off[2]); a.nlist = (unsigned long long*)(b + off[3]);
+  a.dst = (uint32_t*)(b + off[4]); a.bact = b + off[5];
+  HIP_TRY(hipMemsetAsync(a.blist, 0, sizeof(unsigned long long), p->stream));
+  HIP_TRY(hipMemsetAsync(a.nlist, 0, sizeof(unsigned long long), p->stream));
+  const int waves_grid = grid_for(nb * 64, SE_WG, 8192);
+  hipLaunchKernelGGL(k_shift_select, dim3(grid_for(std::max(nb, nn), SE_WG, 2048)), dim3(SE_WG), 0, p->stream, m, a);
+  if (nb) hipLaunchKernelGGL(k_shift_gather, dim3(waves_grid), dim3(SE_WG), 0, p->stream, m, a);
+  p->scan_pending = false; p->occ_commit_due = false; p->occ_lists = OccLists{nullptr, 0, 0};
+  clear_map_index(p, nb, nn);
+  hipLaunchKernelGGL(k_alloc_commit, dim3(256, 1), dim3(SE_WG), 0, p->stream, m, a.nlist, 1, (long long)(nn + 1));
+  hipLaunchKernelGGL(k_alloc_commit, dim3(256, 1), dim3(SE_WG), 0, p->stream, m, a.blist, 1, (long long)(nb + 1));
+  hipLaunchKernelGGL(k_shift_scatter, dim3(waves_grid), dim3(SE_WG), 0, p->stream, m, a);
+  HIP_TRY(hipGetLastError());
+  unsigned long long kept[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(&kept[0], a.blist, sizeof(unsigned long long), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipMemcpyAsync(&kept[1], a.nlist, sizeof(unsigned long long), hipMemcpyDeviceToHost, p->stream));
+  p->images_shifted = true;
+  const int rc = fetch_counters(p);   // (synchronises; a node pool that ran out while the ancestors were rebuilt: SE_HIP_E_CAPACITY, sticky)
+  // 4 KiB per block is not held on to: the next shift is seconds away (the small buffers of the batched queries stay)
+  if (p->staging_cap > p->shift_keep_bytes) { hipFree(p->staging); p->staging = nullptr; p->staging_cap = 0; }
+  if (host_counts) {
+    host_counts[0] = (int64_t)kept[0]; host_counts[1] = (int64_t)(nb - kept[0]);
+    host_counts[2] = (int64_t)kept[1]; host_counts[3] = (int64_t)(nn - kept[1]);   // (the root gave up its values: dropped)
+  }
+  return rc;
 }
 
 // DenseSLAMSystem::dump_volume (DenseSLAMSystem.h:219) has an empty body in the reference (DenseSLAMSystem.cpp:270-272); the

@@ -14,6 +14,7 @@ MAX_VIEWS = 64   # SE_HIP_MESH_MAX_VIEWS
 class LiveMesh:
     def __init__(self):
         self.blocks = {}   # (x, y, z) voxel coordinates of the block corner -> [n, 3, 3] float32
+        self.size = self.voxel = None   # the volume's side in voxels and the voxel's in metres, learnt from the source of the first update
 
     def update(self, source, views=None, region=None) -> int:
         """Brings the blocks up to date that `views` (the views integrated since the last update: (pose, k) or (pose, k, width, height)) may
@@ -24,6 +25,8 @@ class LiveMesh:
         views = None if views is None else list(views)
         if views is not None and (len(views) == 0 or len(views) > MAX_VIEWS):
             views = None
+        if getattr(source, "size", None):
+            self.size, self.voxel = int(source.size), np.float32(source.dim) / np.float32(source.size)
         res = source.mesh_blocks(region=region, views=views, skip_empty=False)
         coords, ranges, tris = (np.asarray(res[k]) for k in ("coords", "ranges", "triangles"))
         for c, (first, count) in zip(coords.tolist(), ranges.tolist()):
@@ -32,6 +35,29 @@ class LiveMesh:
             else:
                 self.blocks.pop(tuple(c), None)
         return len(coords)
+
+    def shift(self, shift_voxels) -> int:
+        """Follows DenseSLAMPipeline.shift(shift_voxels) (three integers, multiples of 8): every entry moves by s, its triangles by s * voxel
+        metres (a float32 addition: within an ulp of what meshing the shifted map gives), and what left the cube is dropped -- the map is
+        not meshed again.  What still has to be are the blocks that now lie on a face the content moved towards: on an upper face a block
+        lost the neighbour its last cells read, on a lower face the mesher rejects triangles with a vertex at coordinate 0.  So for every
+        axis k follow with update(source, region=(lo, hi)) over the slab [size - 9, size) of that axis if s[k] > 0, [0, 8) if s[k] < 0.
+        Returns the number of entries dropped."""
+        from .pipeline import DenseSLAMPipeline
+        s = DenseSLAMPipeline._shift_argument(shift_voxels).astype(np.int64)
+        if not self.blocks or not s.any():
+            return 0
+        if self.size is None:
+            raise ValueError("LiveMesh.shift: the volume is not known yet (no update from a pipeline so far)")
+        move = s.astype(np.float32) * self.voxel
+        kept = {}
+        for c, tris in self.blocks.items():
+            q = np.asarray(c, np.int64) + s
+            if (q >= 0).all() and (q <= self.size - 8).all():
+                kept[tuple(int(v) for v in q)] = tris + move
+        dropped = len(self.blocks) - len(kept)
+        self.blocks = kept
+        return dropped
 
     def triangles(self) -> np.ndarray:
         """All triangles, [n, 3, 3] float32 metres, blocks in coordinate order."""

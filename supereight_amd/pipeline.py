@@ -175,6 +175,7 @@ EXPORTS = {
     "se_hip_render_track": (C.c_int, [C.c_void_p, C.c_void_p]),
     "se_hip_save_map": (C.c_int, [C.c_void_p, C.c_char_p]),
     "se_hip_load_map": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "se_hip_shift_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "se_hip_create_replicas": (C.c_int, [C.POINTER(_Config), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]),
     "se_hip_mesh_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "se_hip_mesh_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
@@ -1146,6 +1147,36 @@ class DenseSLAMPipeline:
     def load(self, filename: str):
         """Octree::load counterpart (octree.hpp:917-950, minus its two defects): the map becomes what the file holds."""
         self._check(self.lib.se_hip_load_map(self._h, filename.encode()))
+
+    @staticmethod
+    def _shift_argument(shift_voxels) -> np.ndarray:
+        """The shift as int32 [3], checked (TypeError / ValueError) before any library call: three integers, multiples of 8, within +-2^30."""
+        s = np.asarray(shift_voxels)
+        if s.dtype.kind not in "iu":
+            raise TypeError(f"shift: shift_voxels must be integers (voxels), got {s.dtype}")
+        if s.shape != (3,):
+            raise ValueError(f"shift: shift_voxels must have shape (3,), got {list(s.shape)}")
+        s = s.astype(np.int64)
+        if (s % 8 != 0).any():
+            raise ValueError(f"shift: every component must be a multiple of 8 (the block side), got {s.tolist()}")
+        if (np.abs(s) > 1 << 30).any():
+            raise ValueError(f"shift: every component must lie in [-2^30, 2^30], got {s.tolist()}")
+        return s.astype(np.int32)
+
+    def shift(self, shift_voxels) -> np.ndarray:
+        """Rolling volume (se_hip_shift_map, include/se_hip.h): the map content is translated by shift_voxels (three integers, multiples of
+        8) on the device -- content at voxel c is at c + s afterwards, what leaves the cube is forgotten, the vacated side is unseen;
+        surviving blocks keep their values and active flags, nodes the shift is aligned to keep theirs.  pose_ is translated with the map
+        (s * dim / size added to its translation), so the camera stays where it was relative to the content; a robot that walks towards +x
+        passes a negative s[0].  The vertex / normal images stay in the old frame of reference: tracking() raises until a raycast has run.
+        Returns int64 [4]: blocks kept, blocks dropped, nodes kept, nodes dropped.  Wrong types and shapes raise before any library call."""
+        s = self._shift_argument(shift_voxels)
+        out = np.zeros(4, np.int64)
+        self._check(self.lib.se_hip_shift_map(self._h, s.ctypes.data, out.ctypes.data))
+        pose = self.pose_.copy()
+        pose[:3, 3] += s.astype(np.float32) * (np.float32(self.dim) / np.float32(self.size))
+        self.pose_ = pose
+        return out
 
     # ------------------------------------------------------------------ measurement
     def enable_timing(self, on: bool = True):
