@@ -93,6 +93,8 @@ def _declare(lib):
         "so_pipe_counts": (None, [vp, C.POINTER(i32), C.POINTER(i32)]),
         "so_pipe_get_blocks": (None, [vp, c_i32p, c_f32p, c_f32p, c_u8p]),
         "so_pipe_get_nodes": (None, [vp, c_u64p, c_u32p, c_f32p, c_f32p]),
+        "so_pipe_set_blocks": (i32, [vp, c_i32p, c_f32p, c_f32p, i32]),
+        "so_pipe_set_nodes": (i32, [vp, c_u64p, c_f32p, c_f32p, i32]),
         "so_pipe_stats": (None, [vp, c_u64p]),
         "so_pipe_timings": (None, [vp, c_f64p]),
         "so_bilateral_filter": (None, [c_f32p, c_f32p, i32, i32]),
@@ -238,6 +240,25 @@ class OraclePipeline:
         y = np.zeros((nn, 8), np.float32)
         self.lib.so_pipe_get_nodes(self.h, code, side, x.reshape(-1), y.reshape(-1))
         return code, side, x, y
+
+    def set_values(self, blocks=None, nodes=None):
+        """The inverse of blocks() / nodes(): blocks = (coords[n,3], x[n,512], y[n,512], ...), nodes = (code[n], side or None, x[n,8], y[n,8]);
+        what follows y in `blocks` (the active flags of blocks()) is ignored.  Overwrites the values of the blocks and nodes that exist and
+        nothing else; returns (blocks found, nodes found)."""
+        fb = fn = 0
+        if blocks is not None:
+            c = np.ascontiguousarray(blocks[0], np.int32).reshape(-1, 3)
+            x = np.ascontiguousarray(blocks[1], np.float32).reshape(-1)
+            y = np.ascontiguousarray(blocks[2], np.float32).reshape(-1)
+            assert x.size == 512 * len(c) and y.size == 512 * len(c)
+            fb = self.lib.so_pipe_set_blocks(self.h, c.reshape(-1), x, y, len(c)) if len(c) else 0
+        if nodes is not None:
+            code = np.ascontiguousarray(nodes[0], np.uint64).reshape(-1)
+            x = np.ascontiguousarray(nodes[-2], np.float32).reshape(-1)
+            y = np.ascontiguousarray(nodes[-1], np.float32).reshape(-1)
+            assert x.size == 8 * len(code) and y.size == 8 * len(code)
+            fn = self.lib.so_pipe_set_nodes(self.h, code, x, y, len(code)) if len(code) else 0
+        return fb, fn
 
     def stats(self) -> dict:
         out = np.zeros(11, np.uint64)

@@ -13,146 +13,11 @@ from supereight_amd.pipeline import (COLLISION_EMPTY, EDIT_BLOCKS, EDIT_DTYPE, E
                                      DenseSLAMPipeline, _CollideTest)
 from supereight_amd.synthetic import make_stream
 from tests.gpu_state_util import H, W, bits, map_state, run_stream, streamed_with
-from tests.host_util import build_kats, unpack
+from tests.host_util import build_kats
 
 pytestmark = pytest.mark.gpu
-INIT = {SDF: (1.0, 0.0), OFUSION: (0.0, 0.0)}    # voxel_traits<T>::initValue()
-LIMIT = 1 << 30
-OFF = np.stack([np.arange(512) & 7, (np.arange(512) >> 3) & 7, np.arange(512) >> 6], 1).astype(np.int64)   # voxel index -> (x, y, z)
-# REFERENCE mode: the running sum of dir(i) * h over i, in units of h
-CUM = np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0], [2, 2, 0], [2, 2, 1], [3, 2, 2], [3, 3, 3], [4, 4, 4]], np.int64)
-DIR = np.stack([np.arange(8) & 1, (np.arange(8) >> 1) & 1, np.arange(8) >> 2], 1).astype(np.int64)
+from tests.edit_util import CUM, DIR, INIT, LIMIT, OFF, _classes, _valid, make_edits, truth   # noqa: F401
 
-
-# ------------------------------------------------------------------ the truth, in numpy, from the definitions of include/se_hip.h
-def _valid(e, field, test):
-    for v in list(e["lo"]) + list(e["hi"]):
-        if not -LIMIT <= int(v) <= LIMIT:
-            return False
-    fl, only = int(e["flags"]), int(e["only"])
-    if fl & ~15 or not 1 <= only <= 7:
-        return False
-    if only != 7 and (test is None or not np.isfinite(np.float32(test[0]))):
-        return False
-    if fl & EDIT_SET_X and not np.isfinite(e["x"]):
-        return False
-    if fl & EDIT_SET_Y:
-        if not np.isfinite(e["y"]):
-            return False
-        if field == SDF and not (0 <= e["y"] <= 255 and float(e["y"]) == int(e["y"])):
-            return False
-    return True
-
-
-def _classes(x, y, field, test):
-    """class code per value: 0 occupied, 1 unseen, 2 empty"""
-    thr, above = np.float32(test[0]), test[1]
-    unseen = (x == np.float32(INIT[field][0])) & (y == np.float32(INIT[field][1]))
-    occ = (x > thr) if above else (x < thr)
-    return np.where(unseen, 1, np.where(occ, 0, 2))
-
-
-def truth(field, coords, X, Y, code, side, NX, NY, rec, test, mode):
-    """Applies the records one after another to copies of the downloads.  Returns X, Y, NX, NY, counts[4] and a dict of what happened on the
-    way (for the conditions that keep the test from passing vacuously)."""
-    X, Y, NX, NY = X.copy(), Y.copy(), NX.copy(), NY.copy()
-    counts = np.zeros(4, np.int64)
-    touched = np.zeros(len(coords), bool)
-    writes = np.zeros(X.shape, np.int32)
-    suppressed = 0
-    c64 = coords.astype(np.int64)
-    corner = unpack(code & ~np.uint64(0xFFF))
-    ref0 = unpack(code)                      # the level bits still in the code
-    h = (side.astype(np.int64) // 2)[:, None, None]
-    strict_lo = corner[:, None, :] + DIR[None] * h           # [nn, 8, 3]
-    ref_pos = ref0[:, None, :] + CUM[None] * h
-    for e in rec:
-        if not _valid(e, field, test):
-            counts[3] += 1
-            continue
-        lo, hi = e["lo"].astype(np.int64), e["hi"].astype(np.int64)
-        fl, only = int(e["flags"]), int(e["only"])
-        if fl & EDIT_BLOCKS:
-            rows = np.nonzero(((c64 < hi) & (c64 + 8 > lo)).all(1))[0]
-            if len(rows):
-                P = c64[rows][:, None, :] + OFF[None]
-                m = ((P >= lo) & (P < hi)).all(2)
-                if only != 7:
-                    ok = ((only >> _classes(X[rows], Y[rows], field, test)) & 1) != 0
-                    suppressed += int((m & ~ok).sum())
-                    m &= ok
-                counts[0] += int(m.sum())
-                touched[rows] |= m.any(1)
-                if fl & (EDIT_SET_X | EDIT_SET_Y):
-                    w = writes[rows]; w[m] += 1; writes[rows] = w
-                if fl & EDIT_SET_X:
-                    x = X[rows]; x[m] = e["x"]; X[rows] = x
-                if fl & EDIT_SET_Y:
-                    y = Y[rows]; y[m] = e["y"]; Y[rows] = y
-        if fl & EDIT_NODES:
-            if mode == "reference":
-                m = ((ref_pos >= lo) & (ref_pos <= hi)).all(2)
-            else:
-                m = ((strict_lo >= lo) & (strict_lo + h <= hi)).all(2)
-            if only != 7:
-                ok = ((only >> _classes(NX, NY, field, test)) & 1) != 0
-                suppressed += int((m & ~ok).sum())
-                m &= ok
-            counts[1] += int(m.sum())
-            if fl & EDIT_SET_X:
-                NX[m] = e["x"]
-            if fl & EDIT_SET_Y:
-                NY[m] = e["y"]
-    counts[2] = int(touched.sum())
-    return X, Y, NX, NY, counts, {"rewritten": int((writes >= 2).sum()), "suppressed": suppressed}
-
-
-def make_edits(rng, field, n, dim, coords, hits):
-    """More than 200 records and the number of invalid ones among them."""
-    sdf = field == SDF
-    xs = np.float32([-0.75, -0.25, 0.0, 0.5, 1.0] if sdf else [-5.0, -1.5, 0.0, 0.75, 4.0])
-    rows = []
-
-    def add(lo, hi, flags=None, only=None, x=None, y=None):
-        r = np.zeros((), EDIT_DTYPE)
-        r["lo"], r["hi"] = lo, hi
-        r["x"] = xs[rng.integers(len(xs))] if x is None else x
-        r["y"] = (rng.integers(0, 101) if sdf else rng.integers(0, 9) * 0.5) if y is None else y
-        r["flags"] = len(rows) % 16 if flags is None else flags            # every flag combination, over and over
-        r["only"] = (7 if rng.integers(3) else 1 + len(rows) % 7) if only is None else only   # every class set
-        rows.append(r)
-
-    # "mark free what is unseen", the whole volume: something is applied and something is suppressed, whatever the seed
-    add([0, 0, 0], [n, n, n], flags=15, only=2, x=xs[1], y=3)
-    for _ in range(110):                                                    # anisotropic, some partly or wholly outside
-        lo = rng.integers(-48, n + 8, 3); add(lo, lo + rng.integers(1, 65, 3))
-    hv = (hits[rng.choice(len(hits), 40)] * (n / dim)).astype(np.int64)     # centred on raycast hits
-    for c in hv:
-        s = rng.integers(1, 41, 3); add(c - s // 2, c - s // 2 + s)
-    for c in coords[rng.choice(len(coords), 12)].astype(np.int64):          # overlapping pairs with different values, on allocated blocks
-        lo = c + rng.integers(-6, 4, 3); s = rng.integers(6, 20, 3)
-        add(lo, lo + s, flags=15, only=7, x=xs[0], y=1)
-        add(lo + 2, lo + s + 3, flags=15, only=7, x=xs[3], y=2)
-    for i in range(8):                                                      # a node's whole octant, so that strict mode writes node values
-        s = 16 << (i % 3); lo = (coords[rng.integers(len(coords))].astype(np.int64) // s) * s
-        add(lo, lo + s, flags=EDIT_NODES | EDIT_SET_X | (EDIT_SET_Y if i & 1 else 0), only=7)
-    add([-n, -n, -n], [2 * n, 2 * n, 2 * n], flags=EDIT_NODES | EDIT_SET_Y, only=7, y=4)
-    add([10, 10, 10], [10, 40, 40]); add([50, 60, 70], [40, 90, 90]); add([0, 0, 0], [-5, -5, -5]); add([n, n, n], [0, 0, 0])   # empty, inverted
-    n_valid = len(rows)
-    nan, inf = np.float32("nan"), np.float32("inf")
-    add([0, 0, LIMIT + 1], [8, 8, 8]); add([-LIMIT - 1, 0, 0], [8, 8, 8]); add([0, 0, 0], [8, 2 ** 31 - 1, 8])     # coordinates
-    add([0, 0, 0], [n, n, n], flags=16 | 15); add([0, 0, 0], [n, n, n], flags=0x80000004)                                # flag bits
-    add([0, 0, 0], [n, n, n], only=0); add([0, 0, 0], [n, n, n], only=8)                                                 # classes
-    add([0, 0, 0], [n, n, n], flags=15, x=nan); add([0, 0, 0], [n, n, n], flags=13, x=inf)                               # non-finite x with SET_X
-    add([0, 0, 0], [n, n, n], flags=14, y=nan); add([0, 0, 0], [n, n, n], flags=15, y=-inf)                              # non-finite y with SET_Y
-    n_invalid = len(rows) - n_valid
-    for yv in (100.5, 256.0, -1.0):                                         # SDF: the weight is a byte
-        add([0, 0, 0], [n, n, n], flags=15, only=7, y=yv)
-        n_invalid += 1 if sdf else 0
-    add([0, 0, 0], [8, 8, 8], flags=EDIT_BLOCKS | EDIT_SET_X, x=xs[2], y=nan)          # valid: y is not assigned
-    rec = np.stack(rows)
-    order = np.concatenate([[0], 1 + rng.permutation(len(rec) - 1)])       # the whole-volume edit first, the rest shuffled (pairs may swap: still a pair)
-    return np.ascontiguousarray(rec[order]), n_invalid
 
 
 def _check_list(p, field, n, dim, rng, mode, device):
