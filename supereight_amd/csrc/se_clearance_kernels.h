@@ -13,10 +13,8 @@
 // key.  The best starts at (r_max^2, no key), which also keeps everything beyond r_max out.  Gaps are clamped to 32768 (anything beyond
 // r_max is beyond) and squared in uint32: three such squares stay below 2^32.
 //
-// One wave64 per query (grid-stride over int64 n), wave-uniform control flow; the frontier scheme is that of k_collide_boxes
-// (se_collide_kernels.h): a frontier of present octants per level in LDS, a step pops up to 8 nodes of the deepest non-empty level and
-// tests their 64 children, one per lane, and compacts the present kept ones into the next level with ballot + mbcnt.  The deepest non-empty
-// level is always taken, so the next level is empty when it is filled: 64 entries per level suffice, whatever the test.
+// One wave64 per query (grid-stride over int64 n), wave-uniform control flow, on the frontier descent of se_frontier.h; the frontier holds
+// the present octants whose pair is below the best.
 //   - an absent kept child whose classify(value_[child]) blocks is a candidate as a whole cube, with the cube's pair: exact, because every
 //     voxel of the octant reads that value;
 //   - at a block the lanes are its 8 x 8 columns: a lane forms the x / y part of its column's distance once and then tests its 8 z voxels
@@ -25,8 +23,8 @@
 //     reads and what is written;
 //   - the voxels outside the volume (they block only with stop_at unseen) are six half-spaces with a closed form each, folded in before the
 //     descent.
-// Every loop is bounded by the structure: a step pops at least one frontier entry and pushes only children of what it popped (the pyramid is
-// finite), and a leaf step visits at most 64 blocks.
+// Every loop is bounded by the structure: the descent by the argument in se_frontier.h, whatever the test, and a leaf step visits at most
+// 64 blocks.
 #pragma once
 #include "se_collide_kernels.h"
 
@@ -50,17 +48,19 @@ __device__ __forceinline__ unsigned long long se_clear_key(int x, int y, int z) 
 // (d, k) < (bd, bk), lexicographically
 __device__ __forceinline__ bool se_clear_less(uint32_t d, unsigned long long k, uint32_t bd, unsigned long long bk) { return d < bd || (d == bd && k < bk); }
 
-// the wave's smallest pair, the same in every lane
-__device__ __forceinline__ void se_clear_wave_min(uint32_t& d, unsigned long long& k) {
+// If some lane improved its best (bd, bk): the wave's smallest pair into every lane's best and into the uniform (gd, gk).
+__device__ __forceinline__ void se_clear_settle(uint32_t& bd, unsigned long long& bk, bool& improved, uint32_t& gd, unsigned long long& gk) {
+  if (__ballot(improved) == 0ull) return;
 #pragma unroll
   for (int off = 32; off; off >>= 1) {
-    const uint32_t od = (uint32_t)__shfl_xor((int)d, off);
-    const uint32_t ol = (uint32_t)__shfl_xor((int)(uint32_t)k, off), oh = (uint32_t)__shfl_xor((int)(uint32_t)(k >> 32), off);
+    const uint32_t od = (uint32_t)__shfl_xor((int)bd, off);
+    const uint32_t ol = (uint32_t)__shfl_xor((int)(uint32_t)bk, off), oh = (uint32_t)__shfl_xor((int)(uint32_t)(bk >> 32), off);
     const unsigned long long ok = ((unsigned long long)oh << 32) | ol;
-    if (se_clear_less(od, ok, d, k)) { d = od; k = ok; }
+    if (se_clear_less(od, ok, bd, bk)) { bd = od; bk = ok; }
   }
-  d = (uint32_t)__builtin_amdgcn_readfirstlane((int)d);
-  k = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(k >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)k);
+  gd = bd = (uint32_t)__builtin_amdgcn_readfirstlane((int)bd);
+  gk = bk = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(bk >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bk);
+  improved = false;
 }
 
 // The voxels of the block at slot `slot` (corner bc) whose pair is below the lane's best (bd, bk) and which block: folded into that best.
@@ -85,7 +85,7 @@ __device__ __forceinline__ void se_clear_block(const DevMap& m, const FieldConst
   for (int k = 0; k < 8; ++k) {
     vx[k] = fc.init_x; vy[k] = fc.init_y;
     if (t[k]) {
-      const size_t vi = (size_t)slot * SE_BRICK_STRIDE + (size_t)((lane & 7) + ((lane >> 3) << 3) + (k << 6));
+      const size_t vi = se_brick_voxel(slot, k);
       vx[k] = m.vx[vi]; vy[k] = se_ld_y(m, vi);
     }
   }
@@ -98,18 +98,12 @@ __device__ __forceinline__ void se_clear_block(const DevMap& m, const FieldConst
   }
 }
 
-// One instantiation per brick layout: the dense grid addresses a block's brick by its grid position, the pooled one by its index entry.
 template <bool DENSE>
 __global__ __launch_bounds__(SE_WG_COLLIDE) void k_clearance_boxes(DevMap m, ClearanceArgs a) {
-  __shared__ uint32_t s_pos[SE_MAX_LEVELS][64];   // frontier per level: packed octant position (x | y << 10 | z << 20)
-  __shared__ uint32_t s_nid[SE_MAX_LEVELS][64];   // ... and its node id
-  __shared__ uint32_t s_off[SE_MAX_LEVELS];       // m.off[] (a by-value DevMap array indexed by a runtime level would go to scratch)
-  __shared__ int s_cnt[SE_MAX_LEVELS];
+  __shared__ SeFrontier f;
   const FieldConst fc = se_field_const(m);
   const int lane = (int)(threadIdx.x & 63u);
-#pragma unroll
-  for (int l = 0; l < SE_MAX_LEVELS; ++l)
-    if (lane == l) s_off[l] = m.off[l];
+  se_frontier_init(f, m);
   const int leaf = m.leaf_level;
   const float thr = a.thr;
   const int above = a.above;
@@ -153,62 +147,29 @@ __global__ __launch_bounds__(SE_WG_COLLIDE) void k_clearance_boxes(DevMap m, Cle
     uint32_t bd = gd;             // this lane's best; equal to the wave's after each step
     unsigned long long bk = gk;
     bool improved = false;
-    __syncthreads();
-    if (lane == 0) {
-      s_pos[0][0] = 0u; s_nid[0][0] = 0u;
-#pragma unroll
-      for (int l = 0; l < SE_MAX_LEVELS; ++l) s_cnt[l] = l == 0 ? 1 : 0;
-    }
-    __syncthreads();
-    int l = 0;
-    while (run) {
-      const int cnt = s_cnt[l];
-      if (cnt == 0) {
-        if (l == 0) break;
-        --l;
-        continue;
-      }
-      const int take = min(cnt, 8);
-      const int j = lane >> 3, c = lane & 7;
-      const bool lv = j < take;
-      const uint32_t pp = lv ? s_pos[l][cnt - 1 - j] : 0u;
-      const uint32_t nid = lv ? s_nid[l][cnt - 1 - j] : 0u;
-      __syncthreads();
-      if (lane == 0) s_cnt[l] = cnt - take;
-      const int L = l + 1;
-      const int s = m.size >> L;   // child side in voxels
-      const int cx = (int)((pp & 1023u) << 1) | (c & 1), cy = (int)(((pp >> 10) & 1023u) << 1) | ((c >> 1) & 1), cz = (int)((pp >> 20) << 1) | (c >> 2);
+    int l;
+    SeFrontierStep t;
+    se_frontier_root(f, l);
+    while (run && se_frontier_pop(f, m, l, t)) {
+      const int s = t.s, cx = t.cx, cy = t.cy, cz = t.cz;
       // the child octant's pair: its distance and the key of its lowest nearest voxel
       const uint32_t g0 = se_clear_gap(lo[0], hi[0], cx * s, s), g1 = se_clear_gap(lo[1], hi[1], cy * s, s), g2 = se_clear_gap(lo[2], hi[2], cz * s, s);
       const uint32_t cd = g0 * g0 + g1 * g1 + g2 * g2;
       const unsigned long long ck = se_clear_key(se_clear_low(lo[0], hi[0], cx * s, s), se_clear_low(lo[1], hi[1], cy * s, s), se_clear_low(lo[2], hi[2], cz * s, s));
-      const bool keep = lv && se_clear_less(cd, ck, gd, gk);
-      const uint32_t e = keep ? m.tab[s_off[L] + (((((uint32_t)cz << L) | (uint32_t)cy) << L) | (uint32_t)cx)] : 0u;
+      const bool keep = t.live && se_clear_less(cd, ck, gd, gk);
+      const uint32_t e = se_frontier_entry(f, m, t, keep);
       const bool present = keep && e != 0u && e != SE_PENDING;
       // absent kept children: the whole octant has the class of value_[child]
       if (keep && !present) {
-        const uint32_t cls = se_collide_class(m.nx[(size_t)nid * 8 + c], m.ny[(size_t)nid * 8 + c], fc, thr, above);
+        const uint32_t cls = se_collide_class(m.nx[(size_t)t.nid * 8 + t.c], m.ny[(size_t)t.nid * 8 + t.c], fc, thr, above);
         if (cls <= stop_at && se_clear_less(cd, ck, bd, bk)) { bd = cd; bk = ck; improved = true; }
       }
       const bool hit = keep && present;
-      if (L < leaf) {
-        const unsigned long long b = __ballot(hit);
-        const int tot = __popcll(b);
-        if (hit) {
-          const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-          s_pos[L][tot - 1 - (int)rank] = pack_pos(cx, cy, cz);
-          s_nid[L][tot - 1 - (int)rank] = e - 1u;
-        }
-        __syncthreads();
-        if (lane == 0 && tot) s_cnt[L] = tot;
-        __syncthreads();
-        if (tot) l = L;
+      if (t.L < leaf) {
+        se_frontier_push(f, t, hit, e, l);
       } else {
-        __syncthreads();
-        if (__ballot(improved) != 0ull) {   // absent siblings of this step may already beat some of its blocks
-          se_clear_wave_min(bd, bk);
-          gd = bd; gk = bk; improved = false;
-        }
+        __syncthreads();   // the leaf step's barrier (se_frontier.h)
+        se_clear_settle(bd, bk, improved, gd, gk);   // absent siblings of this step may already beat some of its blocks
         unsigned long long b = __ballot(hit);
         while (b) {
           const int w = (int)__builtin_ctzll(b);
@@ -217,20 +178,13 @@ __global__ __launch_bounds__(SE_WG_COLLIDE) void k_clearance_boxes(DevMap m, Cle
           const uint32_t wd = (uint32_t)__builtin_amdgcn_readlane((int)cd, w);
           const unsigned long long wk = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(ck >> 32), w) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)ck, w);
           if (!se_clear_less(wd, wk, gd, gk)) continue;
-          const int qx = __builtin_amdgcn_readlane(cx, w), qy = __builtin_amdgcn_readlane(cy, w), qz = __builtin_amdgcn_readlane(cz, w);
-          const uint32_t qe = (uint32_t)__builtin_amdgcn_readlane((int)e, w);
-          const uint32_t slot = DENSE ? block_linear(m, qx, qy, qz) : qe - 1u;
+          int qx, qy, qz;
+          const uint32_t slot = se_frontier_block<DENSE>(m, t, e, w, qx, qy, qz);
           se_clear_block(m, fc, thr, above, stop_at, slot, qx * 8, qy * 8, qz * 8, lo, hi, bd, bk, improved);
-          if (__ballot(improved) != 0ull) {
-            se_clear_wave_min(bd, bk);
-            gd = bd; gk = bk; improved = false;
-          }
+          se_clear_settle(bd, bk, improved, gd, gk);
         }
       }
-      if (__ballot(improved) != 0ull) {
-        se_clear_wave_min(bd, bk);
-        gd = bd; gk = bk; improved = false;
-      }
+      se_clear_settle(bd, bk, improved, gd, gk);
     }
     if (lane == 0) {
       const bool found = valid && gk != SE_CLEAR_NO_KEY;

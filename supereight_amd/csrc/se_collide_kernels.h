@@ -2,21 +2,17 @@
 // units, what the reference's se::geometry::collides_with (se_core/include/se/geometry/octree_collision.hpp:74-167) answers -- exactly
 // (SE_HIP_COLLIDE_REFERENCE), or as the min over the box's voxels of classify(Octree::get(v)) (SE_HIP_COLLIDE_STRICT).
 //
-// One wave64 per box (grid-stride over int64 n), wave-uniform control flow.  The wave descends the index pyramid tab[] from the root and
-// never enters an absent octant (SE_PENDING counts as absent, as in k_query_points; occ[] is not read, so its lazy commit does not matter):
-//   - a frontier of present overlapping octants per level lives in LDS.  A step pops up to 8 nodes of the deepest non-empty level and
-//     tests their 64 children, one per lane; the present overlapping ones are compacted into the next level with ballot + mbcnt.  Because
-//     the deepest non-empty level is always taken, the next level is empty when it is filled: 64 entries per level suffice.
-//   - each level is kept in descending Morton order and popped from its end, so the pending octants of a deeper level always precede (in
-//     Morton order) those of a shallower one: leaf steps find present overlapping blocks in ascending Morton order.
+// One wave64 per box (grid-stride over int64 n), wave-uniform control flow, on the frontier descent of se_frontier.h; the frontier holds
+// the present overlapping octants.  Its loops are bounded by the structure, as argued there.
 //   - at the leaf level the 64 lanes cover the 8 x 8 columns of one block, each lane the box's z range of its column (loads unrolled).
 // STRICT folds classify(value_[child]) of every overlapping absent child and the voxels of every overlapping present block, plus unseen for a
 // box that leaves the volume; it stops at the first occupied step.
-// REFERENCE evaluates the closed form of the reference's DFS: the first leaf step with a hit yields L* (its lowest lane),
-// the events ev(Q) = classify(Q.value_[0]) of expanded nodes count when Q's octant ends at or before code(L*), and the search stops there.
+// REFERENCE evaluates the closed form of the reference's DFS: leaf steps meet the hit blocks in ascending Morton order, so
+// the first leaf step with a hit yields L* (its lowest lane), the events ev(Q) = classify(Q.value_[0]) of expanded nodes count when Q's
+// octant ends at or before code(L*), and the search stops there.
 // Per step, the events of one class come from nodes of one level in ascending lane order, so the lowest lane carries the smallest end.
 #pragma once
-#include "se_kernels.h"
+#include "se_frontier.h"
 
 #define SE_WG_COLLIDE 64                // one wave per workgroup
 #define SE_COLLIDE_LIMIT (1 << 30)      // lo and lo + side within [-2^30, 2^30], else the box is invalid
@@ -50,7 +46,7 @@ __device__ __forceinline__ uint32_t se_collide_block(const DevMap& m, const Fiel
   for (int k = 0; k < 8; ++k) {
     const int z = bcz + k;
     if (col && z >= r0z && z < r1z) {
-      const size_t vi = (size_t)slot * SE_BRICK_STRIDE + (size_t)((lane & 7) + ((lane >> 3) << 3) + (k << 6));
+      const size_t vi = se_brick_voxel(slot, k);
       c = min(c, se_collide_class(m.vx[vi], se_ld_y(m, vi), fc, thr, above));
     }
   }
@@ -64,18 +60,12 @@ __device__ __forceinline__ bool se_collide_ref_overlap(long long amid, long long
   return (d < 0 ? -d : d) <= (ae + s) / 2;
 }
 
-// One instantiation per brick layout: the dense grid addresses a block's brick by its grid position, the pooled one by its index entry.
 template <bool DENSE>
 __global__ __launch_bounds__(SE_WG_COLLIDE) void k_collide_boxes(DevMap m, CollideArgs a) {
-  __shared__ uint32_t s_pos[SE_MAX_LEVELS][64];   // frontier per level: packed octant position (x | y << 10 | z << 20), descending Morton order
-  __shared__ uint32_t s_nid[SE_MAX_LEVELS][64];   // ... and its node id
-  __shared__ uint32_t s_off[SE_MAX_LEVELS];       // m.off[] (a by-value DevMap array indexed by a runtime level would go to scratch)
-  __shared__ int s_cnt[SE_MAX_LEVELS];
+  __shared__ SeFrontier f;
   const FieldConst fc = se_field_const(m);
   const int lane = (int)(threadIdx.x & 63u);
-#pragma unroll
-  for (int l = 0; l < SE_MAX_LEVELS; ++l)
-    if (lane == l) s_off[l] = m.off[l];
+  se_frontier_init(f, m);
   const int leaf = m.leaf_level;
   const float thr = a.thr;
   const int above = a.above;
@@ -109,53 +99,34 @@ __global__ __launch_bounds__(SE_WG_COLLIDE) void k_collide_boxes(DevMap m, Colli
     // REFERENCE bookkeeping: per class, the smallest end (block-unit Morton code) of an expanded node that raised it; L* found
     uint32_t end_cls[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
     bool found = false;
-    __syncthreads();
-    if (lane == 0) {
-      s_pos[0][0] = 0u; s_nid[0][0] = 0u;
-#pragma unroll
-      for (int l = 0; l < SE_MAX_LEVELS; ++l) s_cnt[l] = l == 0 ? 1 : 0;
-    }
-    __syncthreads();
-    int l = 0;
-    while (run) {
-      const int cnt = s_cnt[l];
-      if (cnt == 0) {
-        if (l == 0) break;
-        --l;
-        continue;
-      }
-      const int take = min(cnt, 8);
-      const int j = lane >> 3, c = lane & 7;
-      const bool lv = j < take;
-      const uint32_t pp = lv ? s_pos[l][cnt - 1 - j] : 0u;
-      const uint32_t nid = lv ? s_nid[l][cnt - 1 - j] : 0u;
-      __syncthreads();
-      if (lane == 0) s_cnt[l] = cnt - take;
-      const int L = l + 1;
-      const int s = m.size >> L;   // child side in voxels
-      const int cx = (int)((pp & 1023u) << 1) | (c & 1), cy = (int)(((pp >> 10) & 1023u) << 1) | ((c >> 1) & 1), cz = (int)((pp >> 20) << 1) | (c >> 2);
-      uint32_t e = lv ? m.tab[s_off[L] + (((((uint32_t)cz << L) | (uint32_t)cy) << L) | (uint32_t)cx)] : 0u;
-      const bool present = lv && e != 0u && e != SE_PENDING;
+    int l;
+    SeFrontierStep t;
+    se_frontier_root(f, l);
+    while (run && se_frontier_pop(f, m, l, t)) {
+      const int s = t.s, cx = t.cx, cy = t.cy, cz = t.cz;
+      // (REFERENCE needs `present` of all eight children of a parent, overlapping or not)
+      const uint32_t e = se_frontier_entry(f, m, t, t.live);
+      const bool present = t.live && e != 0u && e != SE_PENDING;
       bool ov;
       if (a.reference) {
         ov = se_collide_ref_overlap(amid[0], ae[0], cx * s, s) && se_collide_ref_overlap(amid[1], ae[1], cy * s, s) && se_collide_ref_overlap(amid[2], ae[2], cz * s, s);
       } else {
         ov = cx * s < b1[0] && cx * s + s > b0[0] && cy * s < b1[1] && cy * s + s > b0[1] && cz * s < b1[2] && cz * s + s > b0[2];
       }
-      ov = ov && lv;
+      ov = ov && t.live;
       // events of absent overlapping children
       const bool absent = ov && !present;
       if (!a.reference) {
         uint32_t cls = SE_COLLIDE_EMPTY;
-        if (absent) cls = se_collide_class(m.nx[(size_t)nid * 8 + c], m.ny[(size_t)nid * 8 + c], fc, thr, above);
+        if (absent) cls = se_collide_class(m.nx[(size_t)t.nid * 8 + t.c], m.ny[(size_t)t.nid * 8 + t.c], fc, thr, above);
         st = min(st, se_collide_wave_min(cls));
       } else {
         const unsigned long long has = __ballot(present);   // children_mask_ != 0 of each parent: its 8-lane group
-        const bool ev = absent && ((has >> (8 * j)) & 0xFFull) != 0ull;
+        const bool ev = absent && ((has >> (8 * t.j)) & 0xFFull) != 0ull;
         uint32_t cls = SE_COLLIDE_EMPTY + 1u;
-        if (ev) cls = se_collide_class(m.nx[(size_t)nid * 8], m.ny[(size_t)nid * 8], fc, thr, above);
-        const int sh = 3 * (leaf - l);   // a level-l octant spans 8^(leaf - l) block codes
-        const uint32_t end = (morton30((int)(pp & 1023u), (int)((pp >> 10) & 1023u), (int)(pp >> 20)) + 1u) << sh;
+        if (ev) cls = se_collide_class(m.nx[(size_t)t.nid * 8], m.ny[(size_t)t.nid * 8], fc, thr, above);
+        const int sh = 3 * (leaf - t.L + 1);   // the parent, a level-(L - 1) octant, spans 8^(leaf - L + 1) block codes
+        const uint32_t end = (morton30((int)(t.pp & 1023u), (int)((t.pp >> 10) & 1023u), (int)(t.pp >> 20)) + 1u) << sh;
 #pragma unroll
         for (uint32_t k = 0; k < 3; ++k) {
           const unsigned long long b = __ballot(cls == k);
@@ -166,27 +137,15 @@ __global__ __launch_bounds__(SE_WG_COLLIDE) void k_collide_boxes(DevMap m, Colli
         }
       }
       const bool hit = ov && present;
-      if (L < leaf) {
-        const unsigned long long b = __ballot(hit);
-        const int tot = __popcll(b);
-        if (hit) {
-          const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-          s_pos[L][tot - 1 - (int)rank] = pack_pos(cx, cy, cz);
-          s_nid[L][tot - 1 - (int)rank] = e - 1u;
-        }
-        __syncthreads();
-        if (lane == 0 && tot) s_cnt[L] = tot;
-        __syncthreads();
-        if (tot) l = L;
+      if (t.L < leaf) {
+        se_frontier_push(f, t, hit, e, l);
       } else {
-        __syncthreads();
+        __syncthreads();   // the leaf step's barrier (se_frontier.h)
         unsigned long long b = __ballot(hit);
+        int qx, qy, qz;
         if (a.reference) {
           if (b) {   // L* = the lowest lane: its voxels that pass the inclusive test, folded from empty
-            const int w = (int)__builtin_ctzll(b);
-            const int qx = __builtin_amdgcn_readlane(cx, w), qy = __builtin_amdgcn_readlane(cy, w), qz = __builtin_amdgcn_readlane(cz, w);
-            const uint32_t qe = (uint32_t)__builtin_amdgcn_readlane((int)e, w);
-            const uint32_t slot = DENSE ? block_linear(m, qx, qy, qz) : qe - 1u;
+            const uint32_t slot = se_frontier_block<DENSE>(m, t, e, (int)__builtin_ctzll(b), qx, qy, qz);
             int r0[3], r1[3];
             const int q[3] = {qx * 8, qy * 8, qz * 8};
 #pragma unroll
@@ -207,9 +166,7 @@ __global__ __launch_bounds__(SE_WG_COLLIDE) void k_collide_boxes(DevMap m, Colli
           while (b && st != SE_COLLIDE_OCC) {
             const int w = (int)__builtin_ctzll(b);
             b &= b - 1ull;
-            const int qx = __builtin_amdgcn_readlane(cx, w), qy = __builtin_amdgcn_readlane(cy, w), qz = __builtin_amdgcn_readlane(cz, w);
-            const uint32_t qe = (uint32_t)__builtin_amdgcn_readlane((int)e, w);
-            const uint32_t slot = DENSE ? block_linear(m, qx, qy, qz) : qe - 1u;
+            const uint32_t slot = se_frontier_block<DENSE>(m, t, e, w, qx, qy, qz);
             st = min(st, se_collide_block(m, fc, thr, above, slot, qx * 8, qy * 8, qz * 8, max(b0[0], qx * 8), min(b1[0], qx * 8 + 8),
                                           max(b0[1], qy * 8), min(b1[1], qy * 8 + 8), max(b0[2], qz * 8), min(b1[2], qz * 8 + 8)));
           }

@@ -567,6 +567,12 @@ int batch_host(se_hip_pipeline* p, const void* in, size_t in_item_bytes, int64_t
   // (synchronises; a sticky overflow is reported as the other read-back calls report it)
   return fetch_counters(p);
 }
+// The launch of the wave-per-item query kernels (boxes, motions, clearance): grid-stride beyond 2^20 workgroups, one instantiation per brick layout.
+template <class Args>
+void launch_wave_per_item(se_hip_pipeline* p, int64_t n, void (*dense)(DevMap, Args), void (*pooled)(DevMap, Args), const Args& a) {
+  const int grid = (int)std::min<int64_t>(n, 1 << 20);
+  hipLaunchKernelGGL(p->map.dense ? dense : pooled, dim3(grid), dim3(SE_WG_COLLIDE), 0, p->stream, p->map, a);
+}
 
 // the images the raycast of `frame` writes, and every consumer (tracking, rendering, the getters) reads from then on
 void select_image_target(se_hip_pipeline* p, uint32_t frame) {
@@ -2182,21 +2188,26 @@ int se_hip_query_points_host(se_hip_pipeline* p, const float* host_points_m, int
 
 // ------------------------------------------------------------------------------------ box collision queries
 namespace {
+// The checks of the se_hip_collide_test, and of stop_at where the entry has one (else null), that the box, motion and clearance queries
+// share; `entry` names the caller in the message.
+int collide_test_args(const char* entry, const se_hip_collide_test* test, const int32_t* stop_at) {
+  const std::string e = std::string(entry) + ": ";
+  if (!test) return fail(SE_HIP_E_INVALID, e + "null test");
+  if (!std::isfinite(test->threshold)) return fail(SE_HIP_E_INVALID, e + "non-finite threshold");
+  if (test->occupied_above != 0 && test->occupied_above != 1) return fail(SE_HIP_E_INVALID, e + "occupied_above must be 0 or 1");
+  if (stop_at && *stop_at != SE_HIP_COLLISION_OCCUPIED && *stop_at != SE_HIP_COLLISION_UNSEEN) return fail(SE_HIP_E_INVALID, e + "stop_at must be occupied or unseen");
+  return SE_HIP_OK;
+}
 int collide_args(const int32_t* boxes, int64_t n, const se_hip_collide_test* test, int32_t mode, const uint8_t* status) {
   if (n < 0) return fail(SE_HIP_E_INVALID, "se_hip_collide_boxes: n < 0");
   if (n > 0 && (!boxes || !status)) return fail(SE_HIP_E_INVALID, "se_hip_collide_boxes: null boxes or status");
-  if (!test) return fail(SE_HIP_E_INVALID, "se_hip_collide_boxes: null test");
-  if (!std::isfinite(test->threshold)) return fail(SE_HIP_E_INVALID, "se_hip_collide_boxes: non-finite threshold");
-  if (test->occupied_above != 0 && test->occupied_above != 1) return fail(SE_HIP_E_INVALID, "se_hip_collide_boxes: occupied_above must be 0 or 1");
+  if (int r = collide_test_args("se_hip_collide_boxes", test, nullptr)) return r;
   if (mode != SE_HIP_COLLIDE_STRICT && mode != SE_HIP_COLLIDE_REFERENCE) return fail(SE_HIP_E_INVALID, "se_hip_collide_boxes: unknown mode");
   return SE_HIP_OK;
 }
 void launch_collide(se_hip_pipeline* p, const int32_t* boxes, int64_t n, const se_hip_collide_test* test, int32_t mode, uint8_t* status) {
-  const DevMap& m = p->map;
   const CollideArgs a{boxes, (long long)n, status, test->threshold, test->occupied_above, mode == SE_HIP_COLLIDE_REFERENCE ? 1 : 0};
-  const int grid = (int)std::min<int64_t>(n, 1 << 20);   // one wave per box, grid-stride beyond
-  if (m.dense) hipLaunchKernelGGL((k_collide_boxes<true>), dim3(grid), dim3(SE_WG_COLLIDE), 0, p->stream, m, a);
-  else hipLaunchKernelGGL((k_collide_boxes<false>), dim3(grid), dim3(SE_WG_COLLIDE), 0, p->stream, m, a);
+  launch_wave_per_item(p, n, k_collide_boxes<true>, k_collide_boxes<false>, a);
 }
 }  // namespace
 
@@ -2222,11 +2233,7 @@ int motion_args(const int32_t* motions, int64_t n, const se_hip_collide_test* te
   if (n < 0) return fail(SE_HIP_E_INVALID, "se_hip_collide_motions: n < 0");
   if (!out) return fail(SE_HIP_E_INVALID, "se_hip_collide_motions: null out");
   if (n > 0 && (!motions || !out->status)) return fail(SE_HIP_E_INVALID, "se_hip_collide_motions: null motions or status");
-  if (!test) return fail(SE_HIP_E_INVALID, "se_hip_collide_motions: null test");
-  if (!std::isfinite(test->threshold)) return fail(SE_HIP_E_INVALID, "se_hip_collide_motions: non-finite threshold");
-  if (test->occupied_above != 0 && test->occupied_above != 1) return fail(SE_HIP_E_INVALID, "se_hip_collide_motions: occupied_above must be 0 or 1");
-  if (stop_at != SE_HIP_COLLISION_OCCUPIED && stop_at != SE_HIP_COLLISION_UNSEEN) return fail(SE_HIP_E_INVALID, "se_hip_collide_motions: stop_at must be occupied or unseen");
-  return SE_HIP_OK;
+  return collide_test_args("se_hip_collide_motions", test, &stop_at);
 }
 // t_first (4-byte items) before status (bytes): the order the staging layout asks for (static: see query_outs)
 static BatchOuts motion_outs(const se_hip_motion_out* out) {
@@ -2234,11 +2241,8 @@ static BatchOuts motion_outs(const se_hip_motion_out* out) {
   return {2, {{out->t_first, sizeof(float)}, {out->status, 1}}};
 }
 void launch_motions(se_hip_pipeline* p, const int32_t* motions, int64_t n, const se_hip_collide_test* test, int32_t stop_at, void* const* out) {
-  const DevMap& m = p->map;
   const MotionArgs a{motions, (long long)n, (uint8_t*)out[1], (float*)out[0], test->threshold, test->occupied_above, (uint32_t)stop_at};
-  const int grid = (int)std::min<int64_t>(n, 1 << 20);   // one wave per motion, grid-stride beyond
-  if (m.dense) hipLaunchKernelGGL((k_collide_motions<true>), dim3(grid), dim3(SE_WG_COLLIDE), 0, p->stream, m, a);
-  else hipLaunchKernelGGL((k_collide_motions<false>), dim3(grid), dim3(SE_WG_COLLIDE), 0, p->stream, m, a);
+  launch_wave_per_item(p, n, k_collide_motions<true>, k_collide_motions<false>, a);
 }
 }  // namespace
 
@@ -2262,11 +2266,7 @@ int clearance_args(const int32_t* queries, int64_t n, const se_hip_collide_test*
   if (n < 0) return fail(SE_HIP_E_INVALID, "se_hip_clearance_boxes: n < 0");
   if (!out) return fail(SE_HIP_E_INVALID, "se_hip_clearance_boxes: null out");
   if (n > 0 && (!queries || !out->d2)) return fail(SE_HIP_E_INVALID, "se_hip_clearance_boxes: null queries or d2");
-  if (!test) return fail(SE_HIP_E_INVALID, "se_hip_clearance_boxes: null test");
-  if (!std::isfinite(test->threshold)) return fail(SE_HIP_E_INVALID, "se_hip_clearance_boxes: non-finite threshold");
-  if (test->occupied_above != 0 && test->occupied_above != 1) return fail(SE_HIP_E_INVALID, "se_hip_clearance_boxes: occupied_above must be 0 or 1");
-  if (stop_at != SE_HIP_COLLISION_OCCUPIED && stop_at != SE_HIP_COLLISION_UNSEEN) return fail(SE_HIP_E_INVALID, "se_hip_clearance_boxes: stop_at must be occupied or unseen");
-  return SE_HIP_OK;
+  return collide_test_args("se_hip_clearance_boxes", test, &stop_at);
 }
 // (static: see query_outs)
 static BatchOuts clearance_outs(const se_hip_clearance_out* out) {
@@ -2274,11 +2274,8 @@ static BatchOuts clearance_outs(const se_hip_clearance_out* out) {
   return {2, {{out->d2, sizeof(int32_t)}, {out->nearest, 3 * sizeof(int32_t)}}};
 }
 void launch_clearance(se_hip_pipeline* p, const int32_t* queries, int64_t n, const se_hip_collide_test* test, int32_t stop_at, void* const* out) {
-  const DevMap& m = p->map;
   const ClearanceArgs a{queries, (long long)n, (int32_t*)out[0], (int32_t*)out[1], test->threshold, test->occupied_above, (uint32_t)stop_at};
-  const int grid = (int)std::min<int64_t>(n, 1 << 20);   // one wave per query, grid-stride beyond
-  if (m.dense) hipLaunchKernelGGL((k_clearance_boxes<true>), dim3(grid), dim3(SE_WG_COLLIDE), 0, p->stream, m, a);
-  else hipLaunchKernelGGL((k_clearance_boxes<false>), dim3(grid), dim3(SE_WG_COLLIDE), 0, p->stream, m, a);
+  launch_wave_per_item(p, n, k_clearance_boxes<true>, k_clearance_boxes<false>, a);
 }
 }  // namespace
 

@@ -11,10 +11,8 @@
 // magnitude -- compared by cross-multiplication in int64 (products below 2^44).  The entry parameter of a part of a cube is never smaller than
 // the cube's, so skipping an octant whose entry parameter is not below the best found so far loses nothing.
 //
-// One wave64 per motion (grid-stride over int64 n), wave-uniform control flow; the frontier scheme is that of k_collide_boxes
-// (se_collide_kernels.h): a frontier of present touched octants per level in LDS, a step pops up to 8 nodes of the deepest non-empty level and
-// tests their 64 children, one per lane, and compacts the present touched ones into the next level with ballot + mbcnt.  The deepest non-empty
-// level is always taken, so the next level is empty when it is filled: 64 entries per level suffice, whatever the overlap test.
+// One wave64 per motion (grid-stride over int64 n), wave-uniform control flow, on the frontier descent of se_frontier.h; the frontier holds
+// the present touched octants that can still change an output.
 //   - an absent touched child folds classify(value_[child]) into the status and, if that class blocks, its entry parameter into the lane's
 //     best: exact, because every voxel of the octant reads that value;
 //   - at a block the lanes are its 8 x 8 columns: a lane forms the x / y part of its column's interval once and then tests its 8 z voxels
@@ -23,8 +21,8 @@
 //     the end: the uniform best is what pruning reads and what is written;
 //   - an octant or block is skipped iff it can change neither output: the status is already occupied and t_first is not wanted or the
 //     octant's entry parameter is not below the best.  Without t_first the search stops at the first occupied step, as the box kernel does.
-// Every loop is bounded by the structure: a step pops at least one frontier entry and pushes only children of what it popped (the pyramid is
-// finite), and a leaf step visits at most 64 blocks.
+// Every loop is bounded by the structure: the descent by the argument in se_frontier.h, whatever the test, and a leaf step visits at most
+// 64 blocks.
 #pragma once
 #include "se_collide_kernels.h"
 
@@ -47,15 +45,17 @@ __device__ __forceinline__ bool se_motion_axis(int lo, int hi, int d, int c, int
   return true;
 }
 
-// the wave's smallest n / d, the same pair in every lane
-__device__ __forceinline__ void se_motion_wave_min(int& n, int& d) {
+// If some lane improved its best bn / bd: the wave's smallest pair into every lane's best and into the uniform gn / gd.
+__device__ __forceinline__ void se_motion_settle(int& bn, int& bd, bool& improved, int& gn, int& gd) {
+  if (__ballot(improved) == 0ull) return;
 #pragma unroll
   for (int off = 32; off; off >>= 1) {
-    const int on = __shfl_xor(n, off), od = __shfl_xor(d, off);
-    if (se_rat_less(on, od, n, d)) { n = on; d = od; }
+    const int on = __shfl_xor(bn, off), od = __shfl_xor(bd, off);
+    if (se_rat_less(on, od, bn, bd)) { bn = on; bd = od; }
   }
-  n = __builtin_amdgcn_readfirstlane(n);   // (equal values may be written differently: every lane takes lane 0's pair)
-  d = __builtin_amdgcn_readfirstlane(d);
+  gn = bn = __builtin_amdgcn_readfirstlane(bn);   // (equal values may be written differently: every lane takes lane 0's pair)
+  gd = bd = __builtin_amdgcn_readfirstlane(bd);
+  improved = false;
 }
 
 // The voxels of the block at slot `slot` (corner bc) that the motion touches: their classes folded from empty (returned as the wave's min),
@@ -80,7 +80,7 @@ __device__ __forceinline__ uint32_t se_motion_block(const DevMap& m, const Field
   for (int k = 0; k < 8; ++k) {
     vx[k] = fc.init_x; vy[k] = fc.init_y;
     if (t[k]) {
-      const size_t vi = (size_t)slot * SE_BRICK_STRIDE + (size_t)((lane & 7) + ((lane >> 3) << 3) + (k << 6));
+      const size_t vi = se_brick_voxel(slot, k);
       vx[k] = m.vx[vi]; vy[k] = se_ld_y(m, vi);
     }
   }
@@ -96,18 +96,12 @@ __device__ __forceinline__ uint32_t se_motion_block(const DevMap& m, const Field
   return se_collide_wave_min(c);
 }
 
-// One instantiation per brick layout: the dense grid addresses a block's brick by its grid position, the pooled one by its index entry.
 template <bool DENSE>
 __global__ __launch_bounds__(SE_WG_COLLIDE) void k_collide_motions(DevMap m, MotionArgs a) {
-  __shared__ uint32_t s_pos[SE_MAX_LEVELS][64];   // frontier per level: packed octant position (x | y << 10 | z << 20)
-  __shared__ uint32_t s_nid[SE_MAX_LEVELS][64];   // ... and its node id
-  __shared__ uint32_t s_off[SE_MAX_LEVELS];       // m.off[] (a by-value DevMap array indexed by a runtime level would go to scratch)
-  __shared__ int s_cnt[SE_MAX_LEVELS];
+  __shared__ SeFrontier f;
   const FieldConst fc = se_field_const(m);
   const int lane = (int)(threadIdx.x & 63u);
-#pragma unroll
-  for (int l = 0; l < SE_MAX_LEVELS; ++l)
-    if (lane == l) s_off[l] = m.off[l];
+  se_frontier_init(f, m);
   const int leaf = m.leaf_level;
   const float thr = a.thr;
   const int above = a.above;
@@ -147,64 +141,34 @@ __global__ __launch_bounds__(SE_WG_COLLIDE) void k_collide_motions(DevMap m, Mot
     }
     int bn = gn, bd = gd;    // this lane's best; equal to the wave's after each step
     bool improved = false;
-    __syncthreads();
-    if (lane == 0) {
-      s_pos[0][0] = 0u; s_nid[0][0] = 0u;
-#pragma unroll
-      for (int l = 0; l < SE_MAX_LEVELS; ++l) s_cnt[l] = l == 0 ? 1 : 0;
-    }
-    __syncthreads();
-    int l = 0;
-    while (run) {
-      const int cnt = s_cnt[l];
-      if (cnt == 0) {
-        if (l == 0) break;
-        --l;
-        continue;
-      }
-      const int take = min(cnt, 8);
-      const int j = lane >> 3, c = lane & 7;
-      const bool lv = j < take;
-      const uint32_t pp = lv ? s_pos[l][cnt - 1 - j] : 0u;
-      const uint32_t nid = lv ? s_nid[l][cnt - 1 - j] : 0u;
-      __syncthreads();
-      if (lane == 0) s_cnt[l] = cnt - take;
-      const int L = l + 1;
-      const int s = m.size >> L;   // child side in voxels
-      const int cx = (int)((pp & 1023u) << 1) | (c & 1), cy = (int)(((pp >> 10) & 1023u) << 1) | ((c >> 1) & 1), cz = (int)((pp >> 20) << 1) | (c >> 2);
-      uint32_t e = lv ? m.tab[s_off[L] + (((((uint32_t)cz << L) | (uint32_t)cy) << L) | (uint32_t)cx)] : 0u;
-      const bool present = lv && e != 0u && e != SE_PENDING;
+    int l;
+    SeFrontierStep t;
+    se_frontier_root(f, l);
+    while (run && se_frontier_pop(f, m, l, t)) {
+      const int s = t.s, cx = t.cx, cy = t.cy, cz = t.cz;
+      const uint32_t e = se_frontier_entry(f, m, t, t.live);
+      const bool present = t.live && e != 0u && e != SE_PENDING;
       // the exact test of the child octant; tn / td its entry parameter
       int tn = 0, td = 1, Un = 1, Ud = 1;
       bool ov = se_motion_axis(lo[0], hi[0], d[0], cx * s, s, tn, td, Un, Ud);
       ov = se_motion_axis(lo[1], hi[1], d[1], cy * s, s, tn, td, Un, Ud) && ov;
       ov = se_motion_axis(lo[2], hi[2], d[2], cz * s, s, tn, td, Un, Ud) && ov;
-      ov = ov && lv && se_rat_less(tn, td, Un, Ud);
+      ov = ov && t.live && se_rat_less(tn, td, Un, Ud);
       // an octant that can change neither output is dropped
       if (st == SE_COLLIDE_OCC) ov = ov && want_t && se_rat_less(tn, td, gn, gd);
       // absent touched children: the whole octant has the class of value_[child]
       const bool absent = ov && !present;
       uint32_t cls = SE_COLLIDE_EMPTY;
       if (absent) {
-        cls = se_collide_class(m.nx[(size_t)nid * 8 + c], m.ny[(size_t)nid * 8 + c], fc, thr, above);
+        cls = se_collide_class(m.nx[(size_t)t.nid * 8 + t.c], m.ny[(size_t)t.nid * 8 + t.c], fc, thr, above);
         if (want_t && cls <= stop_at && se_rat_less(tn, td, bn, bd)) { bn = tn; bd = td; improved = true; }
       }
       st = min(st, se_collide_wave_min(cls));
       const bool hit = ov && present;
-      if (L < leaf) {
-        const unsigned long long b = __ballot(hit);
-        const int tot = __popcll(b);
-        if (hit) {
-          const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-          s_pos[L][tot - 1 - (int)rank] = pack_pos(cx, cy, cz);
-          s_nid[L][tot - 1 - (int)rank] = e - 1u;
-        }
-        __syncthreads();
-        if (lane == 0 && tot) s_cnt[L] = tot;
-        __syncthreads();
-        if (tot) l = L;
+      if (t.L < leaf) {
+        se_frontier_push(f, t, hit, e, l);
       } else {
-        __syncthreads();
+        __syncthreads();   // the leaf step's barrier (se_frontier.h)
         unsigned long long b = __ballot(hit);
         while (b) {
           const int w = (int)__builtin_ctzll(b);
@@ -214,20 +178,13 @@ __global__ __launch_bounds__(SE_WG_COLLIDE) void k_collide_motions(DevMap m, Mot
             const int wn = __builtin_amdgcn_readlane(tn, w), wd = __builtin_amdgcn_readlane(td, w);
             if (!se_rat_less(wn, wd, gn, gd)) continue;
           }
-          const int qx = __builtin_amdgcn_readlane(cx, w), qy = __builtin_amdgcn_readlane(cy, w), qz = __builtin_amdgcn_readlane(cz, w);
-          const uint32_t qe = (uint32_t)__builtin_amdgcn_readlane((int)e, w);
-          const uint32_t slot = DENSE ? block_linear(m, qx, qy, qz) : qe - 1u;
+          int qx, qy, qz;
+          const uint32_t slot = se_frontier_block<DENSE>(m, t, e, w, qx, qy, qz);
           st = min(st, se_motion_block(m, fc, thr, above, stop_at, want_t, slot, qx * 8, qy * 8, qz * 8, lo, hi, d, bn, bd, improved));
-          if (__ballot(improved) != 0ull) {
-            se_motion_wave_min(bn, bd);
-            gn = bn; gd = bd; improved = false;
-          }
+          se_motion_settle(bn, bd, improved, gn, gd);
         }
       }
-      if (__ballot(improved) != 0ull) {
-        se_motion_wave_min(bn, bd);
-        gn = bn; gd = bd; improved = false;
-      }
+      se_motion_settle(bn, bd, improved, gn, gd);
       if (st == SE_COLLIDE_OCC && (!want_t || gn == 0)) break;   // nothing can change either output any more
     }
     if (lane == 0) {
