@@ -36,10 +36,10 @@
 
 #define SE_PENDING 0xFFFFFFFFu
 // Floats from one brick to the next: one array of 4 KB bricks [512 x | y plane at float 512 = byte 2048] -- a voxel's two values share a 4 KB page
-// (one address translation per get() instead of two; dense maps scatter bricks over 8 / 64 GiB), see DESIGN.md 3.  The lean march paths
+// (one address translation per get() instead of two; dense maps scatter bricks over 8 / 64 GiB), see DESIGN.md 3.  The lean forms of se_sample.h
 // (SeDense, se_pooled_index) spell the layout out as shifts: 4 096 bytes per brick, y plane 2 048 bytes behind x.
 #define SE_BRICK_STRIDE 1024
-static_assert(SE_BRICK_STRIDE == 1024, "the march paths of se_kernels.h address bricks as [512 x | 512 y] = 4 KB");
+static_assert(SE_BRICK_STRIDE == 1024, "se_sample.h addresses bricks as [512 x | 512 y] = 4 KB");
 #define SE_MAX_LEVELS 12
 
 enum { C_BLOCKS = 0, C_NODES = 1, C_OVERFLOW = 2, C_COUNT = 8 };

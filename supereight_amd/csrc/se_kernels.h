@@ -4,6 +4,7 @@
 // allocation by atomic insertion, the per-thread active-list build by an in-kernel predicate.
 #pragma once
 #include "se_device.h"
+#include "se_sample.h"
 
 #ifndef SE_WG
 #define SE_WG 256
@@ -1110,227 +1111,30 @@ struct RayArgs {
   unsigned long long* wlog;   // -DSE_WAVE_PROBE builds only (tools/wave_timeline.py): per-wave clock records, pinned host memory; null otherwise
 };
 
-struct BlkCache { int bx, by, bz; uint32_t e; };
-// voxel_traits<T>::initValue() / empty() as register values.  Reading them through the by-value
-// DevMap inside `cond ? load : m.init_x` lets the compiler fold both into one FLAT load of a
-// selected address (and park the constants in scratch to have an address).
-struct FieldConst { float init_x, init_y, empty_x; };
-__device__ __forceinline__ FieldConst se_field_const(const DevMap& m) {
-  FieldConst f = {m.init_x, m.init_y, m.empty_x};
-  asm volatile("" : "+s"(f.init_x), "+s"(f.init_y), "+s"(f.empty_x));
-  return f;
-}
-
-__device__ __forceinline__ size_t se_voxel_index(uint32_t e, int x, int y, int z) {
-  return (size_t)(e - 1u) * SE_BRICK_STRIDE + (size_t)((x & 7) + ((y & 7) << 3) + ((z & 7) << 6));
-}
-
-// Memory-level parallelism is what the raycast kernel lives on: a wave is a chain of dependent L2
-// round trips, so interp and grad are written as "all block look-ups -> all voxel loads -> math"
-// with unconditional loads (a missing block reads a dummy address and the value is replaced
-// afterwards) instead of one branch per sample.
-
-// leaf-grid entry of block (bx,by,bz) or 0 outside the volume; `hint` is a block whose entry is
-// already known (the block of the preceding get) and saves the load.
-template <bool DENSE>
-__device__ __forceinline__ uint32_t se_block_entry(const DevMap& m, int bx, int by, int bz, const BlkCache& hint) {
-  const int nb = m.size >> 3;
-  uint32_t e = 0u;
-  if (DENSE) return ((unsigned)bx < (unsigned)nb && (unsigned)by < (unsigned)nb && (unsigned)bz < (unsigned)nb) ? block_linear(m, bx, by, bz) + 1u : 0u;
-  if (bx == hint.bx && by == hint.by && bz == hint.bz) e = hint.e;
-  else if ((unsigned)bx < (unsigned)nb && (unsigned)by < (unsigned)nb && (unsigned)bz < (unsigned)nb) e = m.tab[leaf_index(m, bx, by, bz)];
-  // Pooled bricks: the allocation scan of the NEXT frame may be inserting blocks while this raycast runs (overlap mode).  An
-  // entry in flight reads as PENDING -> "not allocated"; one already published points at a brick that still holds
-  // initValue() in every voxel (bricks are pre-filled and never recycled), which is exactly what "not allocated" reads as
-  // (initValue().x == empty().x for both field types) -- so the race cannot change a result.
-  return e == SE_PENDING ? 0u : e;
-}
-
-// Octree::interp (octree.hpp:541-563) with gather_points (interp_gather.hpp:107-237): every corner
-// is read from the block that contains it; a missing block yields empty().x, the all-cross case
-// goes through get_fine -> initValue().x (identical values for both field types).
-template <bool DENSE>
-__device__ __forceinline__ float se_interp_generic(const DevMap& m, const FieldConst fc, f3 pos, BlkCache& c) {
-  const float flx = floorf(pos.x), fly = floorf(pos.y), flz = floorf(pos.z);
-  const int bx = cvt_i32(flx), by = cvt_i32(fly), bz = cvt_i32(flz);
-  const float fx = pos.x - flx, fy = pos.y - fly, fz = pos.z - flz;
-  const int lx = max(bx, 0), ly = max(by, 0), lz = max(bz, 0);
-  const bool cx = (lx & 7) == 7, cy = (ly & 7) == 7, cz = (lz & 7) == 7;
-  const float missing = (cx && cy && cz) ? fc.init_x : fc.empty_x;
-  // phase 1: the (up to 8) blocks the cell touches
-  uint32_t e[8];
-  e[0] = se_block_entry<DENSE>(m, lx >> 3, ly >> 3, lz >> 3, c);
-#pragma unroll
-  for (int k = 1; k < 8; ++k) {
-    const bool need = (!(k & 1) || cx) && (!(k & 2) || cy) && (!(k & 4) || cz);
-    e[k] = 0u;
-    if (need) e[k] = se_block_entry<DENSE>(m, (lx + (k & 1)) >> 3, (ly + ((k >> 1) & 1)) >> 3, (lz + (k >> 2)) >> 3, c);
-  }
-  // phase 2: the 8 corner values.  Corner (i, j, k) lies in block (i && cx, j && cy, k && cz) of the 2x2x2 candidates: the entry is picked axis by
-  // axis (12 selects for the cell; r04 -- a chain of seven compares and selects per corner before) and the voxel offset is a sum of per-axis terms
-  uint32_t ex1[4], exy[2][2][2];     // ex1[q] = the x-upper corner's entry for (y, z) block pair q; exy[i][j][s] after the y step
-#pragma unroll
-  for (int q = 0; q < 4; ++q) ex1[q] = cx ? e[2 * q + 1] : e[2 * q];
-#pragma unroll
-  for (int sz = 0; sz < 2; ++sz) {
-    exy[0][0][sz] = e[4 * sz];
-    exy[1][0][sz] = ex1[2 * sz];
-    exy[0][1][sz] = cy ? e[4 * sz + 2] : e[4 * sz];
-    exy[1][1][sz] = cy ? ex1[2 * sz + 1] : ex1[2 * sz];
-  }
-  const uint32_t ox[2] = {(uint32_t)lx & 7u, (uint32_t)(lx + 1) & 7u};
-  const uint32_t oy[2] = {((uint32_t)ly & 7u) << 3, ((uint32_t)(ly + 1) & 7u) << 3};
-  const uint32_t oz[2] = {((uint32_t)lz & 7u) << 6, ((uint32_t)(lz + 1) & 7u) << 6};
-  float p[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int i = k & 1, j = (k >> 1) & 1, kz = k >> 2;
-    const uint32_t ek = kz ? (cz ? exy[i][j][1] : exy[i][j][0]) : exy[i][j][0];
-    const size_t vi = ek ? (size_t)(ek - 1u) * SE_BRICK_STRIDE + (size_t)(ox[i] + oy[j] + oz[kz]) : 0;
-    const float v = m.vx[vi];
-    p[k] = ek ? v : missing;
-  }
-  return (((p[0] * (1 - fx) + p[1] * fx) * (1 - fy) + (p[2] * (1 - fx) + p[3] * fx) * fy) * (1 - fz) +
-          ((p[4] * (1 - fx) + p[5] * fx) * (1 - fy) + (p[6] * (1 - fx) + p[7] * fx) * fy) * fz);
-}
-
-// Dense grid, sample stencil entirely inside the volume (always, for a point the march can reach): the
-// voxel index (bz << 2l | by << l | bx) * 512 + (x & 7) + 8 (y & 7) + 64 (z & 7) is a sum of one term per axis,
-// so a stencil costs a few integer operations per axis plus two additions per sample instead of a full index
-// computation per sample (the gradient's 32 samples were a quarter of the kernel's vector instructions).
-// Same loads, same arithmetic on the values as the generic forms, which stay the fallback.
-struct AxisTerm { uint32_t blk, loc; };
-__device__ __forceinline__ AxisTerm se_axis_x(int x) { return {(uint32_t)(x >> 3), (uint32_t)(x & 7)}; }
-__device__ __forceinline__ AxisTerm se_axis_y(const DevMap& m, int y) { return {(uint32_t)(y >> 3) << m.leaf_level, (uint32_t)(y & 7) << 3}; }
-__device__ __forceinline__ AxisTerm se_axis_z(const DevMap& m, int z) { return {(uint32_t)(z >> 3) << (2 * m.leaf_level), (uint32_t)(z & 7) << 6}; }
-__device__ __forceinline__ size_t se_axis_index(AxisTerm a, AxisTerm b, AxisTerm c) {
-  return (size_t)(a.blk + b.blk + c.blk) * SE_BRICK_STRIDE + (size_t)(a.loc + b.loc + c.loc);
-}
-
-// Octree::grad (octree.hpp:652-737), same term order.  The 48 get() calls of the reference touch
-// 32 distinct voxels: per axis the four clamped coordinates {base-1, base, base+1, base+2} (indices
-// 0..3 below; "lower" = 1, "upper" = 2), every sample having at least two axes on a central index.
-// They lie in at most 2x2x2 blocks.  A voxel of a missing block reads as initValue().x (the cached
-// Octree::get(x,y,z,block) falls back to the tree walk, octree.hpp:379-408).
-template <bool DENSE>
-__device__ __forceinline__ f3 se_grad_generic(const DevMap& m, const FieldConst fc, f3 pos, BlkCache& c) {
-  const float flx = floorf(pos.x), fly = floorf(pos.y), flz = floorf(pos.z);
-  const int bx = cvt_i32(flx), by = cvt_i32(fly), bz = cvt_i32(flz);
-  const float fx = pos.x - flx, fy = pos.y - fly, fz = pos.z - flz;
-  const int hi = m.size - 1;
-  const int X[4] = {max(bx - 1, 0), max(bx, 0), min(bx + 1, hi), min(bx + 2, hi)};
-  const int Y[4] = {max(by - 1, 0), max(by, 0), min(by + 1, hi), min(by + 2, hi)};
-  const int Z[4] = {max(bz - 1, 0), max(bz, 0), min(bz + 1, hi), min(bz + 2, hi)};
-  const int xb0 = X[0] >> 3, yb0 = Y[0] >> 3, zb0 = Z[0] >> 3;
-  const int xb1 = X[3] >> 3, yb1 = Y[3] >> 3, zb1 = Z[3] >> 3;
-  // phase 1: entries of the 2x2x2 candidate blocks (coincident ones are the same cache line)
-  uint32_t e[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) e[k] = se_block_entry<DENSE>(m, (k & 1) ? xb1 : xb0, (k & 2) ? yb1 : yb0, (k & 4) ? zb1 : zb0, c);
-  // phase 2: the 32 voxels.  A voxel's block among the 2x2x2 candidates is (x block != xb0, y block != yb0, z block != zb0): the brick base is
-  // picked axis by axis (x: 16 selects, y: 32, z: one per voxel; r04 -- seven compares and selects per voxel before) and the offset inside the
-  // brick is a sum of per-axis terms.  `base` = brick offset + 1 in voxels' units (0: no brick), so that "missing" stays one test.
-  bool ux[4], uy[4], uz[4];
-  uint32_t ox[4], oy[4], oz[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    ux[i] = (X[i] >> 3) != xb0; uy[i] = (Y[i] >> 3) != yb0; uz[i] = (Z[i] >> 3) != zb0;
-    ox[i] = (uint32_t)X[i] & 7u; oy[i] = ((uint32_t)Y[i] & 7u) << 3; oz[i] = ((uint32_t)Z[i] & 7u) << 6;
-  }
-  uint32_t ex[4][4];        // [xi][q]: entry of x-voxel xi in the (y, z) block pair q
-#pragma unroll
-  for (int xi = 0; xi < 4; ++xi)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) ex[xi][q] = ux[xi] ? e[2 * q + 1] : e[2 * q];
-  float V[4][4][4];
-#pragma unroll
-  for (int yi = 0; yi < 4; ++yi)
-#pragma unroll
-    for (int xi = 0; xi < 4; ++xi) {
-      if (!((xi == 1 || xi == 2) || (yi == 1 || yi == 2))) continue;      // (no voxel of this column is needed)
-      const uint32_t exy0 = uy[yi] ? ex[xi][1] : ex[xi][0], exy1 = uy[yi] ? ex[xi][3] : ex[xi][2];
-      const uint32_t oxy = ox[xi] + oy[yi];
-#pragma unroll
-      for (int zi = 0; zi < 4; ++zi) {
-        const int central = (xi == 1 || xi == 2) + (yi == 1 || yi == 2) + (zi == 1 || zi == 2);
-        if (central < 2) continue;
-        const uint32_t ek = uz[zi] ? exy1 : exy0;
-        const size_t vi = ek ? (size_t)(ek - 1u) * SE_BRICK_STRIDE + (size_t)(oxy + oz[zi]) : 0;
-        const float v = m.vx[vi];
-        V[zi][yi][xi] = ek ? v : fc.init_x;
-      }
-    }
-  f3 g;
-  g.x = (((V[1][1][2] - V[1][1][0]) * (1 - fx) + (V[1][1][3] - V[1][1][1]) * fx) * (1 - fy) +
-         ((V[1][2][2] - V[1][2][0]) * (1 - fx) + (V[1][2][3] - V[1][2][1]) * fx) * fy) * (1 - fz) +
-        (((V[2][1][2] - V[2][1][0]) * (1 - fx) + (V[2][1][3] - V[2][1][1]) * fx) * (1 - fy) +
-         ((V[2][2][2] - V[2][2][0]) * (1 - fx) + (V[2][2][3] - V[2][2][1]) * fx) * fy) * fz;
-  g.y = (((V[1][2][1] - V[1][0][1]) * (1 - fx) + (V[1][2][2] - V[1][0][2]) * fx) * (1 - fy) +
-         ((V[1][3][1] - V[1][1][1]) * (1 - fx) + (V[1][3][2] - V[1][1][2]) * fx) * fy) * (1 - fz) +
-        (((V[2][2][1] - V[2][0][1]) * (1 - fx) + (V[2][2][2] - V[2][0][2]) * fx) * (1 - fy) +
-         ((V[2][3][1] - V[2][1][1]) * (1 - fx) + (V[2][3][2] - V[2][1][2]) * fx) * fy) * fz;
-  g.z = (((V[2][1][1] - V[0][1][1]) * (1 - fx) + (V[2][1][2] - V[0][1][2]) * fx) * (1 - fy) +
-         ((V[2][2][1] - V[0][2][1]) * (1 - fx) + (V[2][2][2] - V[0][2][2]) * fx) * fy) * (1 - fz) +
-        (((V[3][1][1] - V[1][1][1]) * (1 - fx) + (V[3][1][2] - V[1][1][2]) * fx) * (1 - fy) +
-         ((V[3][2][1] - V[1][2][1]) * (1 - fx) + (V[3][2][2] - V[1][2][2]) * fx) * fy) * fz;
-  return g;  // the caller applies (0.5f * dim / size)
-}
-
-// Dense-grid forms of interp / grad on the per-axis terms above; the generic forms are the fallback.
-template <bool DENSE>
-__device__ __forceinline__ float se_interp(const DevMap& m, const FieldConst fc, f3 pos, BlkCache& c) {
-  if (!DENSE) return se_interp_generic<DENSE>(m, fc, pos, c);
-  const float flx = floorf(pos.x), fly = floorf(pos.y), flz = floorf(pos.z);
-  const int bx = cvt_i32(flx), by = cvt_i32(fly), bz = cvt_i32(flz);
-  const int lx = max(bx, 0), ly = max(by, 0), lz = max(bz, 0);
-  const int top = m.size - 1;
-  if (!(lx < top && ly < top && lz < top)) return se_interp_generic<DENSE>(m, fc, pos, c);   // a corner outside the volume
-  const float fx = pos.x - flx, fy = pos.y - fly, fz = pos.z - flz;
-  const AxisTerm X[2] = {se_axis_x(lx), se_axis_x(lx + 1)}, Y[2] = {se_axis_y(m, ly), se_axis_y(m, ly + 1)}, Z[2] = {se_axis_z(m, lz), se_axis_z(m, lz + 1)};
-  float p[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) p[k] = m.vx[se_axis_index(X[k & 1], Y[(k >> 1) & 1], Z[k >> 2])];
-  return (((p[0] * (1 - fx) + p[1] * fx) * (1 - fy) + (p[2] * (1 - fx) + p[3] * fx) * fy) * (1 - fz) +
-          ((p[4] * (1 - fx) + p[5] * fx) * (1 - fy) + (p[6] * (1 - fx) + p[7] * fx) * fy) * fz);
-}
-
-template <bool DENSE>
-__device__ __forceinline__ f3 se_grad(const DevMap& m, const FieldConst fc, f3 pos, BlkCache& c) {
-  if (!DENSE) return se_grad_generic<DENSE>(m, fc, pos, c);
-  const float flx = floorf(pos.x), fly = floorf(pos.y), flz = floorf(pos.z);
-  const int bx = cvt_i32(flx), by = cvt_i32(fly), bz = cvt_i32(flz);
-  const int hi = m.size - 1;
-  // indices 0, 1 are clamped from below only (octree.hpp:658-663): they leave the volume when the point does
-  if (!(bx <= hi && by <= hi && bz <= hi)) return se_grad_generic<DENSE>(m, fc, pos, c);
-  const float fx = pos.x - flx, fy = pos.y - fly, fz = pos.z - flz;
-  const AxisTerm X[4] = {se_axis_x(max(bx - 1, 0)), se_axis_x(max(bx, 0)), se_axis_x(min(bx + 1, hi)), se_axis_x(min(bx + 2, hi))};
-  const AxisTerm Y[4] = {se_axis_y(m, max(by - 1, 0)), se_axis_y(m, max(by, 0)), se_axis_y(m, min(by + 1, hi)), se_axis_y(m, min(by + 2, hi))};
-  const AxisTerm Z[4] = {se_axis_z(m, max(bz - 1, 0)), se_axis_z(m, max(bz, 0)), se_axis_z(m, min(bz + 1, hi)), se_axis_z(m, min(bz + 2, hi))};
-  float V[4][4][4];
-#pragma unroll
-  for (int zi = 0; zi < 4; ++zi)
-#pragma unroll
-    for (int yi = 0; yi < 4; ++yi)
-#pragma unroll
-      for (int xi = 0; xi < 4; ++xi) {
-        const int central = (xi == 1 || xi == 2) + (yi == 1 || yi == 2) + (zi == 1 || zi == 2);
-        if (central < 2) continue;
-        V[zi][yi][xi] = m.vx[se_axis_index(X[xi], Y[yi], Z[zi])];
-      }
-  f3 g;
-  g.x = (((V[1][1][2] - V[1][1][0]) * (1 - fx) + (V[1][1][3] - V[1][1][1]) * fx) * (1 - fy) +
-         ((V[1][2][2] - V[1][2][0]) * (1 - fx) + (V[1][2][3] - V[1][2][1]) * fx) * fy) * (1 - fz) +
-        (((V[2][1][2] - V[2][1][0]) * (1 - fx) + (V[2][1][3] - V[2][1][1]) * fx) * (1 - fy) +
-         ((V[2][2][2] - V[2][2][0]) * (1 - fx) + (V[2][2][3] - V[2][2][1]) * fx) * fy) * fz;
-  g.y = (((V[1][2][1] - V[1][0][1]) * (1 - fx) + (V[1][2][2] - V[1][0][2]) * fx) * (1 - fy) +
-         ((V[1][3][1] - V[1][1][1]) * (1 - fx) + (V[1][3][2] - V[1][1][2]) * fx) * fy) * (1 - fz) +
-        (((V[2][2][1] - V[2][0][1]) * (1 - fx) + (V[2][2][2] - V[2][0][2]) * fx) * (1 - fy) +
-         ((V[2][3][1] - V[2][1][1]) * (1 - fx) + (V[2][3][2] - V[2][1][2]) * fx) * fy) * fz;
-  g.z = (((V[2][1][1] - V[0][1][1]) * (1 - fx) + (V[2][1][2] - V[0][1][2]) * fx) * (1 - fy) +
-         ((V[2][2][1] - V[0][2][1]) * (1 - fx) + (V[2][2][2] - V[0][2][2]) * fx) * fy) * (1 - fz) +
-        (((V[3][1][1] - V[1][1][1]) * (1 - fx) + (V[3][1][2] - V[1][1][2]) * fx) * (1 - fy) +
-         ((V[3][2][1] - V[1][2][1]) * (1 - fx) + (V[3][2][2] - V[1][2][2]) * fx) * fy) * fz;
-  return g;  // the caller applies (0.5f * dim / size)
+// The set-up of se::ray_iterator (ray_iterator.hpp:53-102) for a ray through the volume cube [1, 2)^3: the direction's components clamped away from
+// zero by epsilon, t(plane) = plane * t_coef - t_bias per axis with the axes mirrored so that the ray runs towards lower coordinates (om = the mirrored
+// axes = octant_mask ^ 7), and the distances at which the ray enters and leaves the cube, before the near / far planes are applied.  scaled_origin =
+// origin / dim + 1, given as a callable: se_ray_range forms it by three divisions, which stay behind the direction clamp as before (issued in
+// front of it the volume renderer's kernels compile differently, profiles/march_fold_asm.txt).
+struct SeRaySetup { f3 t_coef, t_bias; uint32_t om; float t_in, t_out; };
+template <typename Origin>
+__device__ __forceinline__ SeRaySetup se_ray_setup(const RayArgs& a, f3 direction, Origin scaled_origin) {
+  SeRaySetup r;
+  const float eps = a.epsilon;
+  f3 d;
+  d.x = fabsf(direction.x) < eps ? copysignf(eps, direction.x) : direction.x;
+  d.y = fabsf(direction.y) < eps ? copysignf(eps, direction.y) : direction.y;
+  d.z = fabsf(direction.z) < eps ? copysignf(eps, direction.z) : direction.z;
+  const f3 so = scaled_origin();
+  r.t_coef = f3_scale(-1.f, {1.f / fabsf(d.x), 1.f / fabsf(d.y), 1.f / fabsf(d.z)});
+  r.t_bias = f3_mul(r.t_coef, so);
+  r.om = 0u;
+  if (d.x > 0.0f) { r.om ^= 1u; r.t_bias.x = 3.0f * r.t_coef.x - r.t_bias.x; }
+  if (d.y > 0.0f) { r.om ^= 2u; r.t_bias.y = 3.0f * r.t_coef.y - r.t_bias.y; }
+  if (d.z > 0.0f) { r.om ^= 4u; r.t_bias.z = 3.0f * r.t_coef.z - r.t_bias.z; }
+  r.t_in = fmaxf(fmaxf(2.0f * r.t_coef.x - r.t_bias.x, 2.0f * r.t_coef.y - r.t_bias.y), 2.0f * r.t_coef.z - r.t_bias.z);
+  r.t_out = fminf(fminf(r.t_coef.x - r.t_bias.x, r.t_coef.y - r.t_bias.y), r.t_coef.z - r.t_bias.z);
+  return r;
 }
 
 struct RaySpan { float tcmin, tmax; int trips; bool found = false; };   // found: se_first_leaf stopped at a leaf (the batch raycast's status bit)
@@ -1353,20 +1157,10 @@ __device__ __forceinline__ RaySpan se_first_leaf(const DevMap& m, const RayArgs&
   uint32_t parent = 1u;  // root
   float scale_exp2 = 0.5f;
   int scale = 22;
-  const float eps = a.epsilon;
-  f3 d;
-  d.x = fabsf(direction.x) < eps ? copysignf(eps, direction.x) : direction.x;
-  d.y = fabsf(direction.y) < eps ? copysignf(eps, direction.y) : direction.y;
-  d.z = fabsf(direction.z) < eps ? copysignf(eps, direction.z) : direction.z;
-  const f3 scaled_origin = {a.scaled_origin[0], a.scaled_origin[1], a.scaled_origin[2]};   // origin / dim + 1: the same for every ray, formed on the host
-  const f3 t_coef = f3_scale(-1.f, {1.f / fabsf(d.x), 1.f / fabsf(d.y), 1.f / fabsf(d.z)});
-  f3 t_bias = f3_mul(t_coef, scaled_origin);
-  uint32_t om = 0u;     // octant_mask ^ 7
-  if (d.x > 0.0f) { om ^= 1u; t_bias.x = 3.0f * t_coef.x - t_bias.x; }
-  if (d.y > 0.0f) { om ^= 2u; t_bias.y = 3.0f * t_coef.y - t_bias.y; }
-  if (d.z > 0.0f) { om ^= 4u; t_bias.z = 3.0f * t_coef.z - t_bias.z; }
-  float t_min = fmaxf(fmaxf(2.0f * t_coef.x - t_bias.x, 2.0f * t_coef.y - t_bias.y), 2.0f * t_coef.z - t_bias.z);
-  float t_max = fminf(fminf(t_coef.x - t_bias.x, t_coef.y - t_bias.y), t_coef.z - t_bias.z);
+  const SeRaySetup rs = se_ray_setup(a, direction, [&]() -> f3 { return {a.scaled_origin[0], a.scaled_origin[1], a.scaled_origin[2]}; });   // origin / dim + 1: the same for every ray, formed on the host
+  const f3 t_coef = rs.t_coef, t_bias = rs.t_bias;
+  const uint32_t om = rs.om;
+  float t_min = rs.t_in, t_max = rs.t_out;
   float h = t_max;
   t_min = fmaxf(t_min, a.near_n);   // nearp / dim
   t_max = fminf(t_max, a.far_n);    // farp / dim
@@ -1513,20 +1307,11 @@ __device__ __forceinline__ RaySpan se_first_leaf_lite(const DevMap& m, const Ray
   uint32_t parent = 1u;  // root
   float scale_exp2 = 0.5f;
   int scale = 22;
-  const float eps = a.epsilon;
-  f3 d;
-  d.x = fabsf(direction.x) < eps ? copysignf(eps, direction.x) : direction.x;
-  d.y = fabsf(direction.y) < eps ? copysignf(eps, direction.y) : direction.y;
-  d.z = fabsf(direction.z) < eps ? copysignf(eps, direction.z) : direction.z;
-  const f3 scaled_origin = {a.scaled_origin[0], a.scaled_origin[1], a.scaled_origin[2]};
-  const f3 t_coef = f3_scale(-1.f, {1.f / fabsf(d.x), 1.f / fabsf(d.y), 1.f / fabsf(d.z)});
-  f3 t_bias = f3_mul(t_coef, scaled_origin);
-  uint32_t om = 0u;     // octant_mask ^ 7
-  if (d.x > 0.0f) { om ^= 1u; t_bias.x = 3.0f * t_coef.x - t_bias.x; }
-  if (d.y > 0.0f) { om ^= 2u; t_bias.y = 3.0f * t_coef.y - t_bias.y; }
-  if (d.z > 0.0f) { om ^= 4u; t_bias.z = 3.0f * t_coef.z - t_bias.z; }
-  float t_min = fmaxf(fmaxf(2.0f * t_coef.x - t_bias.x, 2.0f * t_coef.y - t_bias.y), 2.0f * t_coef.z - t_bias.z);
-  const float h0 = fminf(fminf(t_coef.x - t_bias.x, t_coef.y - t_bias.y), t_coef.z - t_bias.z);
+  const SeRaySetup rs = se_ray_setup(a, direction, [&]() -> f3 { return {a.scaled_origin[0], a.scaled_origin[1], a.scaled_origin[2]}; });
+  const f3 t_coef = rs.t_coef, t_bias = rs.t_bias;
+  const uint32_t om = rs.om;
+  float t_min = rs.t_in;
+  const float h0 = rs.t_out;
   t_min = fmaxf(t_min, a.near_n);
   const float t_lim = fminf(h0, a.far_n);   // t_max_init: all the t_max this loop knows
   const float tmax_m = t_lim * m.dim;
@@ -1614,176 +1399,22 @@ __device__ __forceinline__ RaySpan se_first_leaf_lite(const DevMap& m, const Ray
 // (position, distance) or leaves it zero.  Shared by the raycast kernel and the volume renderer.
 struct RayCounters { unsigned long long n_get, n_interp; unsigned n_batch; };
 
-// ---- lean dense-grid march (r04) ---------------------------------------------------------------------------------
+// ---- lean march (r04) ------------------------------------------------------------------------------------------------
 // The raycast is bound by VALU issue slots, and by r03's counters two thirds of the march's instructions
-// were address arithmetic and range bookkeeping, not the reference's float operations.  For the dense grid:
+// were address arithmetic and range bookkeeping, not the reference's float operations.  Since then:
 //  * float -> int by the hardware conversion (one instruction) instead of the compare-and-select restatement of x86's
 //    cvttss2si: the two agree for |f| < 2^31 and differ only for NaN (0 instead of INT_MIN) -- rays whose direction or
 //    origin is not finite never get here (k_raycast: their result is "no hit" whatever the volume holds, because the
 //    first interp returns NaN) and the host only selects these kernels for poses within 2^30 voxels of the volume;
-//  * "inside the volume" is one compare of the OR of the three integers (size is a power of two, a negative or saturated
-//    value has high bits set);
-//  * a voxel's index is the sum of one term per axis, (block part << 10) | local part, so a sample costs ~4 integer
-//    operations per axis and the 8 / 32 voxels of interp / grad one 3-input add each; maps of <= 4 GiB (O32: 512^3 dense)
-//    carry the terms as byte offsets and load through a 32-bit offset from the scalar base, the brick's y plane with an
-//    immediate offset from the same address (y = x + 512 floats, se_device.h);
+//  * a sample is addressed as its brick layout does it most cheaply (se_sample.h; the layout policies below);
 //  * the eight corners of sample 0 are fetched with the batch only while the march is inside the band (previous value
 //    < 1): in free or unobserved space they were ~100 instructions and 8 loads per batch that nobody used.  A sample
-//    that turns out to need them without having them pays one extra round trip (se_interp), results unchanged;
+//    that turns out to need them without having them pays one extra round trip (the layout's interp), results unchanged;
 //  * `(double)f_tt <= 0.1` is `f_tt < 0.1f` (0.1f is the smallest float above 0.1): no double-precision compare.
 #ifndef SE_MARCH_SKIP
 #define SE_MARCH_SKIP 4    // SDF march in unobserved space: positions asked of the leaf bitmap per round trip (se_march_skip).  Measured off / 4 / 8
                            // (profiles/r04p_march_skip_ab.log): 59.8 / 59.8 / 61.6 us per frame at 512^3, 193.8 / 188.4 / 189.5 at 1024^3, stress 69.7 / 68.6 / 71.3
 #endif
-template <bool O32> struct SeDense;
-template <> struct SeDense<true> {     // byte-offset terms, 32 bit
-  typedef uint32_t idx_t;
-  static __device__ __forceinline__ idx_t tx(const DevMap&, uint32_t x) { return ((x >> 3) << 12) | ((x & 7u) << 2); }
-  static __device__ __forceinline__ idx_t ty(const DevMap& m, uint32_t y) { return ((y >> 3) << (12 + m.leaf_level)) | ((y & 7u) << 5); }
-  static __device__ __forceinline__ idx_t tz(const DevMap& m, uint32_t z) { return ((z >> 3) << (12 + 2 * m.leaf_level)) | ((z & 7u) << 8); }
-  static __device__ __forceinline__ idx_t sum(idx_t a, idx_t b, idx_t c) { return a + b + c; }
-  static __device__ __forceinline__ float ldx(const DevMap& m, idx_t i) { return *(const float*)((const char*)m.vx + (size_t)i); }
-  static __device__ __forceinline__ float ldy(const DevMap& m, idx_t i) { return *(const float*)((const char*)m.vx + (size_t)i + 2048); }
-  // SDF: the weight is a byte, 2048 + voxel bytes into the brick (se_device.h)
-  static __device__ __forceinline__ float ldyb(const DevMap& m, idx_t i) { return (float)*((const uint8_t*)m.vx + (size_t)((i & 0xFFFFF000u) + 2048u + SE_YB((i >> 2) & 511u))); }
-};
-template <> struct SeDense<false> {    // (block sum, local sum) in 32 bit each, widened at the load
-  struct idx_t { uint32_t blk, loc; };
-  static __device__ __forceinline__ idx_t tx(const DevMap&, uint32_t x) { return {x >> 3, x & 7u}; }
-  static __device__ __forceinline__ idx_t ty(const DevMap& m, uint32_t y) { return {(y >> 3) << m.leaf_level, (y & 7u) << 3}; }
-  static __device__ __forceinline__ idx_t tz(const DevMap& m, uint32_t z) { return {(z >> 3) << (2 * m.leaf_level), (z & 7u) << 6}; }
-  static __device__ __forceinline__ idx_t sum(idx_t a, idx_t b, idx_t c) { return {a.blk + b.blk + c.blk, a.loc + b.loc + c.loc}; }
-  static __device__ __forceinline__ float ldx(const DevMap& m, idx_t i) { return m.vx[((size_t)i.blk << 10) | i.loc]; }
-  static __device__ __forceinline__ float ldy(const DevMap& m, idx_t i) { return m.vx[(((size_t)i.blk << 10) | i.loc) + 512]; }
-  static __device__ __forceinline__ float ldyb(const DevMap& m, idx_t i) { return (float)*((const uint8_t*)m.vx + (((size_t)i.blk << 12) + 2048u + SE_YB(i.loc))); }
-};
-template <bool O32> struct SeCell { float fx, fy, fz; typename SeDense<O32>::idx_t vi[8]; bool inside; };
-// the interpolation cell of a point given in voxel units (Octree::interp, octree.hpp:541-563): fractions and the eight
-// corner indices; inside = the whole cell lies in the volume (else the caller takes se_interp_generic)
-template <bool O32>
-__device__ __forceinline__ SeCell<O32> se_cell_lean(const DevMap& m, f3 pos) {
-  typedef SeDense<O32> A;
-  SeCell<O32> cell;
-  const float flx = floorf(pos.x), fly = floorf(pos.y), flz = floorf(pos.z);
-  const int bx = se_cvt_hw(flx), by = se_cvt_hw(fly), bz = se_cvt_hw(flz);
-  cell.fx = pos.x - flx; cell.fy = pos.y - fly; cell.fz = pos.z - flz;
-  const int lx = max(bx, 0), ly = max(by, 0), lz = max(bz, 0);
-  const int top = m.size - 1;
-  cell.inside = max(max(lx, ly), lz) < top;
-  const typename A::idx_t X[2] = {A::tx(m, lx), A::tx(m, lx + 1)}, Y[2] = {A::ty(m, ly), A::ty(m, ly + 1)}, Z[2] = {A::tz(m, lz), A::tz(m, lz + 1)};
-#pragma unroll
-  for (int k = 0; k < 8; ++k) cell.vi[k] = A::sum(X[k & 1], Y[(k >> 1) & 1], Z[k >> 2]);
-  return cell;
-}
-template <bool O32>
-__device__ __forceinline__ float se_interp_lean(const DevMap& m, const FieldConst fc, f3 pos, BlkCache& c) {
-  const SeCell<O32> cell = se_cell_lean<O32>(m, pos);
-  if (!cell.inside) return se_interp_generic<true>(m, fc, pos, c);   // a corner outside the volume
-  float p[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) p[k] = SeDense<O32>::ldx(m, cell.vi[k]);
-  const float fx = cell.fx, fy = cell.fy, fz = cell.fz;
-  return (((p[0] * (1 - fx) + p[1] * fx) * (1 - fy) + (p[2] * (1 - fx) + p[3] * fx) * fy) * (1 - fz) +
-          ((p[4] * (1 - fx) + p[5] * fx) * (1 - fy) + (p[6] * (1 - fx) + p[7] * fx) * fy) * fz);
-}
-// Octree::grad on the dense grid (same terms and order as se_grad); falls back to the generic form when an index leaves the volume
-template <bool O32>
-__device__ __forceinline__ f3 se_grad_lean(const DevMap& m, const FieldConst fc, f3 pos, BlkCache& c) {
-  typedef SeDense<O32> A;
-  const float flx = floorf(pos.x), fly = floorf(pos.y), flz = floorf(pos.z);
-  const int bx = se_cvt_hw(flx), by = se_cvt_hw(fly), bz = se_cvt_hw(flz);
-  const int hi = m.size - 1;
-  if (!(bx <= hi && by <= hi && bz <= hi)) return se_grad_generic<true>(m, fc, pos, c);
-  const float fx = pos.x - flx, fy = pos.y - fly, fz = pos.z - flz;
-  const typename A::idx_t X[4] = {A::tx(m, max(bx - 1, 0)), A::tx(m, max(bx, 0)), A::tx(m, min(bx + 1, hi)), A::tx(m, min(bx + 2, hi))};
-  const typename A::idx_t Y[4] = {A::ty(m, max(by - 1, 0)), A::ty(m, max(by, 0)), A::ty(m, min(by + 1, hi)), A::ty(m, min(by + 2, hi))};
-  const typename A::idx_t Z[4] = {A::tz(m, max(bz - 1, 0)), A::tz(m, max(bz, 0)), A::tz(m, min(bz + 1, hi)), A::tz(m, min(bz + 2, hi))};
-  float V[4][4][4];
-#pragma unroll
-  for (int zi = 0; zi < 4; ++zi)
-#pragma unroll
-    for (int yi = 0; yi < 4; ++yi)
-#pragma unroll
-      for (int xi = 0; xi < 4; ++xi) {
-        const int central = (xi == 1 || xi == 2) + (yi == 1 || yi == 2) + (zi == 1 || zi == 2);
-        if (central < 2) continue;
-        V[zi][yi][xi] = A::ldx(m, A::sum(X[xi], Y[yi], Z[zi]));
-      }
-  f3 g;
-  g.x = (((V[1][1][2] - V[1][1][0]) * (1 - fx) + (V[1][1][3] - V[1][1][1]) * fx) * (1 - fy) +
-         ((V[1][2][2] - V[1][2][0]) * (1 - fx) + (V[1][2][3] - V[1][2][1]) * fx) * fy) * (1 - fz) +
-        (((V[2][1][2] - V[2][1][0]) * (1 - fx) + (V[2][1][3] - V[2][1][1]) * fx) * (1 - fy) +
-         ((V[2][2][2] - V[2][2][0]) * (1 - fx) + (V[2][2][3] - V[2][2][1]) * fx) * fy) * fz;
-  g.y = (((V[1][2][1] - V[1][0][1]) * (1 - fx) + (V[1][2][2] - V[1][0][2]) * fx) * (1 - fy) +
-         ((V[1][3][1] - V[1][1][1]) * (1 - fx) + (V[1][3][2] - V[1][1][2]) * fx) * fy) * (1 - fz) +
-        (((V[2][2][1] - V[2][0][1]) * (1 - fx) + (V[2][2][2] - V[2][0][2]) * fx) * (1 - fy) +
-         ((V[2][3][1] - V[2][1][1]) * (1 - fx) + (V[2][3][2] - V[2][1][2]) * fx) * fy) * fz;
-  g.z = (((V[2][1][1] - V[0][1][1]) * (1 - fx) + (V[2][1][2] - V[0][1][2]) * fx) * (1 - fy) +
-         ((V[2][2][1] - V[0][2][1]) * (1 - fx) + (V[2][2][2] - V[0][2][2]) * fx) * fy) * (1 - fz) +
-        (((V[3][1][1] - V[1][1][1]) * (1 - fx) + (V[3][1][2] - V[1][1][2]) * fx) * (1 - fy) +
-         ((V[3][2][1] - V[1][2][1]) * (1 - fx) + (V[3][2][2] - V[1][2][2]) * fx) * fy) * fz;
-  return g;
-}
-
-// leaf-grid entry (slot + 1) of block (bx, by, bz), 0 if it lies outside the volume or is not allocated.  Both layouts keep
-// the entry in tab[] (a dense brick grid also holds bricks of blocks that were never allocated: initValue() everywhere).
-__device__ __forceinline__ uint32_t se_query_block(const DevMap& m, int bx, int by, int bz) {
-  const int nb = m.size >> 3;
-  if (!((unsigned)bx < (unsigned)nb && (unsigned)by < (unsigned)nb && (unsigned)bz < (unsigned)nb)) return 0u;
-  const uint32_t e = m.tab[leaf_index(m, bx, by, bz)];
-  return e == SE_PENDING ? 0u : e;
-}
-
-// Octree::grad (octree.hpp:652-737) for a stencil that leaves the volume: every one of the 32 voxels is looked up on its own, a voxel outside the
-// volume or in a block that is not allocated reads initValue().x (Octree::get(x, y, z, cached) -> get_fine).  Same clamps, same term order as
-// se_grad_generic.
-__device__ __forceinline__ f3 se_grad_checked(const DevMap& m, const FieldConst fc, f3 pos) {
-  const float flx = floorf(pos.x), fly = floorf(pos.y), flz = floorf(pos.z);
-  const int bx = cvt_i32(flx), by = cvt_i32(fly), bz = cvt_i32(flz);
-  const float fx = pos.x - flx, fy = pos.y - fly, fz = pos.z - flz;
-  const int hi = m.size - 1;
-  const int X[4] = {max(bx - 1, 0), max(bx, 0), min(bx + 1, hi), min(bx + 2, hi)};
-  const int Y[4] = {max(by - 1, 0), max(by, 0), min(by + 1, hi), min(by + 2, hi)};
-  const int Z[4] = {max(bz - 1, 0), max(bz, 0), min(bz + 1, hi), min(bz + 2, hi)};
-  float V[4][4][4];
-#pragma unroll
-  for (int zi = 0; zi < 4; ++zi)
-#pragma unroll
-    for (int yi = 0; yi < 4; ++yi)
-#pragma unroll
-      for (int xi = 0; xi < 4; ++xi) {
-        const int central = (xi == 1 || xi == 2) + (yi == 1 || yi == 2) + (zi == 1 || zi == 2);
-        if (central < 2) continue;
-        const int x = X[xi], y = Y[yi], z = Z[zi];
-        const uint32_t e = in_volume(m, x, y, z) ? se_query_block(m, x >> 3, y >> 3, z >> 3) : 0u;
-        V[zi][yi][xi] = e ? m.vx[se_voxel_index(e, x, y, z)] : fc.init_x;
-      }
-  f3 g;
-  g.x = (((V[1][1][2] - V[1][1][0]) * (1 - fx) + (V[1][1][3] - V[1][1][1]) * fx) * (1 - fy) +
-         ((V[1][2][2] - V[1][2][0]) * (1 - fx) + (V[1][2][3] - V[1][2][1]) * fx) * fy) * (1 - fz) +
-        (((V[2][1][2] - V[2][1][0]) * (1 - fx) + (V[2][1][3] - V[2][1][1]) * fx) * (1 - fy) +
-         ((V[2][2][2] - V[2][2][0]) * (1 - fx) + (V[2][2][3] - V[2][2][1]) * fx) * fy) * fz;
-  g.y = (((V[1][2][1] - V[1][0][1]) * (1 - fx) + (V[1][2][2] - V[1][0][2]) * fx) * (1 - fy) +
-         ((V[1][3][1] - V[1][1][1]) * (1 - fx) + (V[1][3][2] - V[1][1][2]) * fx) * fy) * (1 - fz) +
-        (((V[2][2][1] - V[2][0][1]) * (1 - fx) + (V[2][2][2] - V[2][0][2]) * fx) * (1 - fy) +
-         ((V[2][3][1] - V[2][1][1]) * (1 - fx) + (V[2][3][2] - V[2][1][2]) * fx) * fy) * fz;
-  g.z = (((V[2][1][1] - V[0][1][1]) * (1 - fx) + (V[2][1][2] - V[0][1][2]) * fx) * (1 - fy) +
-         ((V[2][2][1] - V[0][2][1]) * (1 - fx) + (V[2][2][2] - V[0][2][2]) * fx) * fy) * (1 - fz) +
-        (((V[3][1][1] - V[1][1][1]) * (1 - fx) + (V[3][1][2] - V[1][1][2]) * fx) * (1 - fy) +
-         ((V[3][2][1] - V[1][2][1]) * (1 - fx) + (V[3][2][2] - V[1][2][2]) * fx) * fy) * fz;
-  return g;  // the caller applies (0.5f * dim / size)
-}
-
-// The normal at a hit (raycastKernel / renderVolumeKernel: volume.grad(hit)).  A hit can lie up to a voxel beyond an upper face of the volume
-// (floor(q) = size: the reference's `lower` index max(base, 0) is not clamped there and reads initValue()), outside the band se_grad is exact in;
-// there every voxel of the stencil is read by itself.  (Seen from beyond the +x / +y / +z faces, tests/test_gpu_beam_shell.py.)
-template <bool DENSE, bool O32 = false>
-__device__ __forceinline__ f3 se_hit_grad(const DevMap& m, const FieldConst fc, f3 q, BlkCache& c) {
-  const int hi = m.size - 1;
-  const int bx = cvt_i32(floorf(q.x)), by = cvt_i32(floorf(q.y)), bz = cvt_i32(floorf(q.z));
-  if (!(bx >= -1 && bx <= hi && by >= -1 && by <= hi && bz >= -1 && bz <= hi)) return se_grad_checked(m, fc, q);
-  return DENSE ? se_grad_lean<O32>(m, fc, q, c) : se_grad<DENSE>(m, fc, q, c);
-}
 // Walking through unobserved space (r04).  While the last value had weight 0 the reference's march takes `largestep` after `largestep` until a get()
 // returns a weight again; 43 % of all samples of a frame are such steps, most of them in blocks that were never allocated, and each pair of them
 // was a dependent memory round trip.  The next SE_MARCH_SKIP positions -- formed by the same float additions the loop performs -- are asked of the
@@ -1826,20 +1457,41 @@ __device__ __forceinline__ bool se_march_skip(const DevMap& m, const RayArgs& a,
   }
   return false;
 }
-// one get(): voxel coordinates, inside-the-volume flag and index of the sample at q (metres)
-template <bool O32> struct SeSample { typename SeDense<O32>::idx_t vi; bool in; };
-template <bool O32>
-__device__ __forceinline__ SeSample<O32> se_sample_lean(const DevMap& m, const RayArgs& a, f3 q) {
+// ---- brick-layout policies of the OFusion march -----------------------------------------------------------------------------------------------------
+// A policy names what differs between the layouts when the march reads the field, and nothing else: the sample type and the per-ray state, how a
+// sample is addressed, whether it has a brick, its x and float-y loads, the block hint an interp wants in BlkCache, and the interp itself.
+//   SeLayoutDense<true>    dense grid, 32-bit byte offsets (maps <= 4 GiB: 512^3)
+//   SeLayoutDense<false>   dense grid, (block, local) pairs
+//   SeLayoutPooled         bump-allocated bricks behind the leaf index (the north-star layout)
+// `interp` is a constant function pointer, not a wrapper: one more level of inlining changes the compiled kernels (profiles/march_fold_asm.txt).
+template <bool O32> struct SeLayoutDense {
   typedef SeDense<O32> A;
-  const int ix = se_cvt_hw(a.inv_voxel * q.x), iy = se_cvt_hw(a.inv_voxel * q.y), iz = se_cvt_hw(a.inv_voxel * q.z);
-  SeSample<O32> s;
-  s.in = (uint32_t)(ix | iy | iz) < (uint32_t)m.size;
-  const uint32_t ux = s.in ? (uint32_t)ix : 0u, uy = s.in ? (uint32_t)iy : 0u, uz = s.in ? (uint32_t)iz : 0u;   // (outside: voxel 0, value replaced)
-  s.vi = A::sum(A::tx(m, ux), A::ty(m, uy), A::tz(m, uz));
-  return s;
-}
-// raycast(const Volume<SDF>&, ...) (se_denseslam/src/kfusion/rendering_impl.hpp:34-74) on the dense grid; same float
-// operations in the same order as se_cast_ray's generic form below (which stays the path of pooled bricks)
+  typedef SeSample<O32> sample_t;
+  struct state_t {};
+  static __device__ __forceinline__ state_t state() { return {}; }
+  static __device__ __forceinline__ sample_t sample(const DevMap& m, const RayArgs& a, f3 q, state_t&) { return se_sample_lean<O32>(m, a.inv_voxel, q); }
+  static __device__ __forceinline__ bool has(const sample_t& s) { return s.in; }
+  static __device__ __forceinline__ float ldx(const DevMap& m, const sample_t& s) { return A::ldx(m, s.vi); }
+  static __device__ __forceinline__ float ldy(const DevMap& m, const sample_t& s) { return A::ldy(m, s.vi); }
+  static __device__ __forceinline__ void hint(BlkCache&, const sample_t&) {}
+  static constexpr auto interp = &se_interp_lean<O32>;
+};
+struct SeLayoutPooled {
+  typedef SePSample sample_t;
+  typedef SePCache state_t;
+  static __device__ __forceinline__ state_t state() { return {0xFFFFFFFFu, 0u}; }
+  static __device__ __forceinline__ sample_t sample(const DevMap& m, const RayArgs& a, f3 q, state_t& pc) { return se_sample_pooled(m, a.inv_voxel, q, pc, false); }
+  static __device__ __forceinline__ bool has(const sample_t& s) { return s.e != 0u; }
+  static __device__ __forceinline__ float ldx(const DevMap& m, const sample_t& s) { return m.vx[se_pooled_index(s)]; }
+  static __device__ __forceinline__ float ldy(const DevMap& m, const sample_t& s) { return m.vx[se_pooled_index(s) + 512]; }
+  static __device__ __forceinline__ void hint(BlkCache& c, const sample_t& s) { c.bx = s.bx; c.by = s.by; c.bz = s.bz; c.e = s.e; }   // the block of this sample as the look-up hint
+  static constexpr auto interp = &se_interp_generic<false>;
+};
+
+// raycast(const Volume<SDF>&, ...) (se_denseslam/src/kfusion/rendering_impl.hpp:34-74) on the dense grid.  The SDF march stays two functions, this
+// one and se_cast_ray_sdf_pooled: written once over the layout policy (as the OFusion march below is) the 32-bit-offset and the pooled kernels
+// compile to another schedule, and the stress stream at 512^3 measured 1.1 % slower, beyond the parent's spread (profiles/march_fold_asm.txt).
+// Any change to this loop is made in both.
 template <bool STATS, bool O32>
 __device__ __forceinline__ void se_cast_ray_sdf_lean(const DevMap& m, const RayArgs& a, const FieldConst fc, f3 org, f3 dir, float tnear, float tfar,
                                                      BlkCache& c, float& hx, float& hy, float& hz, float& hw, RayCounters& rc) {
@@ -1880,7 +1532,7 @@ __device__ __forceinline__ void se_cast_ray_sdf_lean(const DevMap& m, const RayA
     // in-band batch: fused launch 36.5 -> 39.0 us at 512^3, 17.3 k -> 16.6 k frames/s, stress stream -3.5 %: where the march creeps at the minimum step the
     // second sample IS consumed, and a batch of one doubles the loop's fixed cost there; profiles/r06j_band_solo_ab.log)
     const f3 q1 = f3_add(q0, f3_scale(S, dir));
-    SeSample<O32> s0 = se_sample_lean<O32>(m, a, q0), s1 = se_sample_lean<O32>(m, a, q1);
+    SeSample<O32> s0 = se_sample_lean<O32>(m, a.inv_voxel, q0), s1 = se_sample_lean<O32>(m, a.inv_voxel, q1);
     float x0, y0, x1, y1;
     bool probed = false;
     if constexpr (!O32) {
@@ -1925,9 +1577,7 @@ __device__ __forceinline__ void se_cast_ray_sdf_lean(const DevMap& m, const RayA
         f_tt = dx;
         if (f_tt < 0.1f && f_tt >= -0.5f) {   // (double)f_tt <= 0.1
           if (i == 0 && have0) {
-            const float fx = cell0.fx, fy = cell0.fy, fz = cell0.fz;
-            f_tt = (((cv0[0] * (1 - fx) + cv0[1] * fx) * (1 - fy) + (cv0[2] * (1 - fx) + cv0[3] * fx) * fy) * (1 - fz) +
-                    ((cv0[4] * (1 - fx) + cv0[5] * fx) * (1 - fy) + (cv0[6] * (1 - fx) + cv0[7] * fx) * fy) * fz);
+            f_tt = se_trilerp(cv0, cell0.fx, cell0.fy, cell0.fz);
           } else {
             f_tt = se_interp_lean<O32>(m, fc, f3_scale(a.inv_voxel, position), c);
           }
@@ -1949,35 +1599,7 @@ __device__ __forceinline__ void se_cast_ray_sdf_lean(const DevMap& m, const RayA
     hx = r.x; hy = r.y; hz = r.z; hw = t;
   }
 }
-// ---- the same for pooled bricks (the north-star layout: bump-allocated bricks behind the index).  A sample's block entry comes from
-// tab[]; while the march is in unobserved space it asks the leaf bitmap first, so that a block that was never allocated costs a bit test
-// in an L2-resident array instead of a line of the 8 / 64 MB leaf index.  The entry of the previous sample's block is kept (most steps
-// stay in or next to it).  interp / grad of a hit go through the generic forms (eight / 2x2x2 block look-ups), as before.
-struct SePSample { uint32_t e, loc; int bx, by, bz; };
-struct SePCache { uint32_t lin, e; };
-template <bool PROBE>
-__device__ __forceinline__ SePSample se_sample_pooled(const DevMap& m, const RayArgs& a, f3 q, SePCache& c, bool unobs) {
-  const int ix = se_cvt_hw(a.inv_voxel * q.x), iy = se_cvt_hw(a.inv_voxel * q.y), iz = se_cvt_hw(a.inv_voxel * q.z);
-  const bool in = (uint32_t)(ix | iy | iz) < (uint32_t)m.size;
-  SePSample s;
-  s.bx = ix >> 3; s.by = iy >> 3; s.bz = iz >> 3;
-  s.loc = ((uint32_t)ix & 7u) | (((uint32_t)iy & 7u) << 3) | (((uint32_t)iz & 7u) << 6);
-  s.e = 0u;
-  if (in) {
-    const uint32_t lin = block_linear(m, s.bx, s.by, s.bz);
-    if (lin == c.lin) s.e = c.e;
-    else {
-      bool present = true;
-      if (PROBE && unobs) present = (m.lbits[lin >> 5] >> (lin & 31u)) & 1u;
-      uint32_t e = 0u;
-      if (present) { e = m.tab[m.leaf_off + lin]; e = e == SE_PENDING ? 0u : e; }   // (PENDING: see se_block_entry)
-      c.lin = lin; c.e = e;
-      s.e = e;
-    }
-  }
-  return s;
-}
-__device__ __forceinline__ size_t se_pooled_index(const SePSample& s) { return ((size_t)(s.e ? s.e - 1u : 0u) << 10) | s.loc; }
+// the same on pooled bricks (se_sample_pooled); interp of a sample goes through se_interp_generic with the sample's block as the look-up hint
 template <bool STATS>
 __device__ __forceinline__ void se_cast_ray_sdf_pooled(const DevMap& m, const RayArgs& a, const FieldConst fc, f3 org, f3 dir, float tnear, float tfar,
                                                        BlkCache& c, float& hx, float& hy, float& hz, float& hw, RayCounters& rc) {
@@ -2000,7 +1622,7 @@ __device__ __forceinline__ void se_cast_ray_sdf_pooled(const DevMap& m, const Ra
     }
     const f3 q0 = position;
     const f3 q1 = f3_add(q0, f3_scale(S, dir));
-    const SePSample s0 = se_sample_pooled<true>(m, a, q0, pc, unobs), s1 = se_sample_pooled<true>(m, a, q1, pc, unobs);
+    const SePSample s0 = se_sample_pooled(m, a.inv_voxel, q0, pc, unobs), s1 = se_sample_pooled(m, a.inv_voxel, q1, pc, unobs);
     const size_t i0 = se_pooled_index(s0), i1 = se_pooled_index(s1);
     // (SDF weights are bytes, 2048 + voxel bytes into the brick: se_device.h)
     const uint8_t* yb = (const uint8_t*)m.vx;
@@ -2037,8 +1659,7 @@ __device__ __forceinline__ void se_cast_ray_sdf_pooled(const DevMap& m, const Ra
         f_tt = dx;
         if (f_tt < 0.1f && f_tt >= -0.5f) {   // (double)f_tt <= 0.1
           if (i == 0 && have0) {
-            f_tt = (((cv0[0] * (1 - cfx) + cv0[1] * cfx) * (1 - cfy) + (cv0[2] * (1 - cfx) + cv0[3] * cfx) * cfy) * (1 - cfz) +
-                    ((cv0[4] * (1 - cfx) + cv0[5] * cfx) * (1 - cfy) + (cv0[6] * (1 - cfx) + cv0[7] * cfx) * cfy) * cfz);
+            f_tt = se_trilerp(cv0, cfx, cfy, cfz);
           } else {
             c.bx = sm.bx; c.by = sm.by; c.bz = sm.bz; c.e = sm.e;      // the block of this sample as the look-up hint
             f_tt = se_interp_generic<false>(m, fc, f3_scale(a.inv_voxel, position), c);
@@ -2112,64 +1733,7 @@ __device__ __forceinline__ int se_of_leap(const RayArgs& a, f3 org, f3 dir, floa
   for (; i < K; ++i) t += a.step;
   return K > 0 ? K : 0;
 }
-template <bool STATS>
-__device__ __forceinline__ void se_cast_ray_of_pooled(const DevMap& m, const RayArgs& a, const FieldConst fc, f3 org, f3 dir, float tnear, float tfar,
-                                                      BlkCache& c, float& hx, float& hy, float& hz, float& hw, RayCounters& rc) {
-  if (!(tnear < tfar)) return;
-  float t = tnear;
-  const float stepsize = a.step;
-  float f_t = se_interp_generic<false>(m, fc, f3_scale(a.inv_voxel, f3_add(org, f3_scale_r(dir, t))), c);
-  if (STATS) ++rc.n_interp;
-  float f_tt = 0;
-  if (!(f_t <= 0.f)) return;
-  bool done = false, quiet = false;   // quiet: no sample of the last batch was observed
-  float leap_hold = 0.f;              // no leap test before t has reached this value (the check point the last test found blocked)
-  SePCache pc = {0xFFFFFFFFu, 0u};
-  for (int guard = 0; t < tfar && !done && guard < 65536; ++guard) {
-    ++rc.n_batch;
-    if (quiet && a.leap_bits && t >= leap_hold) {
-      if (se_of_leap(a, org, dir, tfar, t, leap_hold) > 0) { f_t = f_tt; if (!(t < tfar)) break; }
-    }
-    float tt[SE_SPEC_OF];
-    f3 q[SE_SPEC_OF];
-    SePSample sm[SE_SPEC_OF];
-    float qx[SE_SPEC_OF], qy[SE_SPEC_OF];
-    tt[0] = t;
-#pragma unroll
-    for (int i = 1; i < SE_SPEC_OF; ++i) tt[i] = tt[i - 1] + stepsize;
-#pragma unroll
-    for (int i = 0; i < SE_SPEC_OF; ++i) { q[i] = f3_add(org, f3_scale_r(dir, tt[i])); sm[i] = se_sample_pooled<false>(m, a, q[i], pc, false); }
-    quiet = (a.leap_bits ? se_leap_word(a, q[SE_SPEC_OF - 1]) : 1u) == 0u;   // (see se_cast_ray_of_lean)
-#pragma unroll
-    for (int i = 0; i < SE_SPEC_OF; ++i) { const size_t vi = se_pooled_index(sm[i]); qx[i] = m.vx[vi]; qy[i] = m.vx[vi + 512]; }
-    bool stop = false;
-#pragma unroll
-    for (int i = 0; i < SE_SPEC_OF; ++i) {
-      if (stop) continue;
-      t = tt[i];
-      if (!(t < tfar)) { done = true; stop = true; continue; }
-      if (STATS) ++rc.n_get;
-      const float dx = sm[i].e ? qx[i] : fc.init_x, dy = sm[i].e ? qy[i] : fc.init_y;
-      if (dx > -100.f && dy > 0.f) {
-        quiet = false;
-        c.bx = sm[i].bx; c.by = sm[i].by; c.bz = sm[i].bz; c.e = sm[i].e;
-        f_tt = se_interp_generic<false>(m, fc, f3_scale(a.inv_voxel, q[i]), c);
-        if (STATS) ++rc.n_interp;
-      }
-      if (f_tt > 0.f) { done = true; stop = true; continue; }
-      f_t = f_tt;
-    }
-    if (!stop) t = tt[SE_SPEC_OF - 1] + stepsize;
-  }
-  if (f_tt > 0.f) {
-    t = t - stepsize * (f_tt - 0.f) / (f_tt - f_t);
-    const f3 r = f3_add(org, f3_scale_r(dir, t));
-    hx = r.x; hy = r.y; hz = r.z; hw = t;
-  }
-}
-
-// raycast(const Volume<OFusion>&, ...) (se_denseslam/src/bfusion/rendering_impl.hpp:35-68) on the dense grid with the lean addressing
-// above; same float operations in the same order as the generic form in se_cast_ray
+// raycast(const Volume<OFusion>&, ...) (se_denseslam/src/bfusion/rendering_impl.hpp:35-68): same float operations in the same order
 // (r05, measured and dropped: once the values of a batch are here, fetching the interpolation corners of the samples that want them two / four samples per
 // round trip instead of one -- aimed at batches inside observed blocks, 3.6 us each on the per-wave timeline once the leap had removed the empty-space
 // batches: 84 / 164 bytes of scratch per lane under the 96-register budget and interpolations behind a hit: fused launch 72.5 -> 107 / 115 us.
@@ -2179,19 +1743,19 @@ __device__ __forceinline__ void se_cast_ray_of_pooled(const DevMap& m, const Ray
 // images, and the fused launch 69.6 -> 128 / 111 us at 512^3, the stress stream 89 -> 180 / 146 us: the lanes of a wave are in the two modes at different
 // times, every trip of the loop then runs both bodies, and a short batch advances its lanes a quarter as far.  With the switch made per wave (short batches
 // while >= 16 / 32 / 40 lanes are inside observed space) 75.9 - 78.7 us: still behind.  profiles/r06q_of_observed_batch_ab.log)
-template <bool STATS, bool O32>
-__device__ __forceinline__ void se_cast_ray_of_lean(const DevMap& m, const RayArgs& a, const FieldConst fc, f3 org, f3 dir, float tnear, float tfar,
-                                                    BlkCache& c, float& hx, float& hy, float& hz, float& hw, RayCounters& rc) {
-  typedef SeDense<O32> A;
+template <bool STATS, typename L>
+__device__ __forceinline__ void se_cast_ray_of(const DevMap& m, const RayArgs& a, const FieldConst fc, f3 org, f3 dir, float tnear, float tfar,
+                                               BlkCache& c, float& hx, float& hy, float& hz, float& hw, RayCounters& rc) {
   if (!(tnear < tfar)) return;
   float t = tnear;
   const float stepsize = a.step;
-  float f_t = se_interp_lean<O32>(m, fc, f3_scale(a.inv_voxel, f3_add(org, f3_scale_r(dir, t))), c);
+  float f_t = L::interp(m, fc, f3_scale(a.inv_voxel, f3_add(org, f3_scale_r(dir, t))), c);
   if (STATS) ++rc.n_interp;
   float f_tt = 0;
   if (!(f_t <= 0.f)) return;
   bool done = false, quiet = false;   // quiet: no sample of the last batch was observed
   float leap_hold = 0.f;              // no leap test before t has reached this value (the check point the last test found blocked)
+  typename L::state_t st = L::state();
   for (int guard = 0; t < tfar && !done && guard < 65536; ++guard) {
     ++rc.n_batch;
     if (quiet && a.leap_bits && t >= leap_hold) {
@@ -2199,18 +1763,18 @@ __device__ __forceinline__ void se_cast_ray_of_lean(const DevMap& m, const RayAr
     }
     float tt[SE_SPEC_OF];
     f3 q[SE_SPEC_OF];
-    SeSample<O32> sm[SE_SPEC_OF];
+    typename L::sample_t sm[SE_SPEC_OF];
     float qx[SE_SPEC_OF], qy[SE_SPEC_OF];
     tt[0] = t;
 #pragma unroll
     for (int i = 1; i < SE_SPEC_OF; ++i) tt[i] = tt[i - 1] + stepsize;
 #pragma unroll
-    for (int i = 0; i < SE_SPEC_OF; ++i) { q[i] = f3_add(org, f3_scale_r(dir, tt[i])); sm[i] = se_sample_lean<O32>(m, a, q[i]); }
+    for (int i = 0; i < SE_SPEC_OF; ++i) { q[i] = f3_add(org, f3_scale_r(dir, tt[i])); sm[i] = L::sample(m, a, q[i], st); }
     // (the leap is only tried from block-free space: the batch's last sample asks the dilated grid along with the values -- a quiet batch inside
     // allocated, unobserved blocks would otherwise pay a test that cannot succeed, batch after batch: r05an)
     const uint32_t lw = a.leap_bits ? se_leap_word(a, q[SE_SPEC_OF - 1]) : 1u;
 #pragma unroll
-    for (int i = 0; i < SE_SPEC_OF; ++i) { qx[i] = A::ldx(m, sm[i].vi); qy[i] = A::ldy(m, sm[i].vi); }
+    for (int i = 0; i < SE_SPEC_OF; ++i) { qx[i] = L::ldx(m, sm[i]); qy[i] = L::ldy(m, sm[i]); }
     quiet = lw == 0u;
     bool stop = false;
 #pragma unroll
@@ -2219,10 +1783,12 @@ __device__ __forceinline__ void se_cast_ray_of_lean(const DevMap& m, const RayAr
       t = tt[i];
       if (!(t < tfar)) { done = true; stop = true; continue; }
       if (STATS) ++rc.n_get;
-      const float dx = sm[i].in ? qx[i] : fc.init_x, dy = sm[i].in ? qy[i] : fc.init_y;
+      const bool ok = L::has(sm[i]);
+      const float dx = ok ? qx[i] : fc.init_x, dy = ok ? qy[i] : fc.init_y;
       if (dx > -100.f && dy > 0.f) {
         quiet = false;
-        f_tt = se_interp_lean<O32>(m, fc, f3_scale(a.inv_voxel, q[i]), c);
+        L::hint(c, sm[i]);
+        f_tt = L::interp(m, fc, f3_scale(a.inv_voxel, q[i]), c);
         if (STATS) ++rc.n_interp;
       }
       if (f_tt > 0.f) { done = true; stop = true; continue; }
@@ -2240,10 +1806,10 @@ __device__ __forceinline__ void se_cast_ray_of_lean(const DevMap& m, const RayAr
 template <bool OFUSION, bool STATS, bool DENSE, bool O32 = false>
 __device__ __forceinline__ void se_cast_ray(const DevMap& m, const RayArgs& a, const FieldConst fc, f3 org, f3 dir, float t_min, float tfar,
                                             BlkCache& c, float& hx, float& hy, float& hz, float& hw, RayCounters& rc) {
-  if (!OFUSION && DENSE) se_cast_ray_sdf_lean<STATS, O32>(m, a, fc, org, dir, t_min, tfar, c, hx, hy, hz, hw, rc);
-  else if (OFUSION && DENSE) se_cast_ray_of_lean<STATS, O32>(m, a, fc, org, dir, t_min, tfar, c, hx, hy, hz, hw, rc);
-  else if (!OFUSION) se_cast_ray_sdf_pooled<STATS>(m, a, fc, org, dir, t_min, tfar, c, hx, hy, hz, hw, rc);
-  else se_cast_ray_of_pooled<STATS>(m, a, fc, org, dir, t_min, tfar, c, hx, hy, hz, hw, rc);
+  typedef std::conditional_t<DENSE, SeLayoutDense<O32>, SeLayoutPooled> L;
+  if constexpr (OFUSION) se_cast_ray_of<STATS, L>(m, a, fc, org, dir, t_min, tfar, c, hx, hy, hz, hw, rc);
+  else if constexpr (DENSE) se_cast_ray_sdf_lean<STATS, O32>(m, a, fc, org, dir, t_min, tfar, c, hx, hy, hz, hw, rc);
+  else se_cast_ray_sdf_pooled<STATS>(m, a, fc, org, dir, t_min, tfar, c, hx, hy, hz, hw, rc);
 }
 
 // ---- beam start (r05) ------------------------------------------------------------------------------------------------------------
@@ -2563,19 +2129,8 @@ __global__ void k_depth_from_host(DepthSrc ds, int ow, int oh) {
 // ray_iterator's tmin() / tmax() (ray_iterator.hpp:53-102, 232-240): entry / exit of the volume cube
 // clamped to the near / far planes -- what renderVolumeKernel uses (it does not advance to a leaf)
 __device__ __forceinline__ RaySpan se_ray_range(const DevMap& m, const RayArgs& a, f3 origin, f3 direction) {
-  const float eps = a.epsilon;
-  f3 d;
-  d.x = fabsf(direction.x) < eps ? copysignf(eps, direction.x) : direction.x;
-  d.y = fabsf(direction.y) < eps ? copysignf(eps, direction.y) : direction.y;
-  d.z = fabsf(direction.z) < eps ? copysignf(eps, direction.z) : direction.z;
-  const f3 scaled_origin = f3_add(f3_div(origin, m.dim), {1.f, 1.f, 1.f});
-  const f3 t_coef = f3_scale(-1.f, {1.f / fabsf(d.x), 1.f / fabsf(d.y), 1.f / fabsf(d.z)});
-  f3 t_bias = f3_mul(t_coef, scaled_origin);
-  if (d.x > 0.0f) t_bias.x = 3.0f * t_coef.x - t_bias.x;
-  if (d.y > 0.0f) t_bias.y = 3.0f * t_coef.y - t_bias.y;
-  if (d.z > 0.0f) t_bias.z = 3.0f * t_coef.z - t_bias.z;
-  float t_min = fmaxf(fmaxf(2.0f * t_coef.x - t_bias.x, 2.0f * t_coef.y - t_bias.y), 2.0f * t_coef.z - t_bias.z);
-  float t_max = fminf(fminf(t_coef.x - t_bias.x, t_coef.y - t_bias.y), t_coef.z - t_bias.z);
+  const SeRaySetup rs = se_ray_setup(a, direction, [&]() -> f3 { return f3_add(f3_div(origin, m.dim), {1.f, 1.f, 1.f}); });
+  float t_min = rs.t_in, t_max = rs.t_out;
   t_min = fmaxf(t_min, a.nearp / m.dim);
   t_max = fminf(t_max, a.farp / m.dim);
   return {t_min * m.dim, t_max * m.dim, 0};

@@ -3,7 +3,7 @@
 // get(p) = Octree::get_fine, operator[](p) = Octree::get (coarse node value where no block exists), interp(p, x) and grad(p, x).
 //
 // One thread per point, grid-stride loop over int64 n, wave64 workgroups.  interp / grad are the raycast's own inline
-// se_interp / se_grad (bit-exact with Octree::interp / Octree::grad); the coarse walk is the index pyramid read top-down.
+// forms of se_sample.h (bit-exact with Octree::interp / Octree::grad); the coarse walk is the index pyramid read top-down.
 // Voxel coordinates: q = s * p per axis (s = (float)size / dim), v = (int)q (truncation, VolumeTemplate::get / operator[]).
 // A point with a non-finite q or |q| >= 2^20 on any axis gets the defaults (status 0, initValue() for fine and coarse,
 // empty().x for interp, 0 for grad) and touches no map memory; see se_hip.h for the full definition of every output.
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(SE_WG_QUERY) void k_query_points(DevMap m, const fl
         }
       }
       if (o.status) {
-        // the interpolation cell of se_interp / Octree::interp: corners lower .. lower + 1 per axis, lower = max(floor(q), 0)
+        // the interpolation cell of se_interp_generic / Octree::interp: corners lower .. lower + 1 per axis, lower = max(floor(q), 0)
         const int lx = max(cvt_i32(floorf(q.x)), 0), ly = max(cvt_i32(floorf(q.y)), 0), lz = max(cvt_i32(floorf(q.z)), 0);
         const bool cx = (lx & 7) == 7, cy = (ly & 7) == 7, cz = (lz & 7) == 7;
         bool all = true;
@@ -78,13 +78,13 @@ __global__ __launch_bounds__(SE_WG_QUERY) void k_query_points(DevMap m, const fl
         st |= all ? SE_Q_OBSERVED : 0u;
       }
       BlkCache c = {-1, -1, -1, 0u};
+      // On the dense grid se_interp / se_grad are the lean forms, which convert float -> int with the hardware instruction (se_cvt_hw) where the generic
+      // ones convert as cvttss2si does (cvt_i32): the two agree for non-NaN |f| < 2^31, and |q| < SE_QUERY_LIMIT = 2^20 on every axis here.
       if (o.interp) ip = se_interp<DENSE>(m, fc, q, c);
       if (o.grad) {
-        // se_grad (both forms) takes the stencil's voxels from the blocks of its two extreme clamped coordinates per axis, which holds while
-        // -1 <= floor(q) <= size - 1 on every axis.  Outside that band se_grad_checked (se_kernels.h) reads each voxel by itself.
         const int hi = m.size - 1;
         const int bx = cvt_i32(floorf(q.x)), by = cvt_i32(floorf(q.y)), bz = cvt_i32(floorf(q.z));
-        const bool band = bx >= -1 && bx <= hi && by >= -1 && by <= hi && bz >= -1 && bz <= hi;
+        const bool band = SE_GRAD_BAND(bx, by, bz, hi);   // outside it se_grad_checked reads each voxel by itself (se_sample.h)
         g = f3_scale(grad_scale, band ? se_grad<DENSE>(m, fc, q, c) : se_grad_checked(m, fc, q));
       }
     }

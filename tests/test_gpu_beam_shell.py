@@ -4,7 +4,7 @@ That shell test once accepted only the cells beyond the lower faces: from outsid
 the blocks there (the CPU model of the same arithmetic, ray by ray: tests/test_first_leaf_equivalence.py::test_beam_start_from_beyond_every_face).
 Here the HIP path renders the same sweep of cameras -- the eager raycast, the deferred one that rides in the next frame's fused k_raycast_scan, a
 pooled map, and the three settings of the beam-start knob -- and every image must be the oracle's.  The sweep also reaches hits up to a voxel
-beyond an upper face, whose normals need the per-voxel gradient (se_hit_grad, se_kernels.h)."""
+beyond an upper face, whose normals need the per-voxel gradient (se_hit_grad, se_sample.h)."""
 import numpy as np
 import pytest
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Register / scratch / occupancy of the hot kernels as hipcc reports them (-Rpass-analysis=kernel-resource-usage), without a GPU:
-  tools/kernel_resources.py [extra -D flags]     -> one line per instantiation of the scan, sweep, raycast and meshing kernels"""
+  tools/kernel_resources.py [extra -D flags]     -> one line per instantiation of the scan, sweep, raycast, query and meshing kernels"""
 import os
 import re
 import subprocess
@@ -23,7 +23,7 @@ def main():
     dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.splitlines()
     for (name, v, a, s, sc, occ, lds), d in zip(rows, dem):
         d = re.sub(r"\(.*", "", d).replace("void ", "")
-        if any(k in d for k in ("k_alloc_scan", "k_raycast", "k_integrate", "k_icp", "k_alloc_commit", "k_occ_commit", "k_cast_rays", "k_mesh", "k_edit", "k_alloc_boxes", "k_collide_boxes", "k_collide_motions", "k_clearance_boxes", "k_shift")):
+        if any(k in d for k in ("k_alloc_scan", "k_raycast", "k_integrate", "k_icp", "k_alloc_commit", "k_occ_commit", "k_cast_rays", "k_render_volume", "k_query_points", "k_mesh", "k_edit", "k_alloc_boxes", "k_collide_boxes", "k_collide_motions", "k_clearance_boxes", "k_shift")):
             print(f"{d:<60} VGPR {v:>3} AGPR {a:>3} SGPR {s:>3} scratch {sc:>4} occ {occ} lds {lds}")
 
 
