@@ -14,6 +14,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstring>
+#include <memory>
 #include <thread>
 #include <numeric>
 #include <string>
@@ -37,6 +38,12 @@ namespace {
 
 thread_local std::string g_err;
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
+
+}  // namespace
+
+#include "se_host_resources.h"   // (the owners report through fail())
+
+namespace {
 
 #define HIP_TRY(expr)                                                                             \
   do {                                                                                            \
@@ -70,7 +77,12 @@ void mul3(const float r[9], const float v[3], float out[3]) {
   out[2] = (r[6] * v[0] + r[7] * v[1]) + r[8] * v[2];
 }
 
-struct TimedLaunch { int kernel; hipEvent_t start, stop; };
+struct TimedLaunch { int kernel; Event start, stop; };
+// timing only: without the system-scope fence a record would otherwise put between the kernels it brackets
+constexpr unsigned kTimingEvent = hipEventDisableSystemFence;
+// these only order streams of one device against each other: no system-scope fence (its cache write-back / invalidate sits between the sweep
+// and the raycast otherwise), no timing
+constexpr unsigned kOrderEvent = hipEventDisableTiming | hipEventDisableSystemFence;
 
 // spin-wait hint, portable (the host side must also build on aarch64 hosts)
 inline void cpu_relax() {
@@ -103,18 +115,17 @@ template <typename F> bool spin_until(F done, long long limit_us) {
 struct se_hip_pipeline {
   se_hip_config cfg;
   int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+  // (the streams come first: they are released last, se_host_resources.h.  Every pointer below that is not an owner says whose memory it is.)
+  Stream stream;               // the handle's own, or the caller's after se_hip_set_stream
   // side stream: the allocation scan (and the depth upload feeding it) of frame f+1 runs here,
   // concurrently with the raycast of frame f on `stream`
-  hipStream_t side = nullptr;
-  bool own_side = false;       // false after se_hip_set_scan_stream handed one in
-  hipEvent_t ev_sweep = nullptr, ev_scan = nullptr;
-  hipEvent_t ev_edit = nullptr;   // se_hip_edit_boxes, se_hip_allocate_boxes: recorded behind the call so that a later scan on the side stream waits for it; created on first use
+  Stream side;                 // the handle's own, or the caller's after se_hip_set_scan_stream handed one in
+  Event ev_sweep{kOrderEvent}, ev_scan{kOrderEvent};
+  Event ev_edit{kOrderEvent};   // se_hip_edit_boxes, se_hip_allocate_boxes: recorded behind the call so that a later scan on the side stream waits for it; created on first use
   bool overlap = false;
   // host gate (see RayArgs::gate): replaces the event between the sweep and the next frame's scan for unsharded replicas
   bool host_gate = false;
-  uint32_t* gate_host = nullptr;   // pinned word the raycast kernel writes its sequence number to
+  PinnedBuf<uint32_t> gate_host;   // pinned word the raycast kernel writes its sequence number to
   uint32_t ray_seq = 0;            // raycast launches so far
   uint32_t gate_target = 0;        // sequence number of the first raycast behind the last sweep
   bool gate_armed = false;         // a sweep was enqueued that no scan / upload has waited for yet
@@ -133,7 +144,7 @@ struct se_hip_pipeline {
   bool pinned_input = false;   // se_hip_set_pinned_input: page-locked caller images are read in place
   // dense grid: the block list kept (mostly) in address order, see sort_block_list
   int sort_every = 0;           // 0 = off
-  uint32_t* bpos_sorted = nullptr; void* sort_tmp = nullptr; size_t sort_tmp_bytes = 0, sort_cap = 0;
+  DevBuf<uint32_t> bpos_sorted; DevBuf<> sort_tmp; size_t sort_tmp_bytes = 0, sort_cap = 0;   // (the sizes: set once both buffers exist)
   uint32_t sorted_n = 0; int sweeps_since_sort = 0;
   bool ptrs_exposed = false;   // sticky: se_hip_vertex_normal_device handed out vertex_ / normal_ of a handle without an image ring
   float pend_pose[16] = {0}, pend_k[4] = {0}, pend_mu = 0.f;
@@ -142,39 +153,44 @@ struct se_hip_pipeline {
   bool images_complete = true; // vertex_ / normal_ hold every row of the last raycast (a row-sharded replica: only after se_hip_apply_image_tiles / se_hip_gather_images)
   bool scan_pending = false;   // a scan was enqueued on `side` and not yet joined by `stream`
   bool scan_on_side = false;   // stream the LAST allocation scan ran on: se_hip_alloc_exchange / se_hip_alloc_commit follow it
-  const float* scaled0 = nullptr;   // scaled_depth_[0] of the last se_hip_track
+  const float* scaled0 = nullptr;   // scaled_depth_[0] of the last se_hip_track (alias of pyr_depth[0])
   // direct RCCL exchange of the key lists (se_hip_set_exchange): the caller's communicator and ncclAllGather
   void* xcomm = nullptr;
   int (*xgather)(const void*, void*, size_t, int, void*, hipStream_t) = nullptr;
   int xworld = 0;
   // sharded sweep (se_hip_set_sweep_shard): owner-computes + brick exchange instead of the replicated sweep
   int shard_world = 0, shard_rank = 0;
-  unsigned char* shard_send = nullptr;   // caller's send segment
+  unsigned char* shard_send = nullptr;   // caller's send segment (not owned)
   size_t shard_cap = 0;                  // bricks per segment
   bool mc_table_ready = false;   // SE_MC_TRI uploaded to constant memory
-  unsigned long long* mesh_ctr = nullptr;
+  DevBuf<unsigned long long> mesh_ctr;
   // Device staging of the _host entries of the batched queries (points, boxes, rays, per-block meshes): the caller's input and the outputs, grown on
   // demand (reserve_staging).  One buffer serves them all because no two are ever in use at once: a handle has one caller thread at a time
   // (include/se_hip.h) and every _host entry synchronises the stream before it returns.  A host entry that returned with work in flight would break that.
-  unsigned char* staging = nullptr;
-  size_t staging_cap = 0;
-  unsigned char* meshb_dev = nullptr;   // se_hip_mesh_blocks: view planes [20][64] floats, then the reservation state (3 x uint64); allocated on first use
+  DevBuf<> staging;
+  DevBuf<> meshb_dev;   // se_hip_mesh_blocks: view planes [20][64] floats, then the reservation state (3 x uint64); allocated on first use
   bool filter_input = false;   // preprocessing(..., filterInput): tracking sees the bilateral-filtered depth
   bool occ_commit_due = false; // the next sweep kernel must publish the scan's occupancy bits
   OccLists occ_lists{nullptr, 0, 0};   // ... of these key lists (own list, or every rank's after se_hip_alloc_commit)
   // tracking
   float raycast_pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // column-major, pose of the last raycast
-  std::vector<float*> pyr_depth, pyr_vertex, pyr_normal;  // level 0 depth aliases the current depth image
-  TrackData* track = nullptr;
-  float* reduce_partial = nullptr;   // 8 x SE_TRACK_SEGMENTS x 32 partial sums of the running ICP iteration
-  IcpState* icp = nullptr;           // device: what one ICP iteration hands to the next (two copies: launch j reads [j & 1], writes [(j + 1) & 1])
-  IcpHostRecord* icp_host = nullptr; // pinned: the one record the host reads per tracked frame
+  std::vector<DevBuf<float>> pyr_depth, pyr_vertex, pyr_normal;  // level 0 depth aliases the current depth image
+  DevBuf<TrackData> track;
+  DevBuf<float> reduce_partial;      // 8 x SE_TRACK_SEGMENTS x 32 partial sums of the running ICP iteration
+  DevBuf<IcpState> icp;              // device: what one ICP iteration hands to the next (two copies: launch j reads [j & 1], writes [(j + 1) & 1])
+  PinnedBuf<IcpHostRecord> icp_host; // pinned: the one record the host reads per tracked frame
   unsigned reduce_seq = 0;
   int track_iterations = 0;
   int icp_lookahead = 2;             // launches of a level the host stays ahead of the device (0: all iterations enqueued up front; se_hip_track)
   bool scan_on_main_once = false;    // se_hip_frame_tracked: this frame's scan follows the ICP on the main stream (nothing to overlap with)
-  unsigned char* rgbw = nullptr;   // render target (W*H*4)
+  DevBuf<> rgbw;   // render target (W*H*4)
+  // The map: `map` is the plain struct the kernels take; its pointers are assigned once, in se_hip_create, from the owners behind it (map.newkeys
+  // again wherever a key list is swapped in: the handle's two lists below, or the caller's of se_hip_set_new_keys_buffer, which is not owned)
   DevMap map{};
+  DevBuf<uint32_t> m_tab, m_occ, m_lbits, m_cbits, m_fbits, m_bpos, m_npos, m_ctr;
+  DevBuf<float> m_vx, m_nx, m_ny;
+  DevBuf<uint8_t> m_bactive, m_nlevel;
+  DevBuf<unsigned long long> m_stats;
   int leaf_level = 0, max_level = 0;
   size_t tab_entries = 0;
   size_t occ_words = 0, lbits_words = 0, cbits_words = 0, fbits_words = 0;
@@ -183,7 +199,7 @@ struct se_hip_pipeline {
   size_t slots = 0;
   size_t cap_blocks = 0, cap_nodes = 0;
   int ray_cache_levels = -1;  // -1: choose automatically
-  const float* depth = nullptr;     // what the kernels read: a slot of the handle's own ring or the caller's device image (se_hip_set_depth_device)
+  const float* depth = nullptr;     // what the kernels read: a slot of the handle's own ring or the caller's device image (se_hip_set_depth_device); an alias, never owned
   // Host input (se_hip_upload_depth / se_hip_upload_depth_mm; r06): the caller's image is copied into a slot of a ring of pinned host buffers -- the call
   // returns when the caller's buffer has been read, as the reference's synchronous preprocessing() does -- and NOTHING is enqueued: the first kernel that
   // needs float_depth_ reads the pinned image over PCIe and writes the matching slot of the device ring (DepthSrc, se_kernels.h): the frame's allocation
@@ -191,46 +207,45 @@ struct se_hip_pipeline {
   // no wait for the previous sweep: slot i is reused kIn uploads later, once a raycast enqueued behind the last sweep that read it has started (the
   // host gate's sequence word; without a host gate: an event recorded behind that sweep).
   static constexpr int kIn = 3;
-  float* depth_ring[kIn] = {nullptr, nullptr, nullptr};   // device, width*height floats each
-  void* in_host[kIn] = {nullptr, nullptr, nullptr};       // pinned
-  size_t in_cap = 0;
+  DevBuf<float> depth_ring[kIn];   // device, width*height floats each
+  PinnedBuf<> in_host[kIn];        // pinned
+  size_t in_cap = 0;               // bytes every slot of in_host is known to hold (0 while they are being replaced)
   int in_next = 0;
   int in_state[kIn] = {0, 0, 0};            // 0 free, 1 read by enqueued work that no raycast launch has followed yet, 2 followed: reusable once gate_host reaches in_seq
   uint32_t in_seq[kIn] = {0, 0, 0};
-  hipEvent_t in_done[kIn] = {nullptr, nullptr, nullptr};   // handles without a host gate
+  Event in_done[kIn] = {Event(hipEventDisableTiming), Event(hipEventDisableTiming), Event(hipEventDisableTiming)};   // handles without a host gate; created on first use
   bool in_event[kIn] = {false, false, false};
   int cur_in = -1;                          // ring slot p->depth points into (-1: the caller's device image)
   DepthSrc in_pending{nullptr, nullptr, 0, 0, 0};   // host-resident input not yet materialised on the device
   float* vertex = nullptr;       // vertex_ / normal_ as every consumer (tracking, rendering, the getters) sees them: the images of the LAST raycast
   float* normal = nullptr;       // launched -- the handle's own buffers, or the slot of the image ring that raycast wrote
-  float* vertex_own = nullptr;
-  float* normal_own = nullptr;
-  float* ring = nullptr;         // se_hip_set_image_ring: slot s = [vertex W*H*3 floats][normal W*H*3 floats] at ring + s * 2 * W*H*3
+  DevBuf<float> vertex_own, normal_own;   // (`vertex` / `normal` above are aliases: of these, or of a slot of the caller's ring)
+  float* ring = nullptr;         // se_hip_set_image_ring (the caller's, not owned): slot s = [vertex W*H*3 floats][normal W*H*3 floats] at ring + s * 2 * W*H*3
   int ring_slots = 0;
   int64_t n_launch[SE_HIP_K_COUNT + 1] = {0};   // kernel launches per kind since the last reset, counted on the host (no events needed); [SE_HIP_K_COUNT] = fused
-  float* bspline = nullptr;
-  float* logodds = nullptr;
-  unsigned long long* chain = nullptr;  // 3 candidates for the keys[0] quirk
-  unsigned long long* newkeys_own = nullptr;    // the handle's own key lists: two, used alternately by successive scans; the sweep
-  unsigned long long* newkeys_own2 = nullptr;   // kernel of a frame clears the count word of the list the next scan will use
+  DevBuf<float> bspline, logodds;
+  DevBuf<unsigned long long> chain;  // 3 candidates for the keys[0] quirk
+  DevBuf<unsigned long long> newkeys_own;    // the handle's own key lists: two, used alternately by successive scans; the sweep
+  DevBuf<unsigned long long> newkeys_own2;   // kernel of a frame clears the count word of the list the next scan will use
   unsigned long long cap_keys_own = 0;
   int own_next = 0;                             // which own list the next scan appends to
   bool own_clean[2] = {false, false};           // its count word is known to be zero (cleared by a sweep or a memset, not used since)
-  uint32_t* ctr_host = nullptr;         // pinned
+  PinnedBuf<uint32_t> ctr_host;         // pinned
   bool timing = false, stats = false;
   std::vector<TimedLaunch> pending;
-  std::vector<hipEvent_t> event_pool;
+  std::vector<Event> event_pool;
+  std::string timing_err;               // a timing event could not be created (that launch went untimed): reported by se_hip_get_timings
   double ms_sum[SE_HIP_K_COUNT] = {0};
   int64_t launches[SE_HIP_K_COUNT] = {0};
   int row_begin = 0, row_end = 0;
   int integ_grid = 0;  // > 0: fixed number of workgroups for the integration sweep (tuning knob)
   size_t shift_keep_bytes = (size_t)64 << 20;   // se_hip_shift_map releases a staging buffer larger than this when it returns; SE_HIP_SHIFT_KEEP_MIB (A/B knob)
   bool ieee_sweep = false;   // SE_HIP_IEEE_SWEEP=1: never select the shared-reciprocal sweep (k_integrate<.., FAST = false, ..>)
-  unsigned short* tile_cost = nullptr;   // raycast scheduling hint: per wave tile, cost in the previous launch (see RayArgs)
-  int* prio_thr = nullptr;               // its three priority thresholds (device; written by the integration sweep)
+  DevBuf<unsigned short> tile_cost;      // raycast scheduling hint: per wave tile, cost in the previous launch (see RayArgs)
+  DevBuf<int> prio_thr;                  // its three priority thresholds (device; written by the integration sweep)
   bool prio_hint = true;                 // SE_HIP_PRIO=0 switches the hint off
   int prio_permille[3] = {400, 150, 50}; // share of the tiles raised to priority >= 1 / >= 2 / 3 (SE_HIP_PRIO_SHARE="a,b,c", per mille)
-  uint32_t* ray_order = nullptr;   // raycast schedule: the workgroups' tile pairs by descending previous cost (RayArgs::ray_order)
+  DevBuf<uint32_t> ray_order;      // raycast schedule: the workgroups' tile pairs by descending previous cost (RayArgs::ray_order)
   int n_cus = 256;
 };
 
@@ -238,21 +253,22 @@ namespace {
 
 int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
-hipEvent_t get_event(se_hip_pipeline* p) {
-  if (!p->event_pool.empty()) { hipEvent_t e = p->event_pool.back(); p->event_pool.pop_back(); return e; }
-  hipEvent_t e;
-  // timing only: without the system-scope fence a record would otherwise put between the kernels it brackets
-  hipEventCreateWithFlags(&e, hipEventDisableSystemFence);
-  return e;
+int get_event(se_hip_pipeline* p, Event& e) {
+  if (!p->event_pool.empty()) { e = std::move(p->event_pool.back()); p->event_pool.pop_back(); return SE_HIP_OK; }
+  return e.create("(timing)");
 }
 struct ScopedTimer {
-  se_hip_pipeline* p; int k; hipStream_t s; hipEvent_t a{}, b{};
+  se_hip_pipeline* p; int k; hipStream_t s; Event a{kTimingEvent}, b{kTimingEvent}; bool timed = false;
   ScopedTimer(se_hip_pipeline* p_, int k_, hipStream_t s_ = nullptr) : p(p_), k(k_), s(s_ ? s_ : p_->stream) {
     p->n_launch[k]++;
-    if (p->timing) { a = get_event(p); b = get_event(p); hipEventRecord(a, s); }
+    if (p->timing) {
+      // (a constructor has nowhere to return a code to: the launch goes ahead untimed and se_hip_get_timings reports why)
+      timed = get_event(p, a) == SE_HIP_OK && get_event(p, b) == SE_HIP_OK;
+      if (timed) hipEventRecord(a, s); else p->timing_err = g_err;
+    }
   }
   ~ScopedTimer() {
-    if (p->timing) { hipEventRecord(b, s); p->pending.push_back({k, a, b}); }
+    if (timed) { hipEventRecord(b, s); p->pending.push_back({k, std::move(a), std::move(b)}); }
   }
 };
 void drain_timings(se_hip_pipeline* p) {
@@ -262,8 +278,8 @@ void drain_timings(se_hip_pipeline* p) {
   for (auto& t : p->pending) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, t.start, t.stop) == hipSuccess) { p->ms_sum[t.kernel] += ms; p->launches[t.kernel]++; }
-    p->event_pool.push_back(t.start);
-    p->event_pool.push_back(t.stop);
+    p->event_pool.push_back(std::move(t.start));
+    p->event_pool.push_back(std::move(t.stop));
   }
   p->pending.clear();
 }
@@ -355,7 +371,7 @@ RayLaunchArgs make_ray_args(se_hip_pipeline* p, const float pose_cm[16], const f
   for (int i = 0; i < 3; ++i) a.scaled_origin[i] = a.org[i] / m.dim + 1.f;
   L.smem = ray_map_args(p, mu, a);
   a.W = p->cfg.width; a.H = p->cfg.height; a.row_begin = p->row_begin; a.row_end = p->row_end;
-  a.tile_cost = p->prio_hint ? p->tile_cost : nullptr;
+  a.tile_cost = p->prio_hint ? p->tile_cost.get() : nullptr;
   a.prio_thr = p->prio_thr;
   a.cost_shift = std::max(0, p->leaf_level - 6);
   a.ray_order = p->ray_order; a.n_cus = p->n_cus;
@@ -384,7 +400,7 @@ RayLaunchArgs make_ray_args(se_hip_pipeline* p, const float pose_cm[16], const f
 #ifdef SE_WAVE_PROBE
   {
     // probe builds (tools/wave_timeline.py): the per-wave records of the PREVIOUS raycast launch are written to $SE_HIP_WLOG when the next one is prepared
-    static unsigned long long* wl = nullptr;
+    static unsigned long long* wl = nullptr;   // (raw on purpose: one buffer per process, no handle owns it, never released)
     static bool tried = false;
     if (!tried) { tried = true; if (std::getenv("SE_HIP_WLOG")) { hipHostMalloc((void**)&wl, 4 * 8 * 32768, 0); std::memset(wl, 0, 4 * 8 * 32768); } }
     a.wlog = wl;
@@ -509,11 +525,9 @@ int fetch_counters(se_hip_pipeline* p) {
 // ---- batched queries (points, boxes, rays, per-block meshes): the host path they share
 // Grows the handle's staging buffer to `need` bytes (see se_hip_pipeline::staging): work that still reads the old one is waited for first.
 int reserve_staging(se_hip_pipeline* p, size_t need) {
-  if (need <= p->staging_cap) return SE_HIP_OK;
-  if (p->staging) { HIP_TRY(hipStreamSynchronize(p->stream)); hipFree(p->staging); p->staging = nullptr; p->staging_cap = 0; }
-  HIP_TRY(hipMalloc((void**)&p->staging, need));
-  p->staging_cap = need;
-  return SE_HIP_OK;
+  if (need <= p->staging.size()) return SE_HIP_OK;
+  if (p->staging) HIP_TRY(hipStreamSynchronize(p->stream));
+  return p->staging.reserve(need, "staging");
 }
 // Layout of a staging buffer: the offsets of `k` parts of `bytes[i]` bytes packed in the order given; returns the total.  Nothing is padded: the
 // callers list 8-byte items first, then 4-byte items, then bytes, each part a whole number of its items, so every part is naturally aligned.
@@ -615,7 +629,7 @@ void clear_map_index(se_hip_pipeline* p, size_t nb, size_t nn) {
   hipMemsetAsync(m.newkeys, 0, sizeof(unsigned long long), p->stream);
   if (p->newkeys_own) hipMemsetAsync(p->newkeys_own, 0, sizeof(unsigned long long), p->stream);
   if (p->newkeys_own2) hipMemsetAsync(p->newkeys_own2, 0, sizeof(unsigned long long), p->stream);
-  p->own_clean[0] = p->newkeys_own != nullptr; p->own_clean[1] = p->newkeys_own2 != nullptr;
+  p->own_clean[0] = p->newkeys_own.get() != nullptr; p->own_clean[1] = p->newkeys_own2.get() != nullptr;
   // node 0 = root: level 0, side = size
   const uint32_t ctr0[C_COUNT] = {0u, 1u, 0u, 0u, 0u, 0u, 0u, 0u};
   hipMemcpyAsync(m.ctr, ctr0, sizeof ctr0, hipMemcpyHostToDevice, p->stream);
@@ -657,12 +671,13 @@ int se_hip_create(const se_hip_config* cfg, se_hip_pipeline** out) {
   if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
     return fail(SE_HIP_E_NOGPU, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
 
-  se_hip_pipeline* p = new se_hip_pipeline();
+  std::unique_ptr<se_hip_pipeline> handle(new se_hip_pipeline());   // (every early return below releases what exists by then)
+  se_hip_pipeline* p = handle.get();
   p->cfg = *cfg;
   p->device = cfg->device;
   p->row_begin = cfg->row_begin;
   p->row_end = (cfg->row_end > cfg->row_begin) ? cfg->row_end : cfg->height;
-  if (p->row_begin < 0 || p->row_end > cfg->height) { delete p; return fail(SE_HIP_E_INVALID, "bad row range"); }
+  if (p->row_begin < 0 || p->row_end > cfg->height) return fail(SE_HIP_E_INVALID, "bad row range");
   if (const char* ev = std::getenv("SE_HIP_RAY_CACHE_LEVELS")) p->ray_cache_levels = std::atoi(ev);  // tuning knob
   if (const char* ev = std::getenv("SE_HIP_ICP_LOOKAHEAD")) p->icp_lookahead = std::max(0, std::atoi(ev));   // A/B knob (0: every ICP iteration enqueued up front)
   if (const char* ev = std::getenv("SE_HIP_INTEG_GRID")) p->integ_grid = std::atoi(ev);            // tuning knob
@@ -719,18 +734,12 @@ int se_hip_create(const se_hip_config* cfg, se_hip_pipeline** out) {
   if (cfg->field_type == SE_HIP_FIELD_SDF) { m.init_x = 1.f; m.init_y = 0.f; m.empty_x = 1.f; }
   else { m.init_x = 0.f; m.init_y = 0.f; m.empty_x = 0.f; }
 
-  auto bail = [&](hipError_t e, const char* what) { std::string msg = std::string(what) + ": " + hipGetErrorString(e); se_hip_destroy(p); return fail(SE_HIP_E_DEVICE, msg); };
-#define ALLOC(ptr, bytes) do { hipError_t e_ = hipMalloc((void**)&(ptr), (bytes)); if (e_ != hipSuccess) return bail(e_, "hipMalloc " #ptr); } while (0)
-  hipError_t e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) return bail(e, "hipStreamCreate");
-  p->own_stream = true;
-  e = hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking);
-  if (e != hipSuccess) return bail(e, "hipStreamCreate");
-  p->own_side = true;
-  // these two only order streams of this device against each other: no system-scope fence (its cache write-back /
-  // invalidate sits between the sweep and the raycast otherwise), no timing
-  hipEventCreateWithFlags(&p->ev_sweep, hipEventDisableTiming | hipEventDisableSystemFence);
-  hipEventCreateWithFlags(&p->ev_scan, hipEventDisableTiming | hipEventDisableSystemFence);
+  // an array of the map: its owner's allocation of n items and the DevMap pointer that goes with it
+  auto own = [](auto& buf, auto*& raw, size_t n, const char* name) { const int r = buf.alloc(n, name); raw = buf.get(); return r; };
+  if (int r = p->stream.create("stream")) return r;
+  if (int r = p->side.create("side")) return r;
+  if (int r = p->ev_sweep.create("ev_sweep")) return r;
+  if (int r = p->ev_scan.create("ev_scan")) return r;
   p->sharded = (p->row_begin != 0 || p->row_end != cfg->height);
   // r03: pooled bricks overlap too (their raycast reads the index the scan writes: see se_block_entry for why that race is
   // benign); SE_HIP_POOLED_OVERLAP=0 restores the serial schedule for pooled maps
@@ -738,48 +747,48 @@ int se_hip_create(const se_hip_config* cfg, se_hip_pipeline** out) {
   p->host_gate = p->overlap && !p->sharded;
   if (const char* ev = std::getenv("SE_HIP_HOST_GATE")) p->host_gate = p->host_gate && std::atoi(ev) != 0;   // tuning knob
   if (p->host_gate) {
-    e = hipHostMalloc((void**)&p->gate_host, 64);
-    if (e != hipSuccess) return bail(e, "hipHostMalloc");
+    if (int r = p->gate_host.alloc(16, "gate_host")) return r;
     std::memset(p->gate_host, 0, 64);
   }
-  ALLOC(m.tab, p->tab_entries * sizeof(uint32_t));
-  ALLOC(m.occ, p->occ_words * sizeof(uint32_t));
+  if (int r = own(p->m_tab, m.tab, p->tab_entries, "m.tab")) return r;
+  if (int r = own(p->m_occ, m.occ, p->occ_words, "m.occ")) return r;
   p->lbits_words = (cells + 31) / 32;
-  ALLOC(m.lbits, p->lbits_words * sizeof(uint32_t));
+  if (int r = own(p->m_lbits, m.lbits, p->lbits_words, "m.lbits")) return r;
   m.clevel = std::min(p->leaf_level, 5);      // coarse cells of dim / 32 (15 cm at 4.8 m): see se_beam_start
   p->cbits_words = std::max<size_t>(1, ((size_t)1 << (3 * m.clevel)) / 32);
-  ALLOC(m.cbits, 2 * p->cbits_words * sizeof(uint32_t));   // [dilated bits][undilated bits of the same grid: se_mark_coarse]
+  if (int r = own(p->m_cbits, m.cbits, 2 * p->cbits_words, "m.cbits")) return r;   // [dilated bits][undilated bits of the same grid: se_mark_coarse]
   m.fbits = nullptr;
   // the level-min(leaf, 6) grid, cells of dim / 64 (7.5 cm at 4.8 m): second stage of the beam start, OFusion leap
-  if (se_flevel(m) > m.clevel) { p->fbits_words = ((size_t)1 << (3 * se_flevel(m))) / 32; ALLOC(m.fbits, p->fbits_words * sizeof(uint32_t)); }
-  ALLOC(m.vx, slots * 1024 * sizeof(float));   // [512 x | 512 y] per brick
+  if (se_flevel(m) > m.clevel) { p->fbits_words = ((size_t)1 << (3 * se_flevel(m))) / 32; if (int r = own(p->m_fbits, m.fbits, p->fbits_words, "m.fbits")) return r; }
+  if (int r = own(p->m_vx, m.vx, slots * 1024, "m.vx")) return r;   // [512 x | 512 y] per brick
   m.ybyte = cfg->field_type == SE_HIP_FIELD_SDF ? 1 : 0;   // SDF weights are stored as bytes (se_device.h)
-  ALLOC(m.bpos, cap * sizeof(uint32_t));
-  ALLOC(m.bactive, (slots + 3) & ~(size_t)3);   // whole 32-bit words: se_set_active_once
-  ALLOC(m.nx, capn * 8 * sizeof(float));
-  ALLOC(m.ny, capn * 8 * sizeof(float));
-  ALLOC(m.npos, capn * sizeof(uint32_t));
-  ALLOC(m.nlevel, capn);
-  ALLOC(m.ctr, C_COUNT * sizeof(uint32_t));
-  ALLOC(m.stats, S_COUNT * sizeof(unsigned long long));
-  ALLOC(m.newkeys, (m.cap_keys + 1) * sizeof(unsigned long long));
-  p->newkeys_own = m.newkeys; p->cap_keys_own = m.cap_keys;
-  ALLOC(p->newkeys_own2, (m.cap_keys + 1) * sizeof(unsigned long long));
-  for (int i = 0; i < se_hip_pipeline::kIn; ++i) ALLOC(p->depth_ring[i], (size_t)cfg->width * cfg->height * sizeof(float));
-  ALLOC(p->vertex_own, (size_t)cfg->width * cfg->height * 3 * sizeof(float));
-  ALLOC(p->normal_own, (size_t)cfg->width * cfg->height * 3 * sizeof(float));
+  if (int r = own(p->m_bpos, m.bpos, cap, "m.bpos")) return r;
+  if (int r = own(p->m_bactive, m.bactive, (slots + 3) & ~(size_t)3, "m.bactive")) return r;   // whole 32-bit words: se_set_active_once
+  if (int r = own(p->m_nx, m.nx, capn * 8, "m.nx")) return r;
+  if (int r = own(p->m_ny, m.ny, capn * 8, "m.ny")) return r;
+  if (int r = own(p->m_npos, m.npos, capn, "m.npos")) return r;
+  if (int r = own(p->m_nlevel, m.nlevel, capn, "m.nlevel")) return r;
+  if (int r = own(p->m_ctr, m.ctr, C_COUNT, "m.ctr")) return r;
+  if (int r = own(p->m_stats, m.stats, S_COUNT, "m.stats")) return r;
+  if (int r = own(p->newkeys_own, m.newkeys, m.cap_keys + 1, "newkeys_own")) return r;
+  p->cap_keys_own = m.cap_keys;
+  if (int r = p->newkeys_own2.alloc(m.cap_keys + 1, "newkeys_own2")) return r;
+  const size_t px = (size_t)cfg->width * cfg->height;
+  for (int i = 0; i < se_hip_pipeline::kIn; ++i) if (int r = p->depth_ring[i].alloc(px, "depth_ring")) return r;
+  if (int r = p->vertex_own.alloc(px * 3, "vertex_own")) return r;
+  if (int r = p->normal_own.alloc(px * 3, "normal_own")) return r;
   p->vertex = p->vertex_own; p->normal = p->normal_own;
-  ALLOC(p->chain, 4 * sizeof(unsigned long long));
+  if (int r = p->chain.alloc(4, "chain")) return r;
   const size_t n_tiles = ((size_t)(cfg->width + SE_TILE_W - 1) / SE_TILE_W) * ((size_t)(cfg->height + SE_TILE_H - 1) / SE_TILE_H);
-  ALLOC(p->tile_cost, (n_tiles + 4096) * sizeof(unsigned short));   // (+ padding: se_ray_schedule reads it in 16-byte pieces)
-  ALLOC(p->prio_thr, 4 * sizeof(int));
+  if (int r = p->tile_cost.alloc(n_tiles + 4096, "tile_cost")) return r;   // (+ padding: se_ray_schedule reads it in 16-byte pieces)
+  if (int r = p->prio_thr.alloc(4, "prio_thr")) return r;
   hipMemsetAsync(p->tile_cost, 0, (n_tiles + 4096) * sizeof(unsigned short), p->stream);
   {
     hipDeviceProp_t prop{};
     if (hipGetDeviceProperties(&prop, p->device) == hipSuccess && prop.multiProcessorCount > 0) p->n_cus = prop.multiProcessorCount;
     if (const char* ev = std::getenv("SE_HIP_RAY_DEAL")) p->n_cus = std::max(1, std::atoi(ev));   // tuning knob: width of the snake deal (1 = image order)
     const size_t n_pairs = (n_tiles + 1) / 2;
-    ALLOC(p->ray_order, n_pairs * sizeof(uint32_t));
+    if (int r = p->ray_order.alloc(n_pairs, "ray_order")) return r;
     std::vector<uint32_t> ident(n_pairs);
     for (size_t i = 0; i < n_pairs; ++i) ident[i] = (uint32_t)i;
     hipMemcpyAsync(p->ray_order, ident.data(), n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream);
@@ -787,64 +796,36 @@ int se_hip_create(const se_hip_config* cfg, se_hip_pipeline** out) {
   }
   { const int off[4] = {256, 256, 256, 0}; hipMemcpyAsync(p->prio_thr, off, sizeof off, hipMemcpyHostToDevice, p->stream); }
   p->depth = p->depth_ring[0]; p->cur_in = 0;
-  e = hipHostMalloc((void**)&p->ctr_host, C_COUNT * sizeof(uint32_t));
-  if (e != hipSuccess) return bail(e, "hipHostMalloc");
+  if (int r = p->ctr_host.alloc(C_COUNT, "ctr_host")) return r;
   std::memset(p->ctr_host, 0, C_COUNT * sizeof(uint32_t));
 
   p->cap_blocks = cap; p->cap_nodes = capn;
   reset_map_state(p);
-  for (int i = 0; i < se_hip_pipeline::kIn; ++i) hipMemsetAsync(p->depth_ring[i], 0, (size_t)cfg->width * cfg->height * sizeof(float), p->stream);
-  hipMemsetAsync(p->vertex, 0, (size_t)cfg->width * cfg->height * 3 * sizeof(float), p->stream);
-  hipMemsetAsync(p->normal, 0, (size_t)cfg->width * cfg->height * 3 * sizeof(float), p->stream);
+  for (int i = 0; i < se_hip_pipeline::kIn; ++i) hipMemsetAsync(p->depth_ring[i], 0, px * sizeof(float), p->stream);
+  hipMemsetAsync(p->vertex, 0, px * 3 * sizeof(float), p->stream);
+  hipMemsetAsync(p->normal, 0, px * 3 * sizeof(float), p->stream);
   if (cfg->field_type == SE_HIP_FIELD_OFUSION) {
     std::vector<float> lut, lo;
     make_bspline(lut);
     make_logodds(lut, lo);
-    ALLOC(p->bspline, lut.size() * sizeof(float));
-    ALLOC(p->logodds, lo.size() * sizeof(float));
+    if (int r = p->bspline.alloc(lut.size(), "bspline")) return r;
+    if (int r = p->logodds.alloc(lo.size(), "logodds")) return r;
     hipMemcpy(p->bspline, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice);
     hipMemcpy(p->logodds, lo.data(), lo.size() * sizeof(float), hipMemcpyHostToDevice);
   }
-#undef ALLOC
-  e = hipStreamSynchronize(p->stream);
-  if (e != hipSuccess) return bail(e, "initialisation");
-  *out = p;
+  const hipError_t e = hipStreamSynchronize(p->stream);
+  if (e != hipSuccess) return fail(SE_HIP_E_DEVICE, std::string("initialisation: ") + hipGetErrorString(e));
+  *out = handle.release();
   return SE_HIP_OK;
 }
 
+// (what the handle holds releases itself, the streams last: se_host_resources.h)
 int se_hip_destroy(se_hip_pipeline* p) {
   if (!p) return SE_HIP_OK;
   p->has_pending = false;   // (a deferred raycast nobody will look at)
   hipSetDevice(p->device);
   if (p->side) hipStreamSynchronize(p->side);
   if (p->stream) hipStreamSynchronize(p->stream);
-  for (auto& t : p->pending) { hipEventDestroy(t.start); hipEventDestroy(t.stop); }
-  for (auto& ev : p->event_pool) hipEventDestroy(ev);
-  DevMap& m = p->map;
-  void* ptrs[] = {m.occ, m.lbits, m.cbits, m.fbits, m.tab, m.vx, m.bpos, m.bactive, m.nx, m.ny, m.npos, m.nlevel, m.ctr, m.stats, p->newkeys_own, p->newkeys_own2,
-                  p->depth_ring[0], p->depth_ring[1], p->depth_ring[2], p->vertex_own, p->normal_own, p->bspline, p->logodds, p->chain, p->tile_cost, p->prio_thr, p->ray_order};
-  for (void* q : ptrs) if (q) hipFree(q);
-  for (auto* q : p->pyr_depth) if (q) hipFree(q);
-  for (auto* q : p->pyr_vertex) if (q) hipFree(q);
-  for (auto* q : p->pyr_normal) if (q) hipFree(q);
-  if (p->track) hipFree(p->track);
-  if (p->rgbw) hipFree(p->rgbw);
-  if (p->reduce_partial) hipFree(p->reduce_partial);
-  if (p->icp) hipFree(p->icp);
-  if (p->icp_host) hipHostFree(p->icp_host);
-  if (p->ctr_host) hipHostFree(p->ctr_host);
-  if (p->bpos_sorted) hipFree(p->bpos_sorted);
-  if (p->sort_tmp) hipFree(p->sort_tmp);
-  if (p->gate_host) hipHostFree(p->gate_host);
-  if (p->mesh_ctr) hipFree(p->mesh_ctr);
-  if (p->staging) hipFree(p->staging);
-  if (p->meshb_dev) hipFree(p->meshb_dev);
-  for (int i = 0; i < se_hip_pipeline::kIn; ++i) { if (p->in_host[i]) hipHostFree(p->in_host[i]); if (p->in_done[i]) hipEventDestroy(p->in_done[i]); }
-  if (p->own_side && p->side) hipStreamDestroy(p->side);
-  if (p->ev_sweep) hipEventDestroy(p->ev_sweep);
-  if (p->ev_scan) hipEventDestroy(p->ev_scan);
-  if (p->ev_edit) hipEventDestroy(p->ev_edit);
-  if (p->own_stream && p->stream) hipStreamDestroy(p->stream);
   delete p;
   return SE_HIP_OK;
 }
@@ -877,9 +858,7 @@ int se_hip_set_stream(se_hip_pipeline* p, void* hip_stream) {
   HIP_TRY(hipStreamSynchronize(p->stream));
   p->gate_armed = false;
   drain_timings(p);
-  if (p->own_stream && p->stream) hipStreamDestroy(p->stream);
-  p->stream = (hipStream_t)hip_stream;
-  p->own_stream = false;
+  p->stream.borrow((hipStream_t)hip_stream);   // (the handle's own stream, if it still had it, ends here)
   return SE_HIP_OK;
 }
 
@@ -893,12 +872,8 @@ int se_hip_set_scan_stream(se_hip_pipeline* p, void* hip_stream) {
   if (p->side) HIP_TRY(hipStreamSynchronize(p->side));
   HIP_TRY(hipStreamSynchronize(p->stream));
   drain_timings(p);
-  if (p->own_side && p->side) hipStreamDestroy(p->side);
-  p->side = nullptr; p->own_side = false;
-  if (hip_stream) { p->side = (hipStream_t)hip_stream; return SE_HIP_OK; }
-  HIP_TRY(hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking));
-  p->own_side = true;
-  return SE_HIP_OK;
+  if (hip_stream) { p->side.borrow((hipStream_t)hip_stream); return SE_HIP_OK; }
+  return p->side.create("side");
 }
 
 // Host image -> the next slot of the pinned input ring (see se_hip_pipeline::in_host); nothing is enqueued.
@@ -908,10 +883,10 @@ static int stage_input(se_hip_pipeline* p, const void* host, size_t bytes, int k
     // (first call, or a larger input image: the slots' pending readers first)
     if (p->side) HIP_TRY(hipStreamSynchronize(p->side));
     HIP_TRY(hipStreamSynchronize(p->stream));
-    for (int i = 0; i < R; ++i) { if (p->in_host[i]) hipHostFree(p->in_host[i]); p->in_host[i] = nullptr; p->in_state[i] = 0; p->in_event[i] = false; }
+    for (int i = 0; i < R; ++i) { p->in_state[i] = 0; p->in_event[i] = false; }
     p->in_cap = 0; p->in_pending.kind = 0;
-    for (int i = 0; i < R; ++i) HIP_TRY(hipHostMalloc(&p->in_host[i], bytes));
-    p->in_cap = bytes;
+    for (int i = 0; i < R; ++i) if (int r = p->in_host[i].reserve(bytes, "in_host")) return r;
+    p->in_cap = bytes;   // (only now: a failed allocation leaves 0, and the next upload grows the slots that are still too small)
   }
   const int i = p->in_next;
   p->in_next = (i + 1) % R;
@@ -928,14 +903,14 @@ static int stage_input(se_hip_pipeline* p, const void* host, size_t bytes, int k
     HIP_TRY(hipStreamSynchronize(p->stream));
   }
   p->in_state[i] = 0; p->in_event[i] = false;
-  const void* src = p->in_host[i];
+  const void* src = p->in_host[i].get();
   if (p->pinned_input) {
     // caller-pinned image (se_hip_set_pinned_input): read where it lies; the slot only lends its device image and its place in the ring
     hipPointerAttribute_t at{};
     if (hipPointerGetAttributes(&at, host) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) src = at.devicePointer;
     else (void)hipGetLastError();   // (pageable memory: an error code, not an error)
   }
-  if (src == p->in_host[i]) std::memcpy(p->in_host[i], host, bytes);   // (r06, measured: non-temporal stores here took 21 us instead of 16 us for the 614 KB image and moved nothing on the device side)
+  if (src == p->in_host[i].get()) std::memcpy(p->in_host[i], host, bytes);   // (r06, measured: non-temporal stores here took 21 us instead of 16 us for the 614 KB image and moved nothing on the device side)
   p->in_pending = DepthSrc{src, p->depth_ring[i], kind, in_w, ratio};
   p->depth = p->depth_ring[i];
   p->cur_in = i;
@@ -966,7 +941,7 @@ int se_hip_set_pinned_input(se_hip_pipeline* p, int32_t on) {
   p->pinned_input = on != 0;
   return SE_HIP_OK;
 }
-void* se_hip_host_alloc(size_t bytes) {
+void* se_hip_host_alloc(size_t bytes) {   // (raw on purpose: the memory is the caller's until se_hip_host_free)
   void* h = nullptr;
   if (bytes == 0 || hipHostMalloc(&h, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
   return h;
@@ -1155,7 +1130,7 @@ int se_hip_set_new_keys_buffer(se_hip_pipeline* p, uint64_t* device_list, int64_
   InFrame guard(p);   // (a deferred raycast does not care where the next scan writes its list)
   if (int r = check(p)) return r;
   if (device_list && capacity_words < 2) return fail(SE_HIP_E_INVALID, "key buffer too small");
-  p->map.newkeys = device_list ? (unsigned long long*)device_list : p->newkeys_own;
+  p->map.newkeys = device_list ? (unsigned long long*)device_list : p->newkeys_own.get();
   p->map.cap_keys = device_list ? (unsigned long long)(capacity_words - 1) : p->cap_keys_own;
   return SE_HIP_OK;
 }
@@ -1266,18 +1241,18 @@ static int sort_block_list(se_hip_pipeline* p) {
   const uint32_t n0 = std::min<uint32_t>(p->ctr_host[C_BLOCKS], p->map.cap_blocks);   // (written by an earlier sweep: never more than the list holds)
   if (++p->sweeps_since_sort < p->sort_every || n0 < 4096 || (size_t)n0 * 2 < (size_t)p->sorted_n * 3) return SE_HIP_OK;
   if (p->sort_cap < n0) {
-    if (p->bpos_sorted) hipFree(p->bpos_sorted);
-    if (p->sort_tmp) hipFree(p->sort_tmp);
-    p->bpos_sorted = nullptr; p->sort_tmp = nullptr;
+    // (released behind whatever sort is still enqueued: the release waits for the device.  The sizes say 0 until both buffers exist again)
+    p->sort_cap = 0; p->sort_tmp_bytes = 0;
+    p->bpos_sorted.reset(); p->sort_tmp.reset();
     const size_t cap = std::min<size_t>((size_t)n0 + n0 / 2 + 65536, p->map.cap_blocks);
-    HIP_TRY(hipMalloc((void**)&p->bpos_sorted, cap * sizeof(uint32_t)));
+    if (int r = p->bpos_sorted.alloc(cap, "bpos_sorted")) return r;
     size_t bytes = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, p->map.bpos, p->bpos_sorted, (int)cap, 0, 30, p->stream));
-    HIP_TRY(hipMalloc(&p->sort_tmp, bytes));
+    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, p->map.bpos, p->bpos_sorted.get(), (int)cap, 0, 30, p->stream));
+    if (int r = p->sort_tmp.alloc(bytes, "sort_tmp")) return r;
     p->sort_tmp_bytes = bytes; p->sort_cap = cap;
   }
   size_t bytes = p->sort_tmp_bytes;
-  HIP_TRY(hipcub::DeviceRadixSort::SortKeys(p->sort_tmp, bytes, p->map.bpos, p->bpos_sorted, (int)n0, 0, 30, p->stream));
+  HIP_TRY(hipcub::DeviceRadixSort::SortKeys(p->sort_tmp.get(), bytes, p->map.bpos, p->bpos_sorted.get(), (int)n0, 0, 30, p->stream));
   HIP_TRY(hipMemcpyAsync(p->map.bpos, p->bpos_sorted, (size_t)n0 * sizeof(uint32_t), hipMemcpyDeviceToDevice, p->stream));
   p->sorted_n = n0; p->sweeps_since_sort = 0;
   return SE_HIP_OK;
@@ -1360,7 +1335,7 @@ int se_hip_integrate_sweep(se_hip_pipeline* p, const float pose_cm[16], const fl
     a.n_tiles = ((p->cfg.width + SE_TILE_W - 1) / SE_TILE_W) * ((p->row_end - p->row_begin + SE_TILE_H - 1) / SE_TILE_H);
     // the cost-sorted deal pays for the SDF march (raycast 40.8 -> 39.2 us at 512^3, 81.3 -> 79.1 at 1024^3); OFusion's cost
     // figure predicts its launch less well (126 -> 130 us): its workgroups stay in image order
-    a.ray_order = sdf ? p->ray_order : nullptr;
+    a.ray_order = sdf ? p->ray_order.get() : nullptr;
   }
   const dim3 block(SE_WG);
   {
@@ -1392,7 +1367,7 @@ int se_hip_integrate_sweep(se_hip_pipeline* p, const float pose_cm[16], const fl
     hipEventRecord(p->ev_sweep, p->stream);
     if (p->cur_in >= 0) {   // the input slot's last reader in a frame: what a later upload into the slot waits for (stage_input)
       const int i = p->cur_in;
-      if (!p->in_done[i]) HIP_TRY(hipEventCreateWithFlags(&p->in_done[i], hipEventDisableTiming));
+      if (int r = p->in_done[i].create("in_done")) return r;   // (first use)
       HIP_TRY(hipEventRecord(p->in_done[i], p->stream));
       p->in_event[i] = true;
     }
@@ -1615,20 +1590,20 @@ int se_hip_track(se_hip_pipeline* p, const float k[4], float icp_threshold, uint
   hipStream_t s = p->stream;
   // buffers (first call)
   if ((int)p->pyr_vertex.size() < n_levels) {
-    p->pyr_depth.resize(n_levels, nullptr); p->pyr_vertex.resize(n_levels, nullptr); p->pyr_normal.resize(n_levels, nullptr);
+    p->pyr_depth.resize(n_levels); p->pyr_vertex.resize(n_levels); p->pyr_normal.resize(n_levels);
     for (int i = 0; i < n_levels; ++i) {
       const size_t n = (size_t)(W >> i) * (H >> i);
-      if (!p->pyr_depth[i]) HIP_TRY(hipMalloc((void**)&p->pyr_depth[i], n * sizeof(float)));
-      if (!p->pyr_vertex[i]) { HIP_TRY(hipMalloc((void**)&p->pyr_vertex[i], n * 3 * sizeof(float))); HIP_TRY(hipMemsetAsync(p->pyr_vertex[i], 0, n * 3 * sizeof(float), s)); }
-      if (!p->pyr_normal[i]) { HIP_TRY(hipMalloc((void**)&p->pyr_normal[i], n * 3 * sizeof(float))); HIP_TRY(hipMemsetAsync(p->pyr_normal[i], 0, n * 3 * sizeof(float), s)); }
+      if (!p->pyr_depth[i]) { if (int r = p->pyr_depth[i].alloc(n, "pyr_depth")) return r; }
+      if (!p->pyr_vertex[i]) { if (int r = p->pyr_vertex[i].alloc(n * 3, "pyr_vertex")) return r; HIP_TRY(hipMemsetAsync(p->pyr_vertex[i], 0, n * 3 * sizeof(float), s)); }
+      if (!p->pyr_normal[i]) { if (int r = p->pyr_normal[i].alloc(n * 3, "pyr_normal")) return r; HIP_TRY(hipMemsetAsync(p->pyr_normal[i], 0, n * 3 * sizeof(float), s)); }
     }
   }
-  if (!p->track) {
-    HIP_TRY(hipMalloc((void**)&p->track, (size_t)W * H * sizeof(TrackData)));
+  if (!p->icp_host) {   // (the last of the four: a call that failed half-way is taken up again)
+    if (int r = p->track.alloc((size_t)W * H, "track")) return r;
     HIP_TRY(hipMemsetAsync(p->track, 0, (size_t)W * H * sizeof(TrackData), s));
-    HIP_TRY(hipMalloc((void**)&p->reduce_partial, 2 * 8 * SE_TRACK_SEGMENTS * 32 * sizeof(float)));   // the iterations' partial rows alternate
-    HIP_TRY(hipMalloc((void**)&p->icp, 2 * sizeof(IcpState)));                                       // ... and so does the state (k_icp_iter)
-    HIP_TRY(hipHostMalloc((void**)&p->icp_host, sizeof(IcpHostRecord)));
+    if (int r = p->reduce_partial.alloc(2 * 8 * SE_TRACK_SEGMENTS * 32, "reduce_partial")) return r;   // the iterations' partial rows alternate
+    if (int r = p->icp.alloc(2, "icp")) return r;                                                     // ... and so does the state (k_icp_iter)
+    if (int r = p->icp_host.alloc(1, "icp_host")) return r;
     std::memset(p->icp_host, 0, sizeof(IcpHostRecord));
   }
   // pyramid (DenseSLAMSystem.cpp:149-163): scaled_depth_[0] is the current depth image
@@ -1645,8 +1620,8 @@ int se_hip_track(se_hip_pipeline* p, const float k[4], float icp_threshold, uint
   // buffer that the next upload (or the caller, for zero-copy depth) may overwrite.  The copy and the first two half-sampling passes are one launch
   // (k_depth_pyramid; r04 -- before: a runtime copy, ~20 us of host time in front of the frame's first kernel, and two launches).
   {
-    float* l1 = n_levels > 1 ? p->pyr_depth[1] : nullptr;
-    float* l2 = n_levels > 2 ? p->pyr_depth[2] : nullptr;
+    float* l1 = n_levels > 1 ? p->pyr_depth[1].get() : nullptr;
+    float* l2 = n_levels > 2 ? p->pyr_depth[2].get() : nullptr;
     hipLaunchKernelGGL(k_depth_pyramid, dim3(((W + 3) / 4 + 255) / 256, (H + 3) / 4), dim3(256), 0, s, p->pyr_depth[0], l1, l2, d0, W, H, 0.1f * 3, p->filter_input ? 0 : 1);   // e_delta * 3
     d0 = p->pyr_depth[0];
   }
@@ -1663,7 +1638,7 @@ int se_hip_track(se_hip_pipeline* p, const float k[4], float icp_threshold, uint
       const M4 invK = inverse_camera_matrix(kk);
       for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) L.K[i].m[r * 4 + c] = invK.m[r][c];
       L.w[i] = W >> i; L.h[i] = H >> i;
-      L.depth[i] = i == 0 ? d0 : p->pyr_depth[i];
+      L.depth[i] = i == 0 ? d0 : p->pyr_depth[i].get();
       L.vertex[i] = p->pyr_vertex[i]; L.normal[i] = p->pyr_normal[i];
     }
     hipLaunchKernelGGL(k_vertex_normal_levels, dim3((W + 255) / 256, H, n_levels), dim3(256), 0, s, L, k[1] < 0 ? 1 : 0);
@@ -1770,7 +1745,7 @@ int se_hip_filter_depth(se_hip_pipeline* p, int32_t on) {
 int se_hip_download_scaled_depth(se_hip_pipeline* p, int32_t level, float* host_out) {
   if (int r = check(p)) return r;
   if (!host_out || level < 0 || level >= (int)p->pyr_depth.size() || !p->scaled0) return fail(SE_HIP_E_INVALID, "no such pyramid level (se_hip_track builds it)");
-  const float* src = level == 0 ? p->scaled0 : p->pyr_depth[level];
+  const float* src = level == 0 ? p->scaled0 : p->pyr_depth[level].get();
   const size_t n = (size_t)(p->cfg.width >> level) * (p->cfg.height >> level);
   HIP_TRY(hipMemcpyAsync(host_out, src, n * sizeof(float), hipMemcpyDeviceToHost, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
@@ -1789,8 +1764,7 @@ int se_hip_download_track(se_hip_pipeline* p, void* host_trackdata, float host_r
 
 // -------------------------------------------------------------------------------------- rendering
 static int render_target(se_hip_pipeline* p) {
-  if (!p->rgbw) HIP_TRY(hipMalloc((void**)&p->rgbw, (size_t)p->cfg.width * p->cfg.height * 4));
-  return SE_HIP_OK;
+  return p->rgbw.reserve((size_t)p->cfg.width * p->cfg.height * 4, "rgbw");   // (first use)
 }
 static int render_download(se_hip_pipeline* p, uint8_t* host) {
   HIP_TRY(hipMemcpyAsync(host, p->rgbw, (size_t)p->cfg.width * p->cfg.height * 4, hipMemcpyDeviceToHost, p->stream));
@@ -1868,7 +1842,7 @@ int ensure_mc_table(se_hip_pipeline* p) {
 int run_mesh(se_hip_pipeline* p, float* dev_out, unsigned long long capacity, unsigned long long* n) {
   if (int r = join_scan(p)) return r;
   if (int r = ensure_mc_table(p)) return r;
-  if (!p->mesh_ctr) HIP_TRY(hipMalloc((void**)&p->mesh_ctr, 2 * sizeof(unsigned long long)));
+  if (int r = p->mesh_ctr.reserve(2, "mesh_ctr")) return r;   // (first use)
   HIP_TRY(hipMemsetAsync(p->mesh_ctr, 0, 2 * sizeof(unsigned long long), p->stream));
   MeshArgs a{dev_out, p->mesh_ctr, capacity};
   hipLaunchKernelGGL(k_mesh, dim3(4096), dim3(SE_WG), 0, p->stream, p->map, a);
@@ -1894,8 +1868,8 @@ int se_hip_mesh_download(se_hip_pipeline* p, float* host_triangles, int64_t capa
   if (!host_triangles || capacity_triangles < 0 || !n_written) return fail(SE_HIP_E_INVALID, "bad argument");
   *n_written = 0;
   if (capacity_triangles == 0) return SE_HIP_OK;
-  float* dev = nullptr;
-  HIP_TRY(hipMalloc((void**)&dev, (size_t)capacity_triangles * 9 * sizeof(float)));
+  DevBuf<float> dev;
+  if (int r = dev.alloc((size_t)capacity_triangles * 9, "mesh triangles")) return r;
   unsigned long long n = 0;
   int r = run_mesh(p, dev, (unsigned long long)capacity_triangles, &n);
   if (r == SE_HIP_OK) {
@@ -1904,7 +1878,6 @@ int se_hip_mesh_download(se_hip_pipeline* p, float* host_triangles, int64_t capa
     *n_written = (int64_t)w;
     if (r == SE_HIP_OK && n > (unsigned long long)capacity_triangles) r = fail(SE_HIP_E_CAPACITY, "triangle buffer too small (se_hip_mesh_count gives the size)");
   }
-  hipFree(dev);
   return r;
 }
 
@@ -1943,7 +1916,7 @@ int se_hip_memory_info(se_hip_pipeline* p, int64_t out[4]) {
   size_t all = bricks + p->tab_entries * 4 + (p->occ_words + p->lbits_words + 2 * p->cbits_words + p->fbits_words) * 4 + p->cap_blocks * 4 + ((p->slots + 3) & ~(size_t)3) +
                p->cap_nodes * (2 * 8 * 4 + 4 + 1) + 2 * (m.cap_keys + 1) * 8 + se_hip_pipeline::kIn * px * 4 + 2 * px * 3 * 4;
   all += p->sort_cap * sizeof(uint32_t) + p->sort_tmp_bytes;   // (sort_block_list: allocated at the first sort)
-  all += p->staging_cap;                                       // (the _host entries and se_hip_shift_map: grown on demand)
+  all += p->staging.size();                                    // (the _host entries and se_hip_shift_map: grown on demand)
   out[0] = m.dense ? 1 : 0; out[1] = (int64_t)p->slots; out[2] = (int64_t)bricks; out[3] = (int64_t)all;
   return SE_HIP_OK;
 }
@@ -1986,11 +1959,10 @@ int se_hip_download_blocks(se_hip_pipeline* p, int32_t* coords, float* x, float*
     if (active) active[i] = act_all[slot];
   }
   if (x || y) {
-    uint32_t* d_slots = nullptr;
-    float* d_pack = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_slots, n * sizeof(uint32_t)));
-    hipError_t e2 = hipMalloc((void**)&d_pack, n * 512 * sizeof(float));
-    if (e2 != hipSuccess) { hipFree(d_slots); return fail(SE_HIP_E_DEVICE, "hipMalloc (download staging)"); }
+    DevBuf<uint32_t> d_slots;
+    DevBuf<float> d_pack;
+    if (int r = d_slots.alloc(n, "(download staging)")) return r;
+    if (int r = d_pack.alloc(n * 512, "(download staging)")) return r;
     hipMemcpyAsync(d_slots, slots_sorted.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream);
     for (int plane = 0; plane < 2; ++plane) {
       float* dst = plane ? y : x;
@@ -1999,10 +1971,8 @@ int se_hip_download_blocks(se_hip_pipeline* p, int32_t* coords, float* x, float*
       else hipLaunchKernelGGL(k_gather_bricks, dim3(2048), dim3(SE_WG), 0, p->stream, p->map.vx, d_slots, n, d_pack);
       hipMemcpyAsync(dst, d_pack, n * 512 * sizeof(float), hipMemcpyDeviceToHost, p->stream);
     }
-    hipError_t e3 = hipStreamSynchronize(p->stream);
-    hipFree(d_slots);
-    hipFree(d_pack);
-    if (e3 != hipSuccess) return fail(SE_HIP_E_DEVICE, std::string("download_blocks: ") + hipGetErrorString(e3));
+    const hipError_t e = hipStreamSynchronize(p->stream);
+    if (e != hipSuccess) return fail(SE_HIP_E_DEVICE, std::string("download_blocks: ") + hipGetErrorString(e));
   }
   return SE_HIP_OK;
 }
@@ -2079,8 +2049,8 @@ int launch_mesh_blocks(se_hip_pipeline* p, const se_hip_mesh_select* sel, const 
     return fail(SE_HIP_E_INVALID, "se_hip_mesh_blocks: the block pool is too large for the packed reservation counter");
   if (int r = ensure_mc_table(p)) return r;
   const size_t plane_bytes = (size_t)SE_MB_VIEW_FLOATS * SE_MB_MAX_VIEWS * sizeof(float);
-  if (!p->meshb_dev) HIP_TRY(hipMalloc((void**)&p->meshb_dev, plane_bytes + 3 * sizeof(unsigned long long)));
-  float* planes = (float*)p->meshb_dev;
+  if (int r = p->meshb_dev.reserve(plane_bytes + 3 * sizeof(unsigned long long), "meshb_dev")) return r;   // (first use)
+  float* planes = (float*)p->meshb_dev.get();
   unsigned long long* state = (unsigned long long*)(p->meshb_dev + plane_bytes);
   MeshBlocksArgs a{};
   bool empty = false;
@@ -2315,7 +2285,7 @@ int launch_edit(se_hip_pipeline* p, const se_hip_edit* edits, int64_t n, const s
   hipLaunchKernelGGL(k_edit_blocks, dim3(grid_for((size_t)m.cap_blocks * 64, SE_WG, 4096)), dim3(SE_WG), 0, p->stream, m, a);
   hipLaunchKernelGGL(k_edit_nodes, dim3(grid_for((size_t)m.cap_nodes * 8, SE_WG, 4096)), dim3(SE_WG), 0, p->stream, m, a);
   if (p->side && p->side != p->stream) {
-    if (!p->ev_edit) HIP_TRY(hipEventCreateWithFlags(&p->ev_edit, hipEventDisableTiming | hipEventDisableSystemFence));
+    if (int r = p->ev_edit.create("ev_edit")) return r;   // (first use)
     HIP_TRY(hipEventRecord(p->ev_edit, p->stream));
     HIP_TRY(hipStreamWaitEvent(p->side, p->ev_edit, 0));
   }
@@ -2372,7 +2342,7 @@ int launch_alloc_boxes(se_hip_pipeline* p, const se_hip_alloc_box* boxes, int64_
   if (counts) hipLaunchKernelGGL(k_alloc_boxes_end, dim3(1), dim3(64), 0, p->stream, m, a);
   HIP_TRY(hipMemcpyAsync(p->ctr_host, m.ctr, C_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
   if (p->side && p->side != p->stream) {
-    if (!p->ev_edit) HIP_TRY(hipEventCreateWithFlags(&p->ev_edit, hipEventDisableTiming | hipEventDisableSystemFence));
+    if (int r = p->ev_edit.create("ev_edit")) return r;   // (first use)
     HIP_TRY(hipEventRecord(p->ev_edit, p->stream));
     HIP_TRY(hipStreamWaitEvent(p->side, p->ev_edit, 0));
   }
@@ -2587,11 +2557,10 @@ int se_hip_load_map(se_hip_pipeline* p, const char* filename) {
   for (uint64_t i = 0; i < nb; ++i)
     list.push_back(se_make_key(coords[i * 3] >> 3, coords[i * 3 + 1] >> 3, coords[i * 3 + 2] >> 3, p->leaf_level, p->max_level));
   list[0] = list.size() - 1;
-  unsigned long long* d_list = nullptr; float *d_x = nullptr, *d_y = nullptr; int32_t* d_c = nullptr; unsigned long long* d_k = nullptr;
-  auto cleanup = [&]() { for (void* q : {(void*)d_list, (void*)d_x, (void*)d_y, (void*)d_c, (void*)d_k}) if (q) hipFree(q); };
+  DevBuf<unsigned long long> d_list, d_k; DevBuf<float> d_x, d_y; DevBuf<int32_t> d_c;   // (released on every way out of this function)
   const size_t nval = std::max((size_t)nb * 512, (size_t)nn * 8) + 8;
-  if (hipMalloc((void**)&d_list, list.size() * 8) != hipSuccess || hipMalloc((void**)&d_x, nval * 4) != hipSuccess || hipMalloc((void**)&d_y, nval * 4) != hipSuccess ||
-      hipMalloc((void**)&d_c, ((size_t)nb * 3 + 4) * 4) != hipSuccess || hipMalloc((void**)&d_k, ((size_t)nn + 1) * 8) != hipSuccess) { cleanup(); return fail(SE_HIP_E_DEVICE, "hipMalloc (load staging)"); }
+  const char* const what = "(load staging)";
+  if (d_list.alloc(list.size(), what) || d_x.alloc(nval, what) || d_y.alloc(nval, what) || d_c.alloc((size_t)nb * 3 + 4, what) || d_k.alloc((size_t)nn + 1, what)) return SE_HIP_E_DEVICE;
   // everything that can fail without touching the map has succeeded: quiesce, re-initialise, insert
   if (p->side) HIP_TRY(hipStreamSynchronize(p->side));
   HIP_TRY(hipStreamSynchronize(p->stream));
@@ -2613,7 +2582,6 @@ int se_hip_load_map(se_hip_pipeline* p, const char* filename) {
     hipLaunchKernelGGL(k_load_blocks, dim3(grid_for((size_t)nb * 512, SE_WG, 16384)), dim3(SE_WG), 0, p->stream, p->map, d_c, d_x, d_y, (size_t)nb);
   }
   const hipError_t e = hipStreamSynchronize(p->stream);
-  cleanup();
   if (e != hipSuccess) return fail(SE_HIP_E_DEVICE, std::string("load_map: ") + hipGetErrorString(e));
   int32_t gb = 0, gn = 0;
   if (int r = se_hip_counts(p, &gb, &gn)) return r;
@@ -2668,7 +2636,7 @@ int se_hip_shift_map(se_hip_pipeline* p, const int32_t shift_voxels[3], int64_t*
   p->images_shifted = true;
   const int rc = fetch_counters(p);   // (synchronises; a node pool that ran out while the ancestors were rebuilt: SE_HIP_E_CAPACITY, sticky)
   // 4 KiB per block is not held on to: the next shift is seconds away (the small buffers of the batched queries stay)
-  if (p->staging_cap > p->shift_keep_bytes) { hipFree(p->staging); p->staging = nullptr; p->staging_cap = 0; }
+  if (p->staging.size() > p->shift_keep_bytes) p->staging.reset();
   if (host_counts) {
     host_counts[0] = (int64_t)kept[0]; host_counts[1] = (int64_t)(nb - kept[0]);
     host_counts[2] = (int64_t)kept[1]; host_counts[3] = (int64_t)(nn - kept[1]);   // (the root gave up its values: dropped)
@@ -2704,6 +2672,7 @@ int se_hip_enable_timing(se_hip_pipeline* p, int32_t on) {
 int se_hip_get_timings(se_hip_pipeline* p, double ms_sum[SE_HIP_K_COUNT], int64_t launches[SE_HIP_K_COUNT], int32_t reset) {
   if (int r = check(p)) return r;
   drain_timings(p);
+  if (!p->timing_err.empty()) { const std::string msg = std::move(p->timing_err); p->timing_err.clear(); return fail(SE_HIP_E_DEVICE, msg); }   // (once; the sums stay)
   for (int i = 0; i < SE_HIP_K_COUNT; ++i) {
     if (ms_sum) ms_sum[i] = p->ms_sum[i];
     if (launches) launches[i] = p->launches[i];

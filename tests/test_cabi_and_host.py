@@ -49,6 +49,36 @@ def test_product_never_imports_the_oracle():
                 assert not re.search(r"^\s*(from|import)\s+oracle|#include\s+\"[^\"]*oracle", text, flags=re.M), f"{f} uses the oracle"
 
 
+def test_host_library_releases_nothing_by_hand():
+    """Every device, pinned and event resource of a handle has one owner (csrc/se_host_resources.h): se_hip_api.hip itself neither allocates
+    nor releases.  The exceptions own nothing of a handle's: se_hip_host_alloc / se_hip_host_free (the caller's memory) and the wave probe's
+    process-wide buffer.  This is what guards the small buffers -- no GPU test sees a leak of a few kilobytes."""
+    from supereight_amd import build
+    assert "se_host_resources.h" in build.HEADERS
+    lines = open(os.path.join(ROOT, "supereight_amd", "csrc", "se_hip_api.hip")).read().split("\n")
+    assert '#include "se_host_resources.h"' in "\n".join(lines)
+
+    def region(first, closed):
+        """the line numbers from the one line that begins with `first` to the first line from there on at which closed(text so far) holds"""
+        (start,) = [i for i, l in enumerate(lines) if l.startswith(first)]
+        end = next(j for j in range(start, len(lines)) if closed("\n".join(lines[start:j + 1])))
+        return set(range(start, end + 1))
+
+    def body(text):
+        return "{" in text and text.count("{") == text.count("}")
+
+    def uses(call):
+        return {i for i, l in enumerate(lines) if call in l}
+
+    for call in ("hipFree(", "hipEventDestroy(", "hipStreamDestroy(", "hipMalloc("):
+        assert not uses(call), (call, sorted(i + 1 for i in uses(call)))
+    host_free, host_alloc = region("void se_hip_host_free(", body), region("void* se_hip_host_alloc(", body)
+    probe = region("#ifdef SE_WAVE_PROBE", lambda text: text.endswith("#endif"))
+    assert len(host_free) == 1 and 2 <= len(host_alloc) <= 8 and 3 <= len(probe) <= 12
+    assert uses("hipHostFree(") and uses("hipHostFree(") <= host_free
+    assert uses("hipHostMalloc(") & host_alloc and uses("hipHostMalloc(") <= host_alloc | probe
+
+
 def test_create_argument_validation():
     from supereight_amd.pipeline import _Config, load_library
     lib = load_library()
