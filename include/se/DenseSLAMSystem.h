@@ -26,6 +26,7 @@
 #define SE_HIP_DENSESLAMSYSTEM_H
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <iostream>
 #include <memory>
@@ -212,6 +213,23 @@ class DenseSLAMSystem {
    * those of se::geometry::clearance (include/se/clearance.hpp) on the getMap() snapshot. */
   bool clearanceOf(const int32_t* host_queries, size_t n, const se_hip_collide_test& test, int32_t stop_at, se_hip_clearance_out& host_out) {
     return ok(se_hip_clearance_boxes_host(h_, host_queries, (int64_t)n, &test, stop_at, &host_out));
+  }
+  /* Not in the reference's class: collision queries for n oriented boxes (host_boxes[n][12]: centre xyz, then the half-axes h0, h1, h2 xyz, in
+   * sub-units of 1 / SE_HIP_ORIENTED_SUB voxel), exact for the box given -- se_hip_collide_oriented_host, definitions in se_hip.h.
+   * host_status[n] receives 0 occupied, 1 unseen, 2 empty, 255 invalid box.  The answers are those of se::geometry::oriented_status
+   * (include/se/oriented_collision.hpp) on the getMap() snapshot. */
+  bool collidesOriented(const int32_t* host_boxes, size_t n, const se_hip_collide_test& test, uint8_t* host_status) {
+    return ok(se_hip_collide_oriented_host(h_, host_boxes, (int64_t)n, &test, host_status));
+  }
+  /* The twelve int32 of one such box from a metric one: box_to_world holds the box's axes in the columns of its rotation and its centre in
+   * its translation (metres), half_extents_m the half lengths along those axes.  The centre and the three scaled columns are rounded to the
+   * nearest sub-unit; the query is exact for the rounded box, which lies within sqrt(3) / 8 voxel of the one asked for
+   * (se::geometry::oriented_box_round of include/se/oriented_collision.hpp does the same on plain arrays). */
+  void orientedBox(const Eigen::Matrix4f& box_to_world, const Eigen::Vector3f& half_extents_m, int32_t out[12]) const {
+    const double scale = (double)SE_HIP_ORIENTED_SUB * volume_resolution_.x() / volume_dimension_.x();
+    for (int k = 0; k < 3; ++k) out[k] = (int32_t)std::nearbyint(box_to_world(k, 3) * scale);
+    for (int i = 0; i < 3; ++i)
+      for (int k = 0; k < 3; ++k) out[3 + 3 * i + k] = (int32_t)std::nearbyint((double)box_to_world(k, i) * half_extents_m(i) * scale);
   }
   /* Not in the reference's class (an addition of this mirror): se::functor::axis_aligned_map(map, f, min, max) for a list of n boxes with
    * f = "assign x and / or y where the current value has one of these classes", applied to the device map in list order without save / load --

@@ -455,6 +455,45 @@ int se_hip_clearance_boxes(se_hip_pipeline* p, const int32_t* device_queries, in
 int se_hip_clearance_boxes_host(se_hip_pipeline* p, const int32_t* host_queries, int64_t n, const se_hip_collide_test* test, int32_t stop_at,
                                 const se_hip_clearance_out* host_out);
 
+/* ---- batched collision queries for oriented boxes: "does this robot, at this attitude, touch anything?" for N boxes at once, without
+ *      getMap().  Not in the reference; built on its Octree::get and on the classification above.  The host restatement and the literal
+ *      definition are include/se/oriented_collision.hpp.
+ * Units: SE_HIP_ORIENTED_SUB = 16 sub-units per voxel.
+ * Box: twelve int32, centre c xyz, then the half-axes h0, h1, h2 xyz, all in sub-units (boxes [n][12]).  The box is the open set
+ *     { c + s0 h0 + s1 h1 + s2 h2 : |s_i| < 1 }.
+ *   The half-axes need not be orthogonal and may have either handedness: a rotation matrix rounded to fixed point is not exactly
+ *   orthogonal, and the test does not need it to be.
+ * Touched: take a cube with integer corner v and side s in voxels (a voxel: s = 1).  In doubled sub-units,
+ *     m = 32 v + 16 s - 2 c   is the doubled offset from the box centre to the cube centre, and   e = 16 s   the doubled half-side of the cube.
+ *   An integer axis a separates iff   a != 0   and   |a . m| >= 2 sum_i |a . h_i| + e sum_k |a_k|.
+ *   The cube is touched iff none of these 15 axes separates: e_x, e_y, e_z, then h1 x h2, h2 x h0, h0 x h1, then h_i x e_k for the nine (i, k).
+ *   The inequalities are open: a face, an edge or a vertex that only meets a voxel's boundary touches nothing.  The a != 0 clause is part of
+ *   the definition: a half-axis parallel to a cube edge gives zero cross products, and without the clause 0 >= 0 would separate everything.
+ *   For h_i = r_i e_i with c +- r on voxel boundaries the touched voxels are exactly those of the half-open box of SE_HIP_COLLIDE_STRICT.
+ * Exactness: nothing is rounded.  With the bounds below and sizes up to 8192, a component of a cross product is a difference of two products
+ *   of half-axis components: |a_k| <= 2 * 2^14 * 2^14 = 2^29, which fits int32.  |m_k| <= 32 * 8192 + 16 * 8192 + 2 * 2^20 < 2^22, so
+ *   |a . m| <= 3 * 2^29 * 2^22 < 2^53.  On the right, sum_i |a . h_i| is |det(h0, h1, h2)| <= 6 * 2^42 for a face normal, at most
+ *   2 * 2 * 2^28 = 2^30 for an edge cross product and 3 * 2^14 for a unit axis, and e sum_k |a_k| <= 2^17 * 3 * 2^29 < 2^47.6: every
+ *   right-hand side stays below 2^49.  Everything is evaluated in int64.
+ * A box is invalid if det(h0, h1, h2) == 0, if any |c_k| > 2^20, or if any |h_ik| > 2^14.  An invalid box gets status
+ *   SE_HIP_COLLISION_INVALID and reads no map memory.
+ * Status: the min over the touched voxels of classify(Octree::get(v)), exactly as in strict mode -- the voxel itself, or value_[child] of the
+ *   deepest existing node; a pending index entry counts as absent; every voxel outside [0, size)^3 is unseen.  The box touches a voxel
+ *   outside the volume iff, for some k, c_k - sum_i |h_ik| < 0 or c_k + sum_i |h_ik| > 16 size: no traversal is needed for that.  An absent
+ *   touched octant folds classify(value_[child]), which is exact: an open set that meets an open cube meets the open cube of one of its voxels.
+ * Both entries answer for the map after everything enqueued before them (a scan that ran on the side stream included), refuse n < 0, a null
+ * boxes or status pointer with n > 0, a null test, a non-finite threshold and occupied_above other than 0 / 1 with SE_HIP_E_INVALID
+ * (n == 0 is a no-op), report a sticky SE_HIP_E_CAPACITY like the other read-back calls, and leave the map, the images and the launch
+ * counters (SE_HIP_K_*) alone.
+ *   se_hip_collide_oriented       device arrays (boxes [n][12] int32, status [n] uint8); enqueued on the handle's stream, asynchronous like
+ *                                 the stage calls.
+ *   se_hip_collide_oriented_host  host arrays; staged through a device buffer the handle keeps (and grows); synchronises before it returns. */
+#define SE_HIP_ORIENTED_SUB 16
+#define SE_HIP_ORIENTED_CENTRE_LIMIT (1 << 20)
+#define SE_HIP_ORIENTED_AXIS_LIMIT (1 << 14)
+int se_hip_collide_oriented(se_hip_pipeline* p, const int32_t* device_boxes, int64_t n, const se_hip_collide_test* test, uint8_t* device_status);
+int se_hip_collide_oriented_host(se_hip_pipeline* p, const int32_t* host_boxes, int64_t n, const se_hip_collide_test* test, uint8_t* host_status);
+
 /* ---- batched ray casts against the resident map: the per-pixel body of the reference's raycastKernel (se_denseslam/src/rendering.cpp:51-90)
  *      for N rays of the caller's at once, without getMap() -- simulated range sensors, line-of-sight checks, views from poses that are not
  *      the tracked camera's.

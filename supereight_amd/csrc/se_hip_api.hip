@@ -26,6 +26,7 @@
 #include "se_query_kernels.h"
 #include "se_collide_kernels.h"
 #include "se_motion_kernels.h"
+#include "se_oriented_kernels.h"
 #include "se_clearance_kernels.h"
 #include "se_edit_kernels.h"
 #include "se_alloc_kernels.h"
@@ -581,7 +582,7 @@ int batch_host(se_hip_pipeline* p, const void* in, size_t in_item_bytes, int64_t
   // (synchronises; a sticky overflow is reported as the other read-back calls report it)
   return fetch_counters(p);
 }
-// The launch of the wave-per-item query kernels (boxes, motions, clearance): grid-stride beyond 2^20 workgroups, one instantiation per brick layout.
+// The launch of the wave-per-item query kernels (boxes, motions, clearance, oriented boxes): grid-stride beyond 2^20 workgroups, one instantiation per brick layout.
 template <class Args>
 void launch_wave_per_item(se_hip_pipeline* p, int64_t n, void (*dense)(DevMap, Args), void (*pooled)(DevMap, Args), const Args& a) {
   const int grid = (int)std::min<int64_t>(n, 1 << 20);
@@ -2259,6 +2260,33 @@ int se_hip_clearance_boxes_host(se_hip_pipeline* p, const int32_t* host_queries,
                                 const se_hip_clearance_out* host_out) {
   return batch_host(p, host_queries, 7 * sizeof(int32_t), n, clearance_outs(host_out), [&] { return clearance_args(host_queries, n, test, stop_at, host_out); },
                     [&](const void* q, void* const* o) { launch_clearance(p, (const int32_t*)q, n, test, stop_at, o); });
+}
+
+
+// ------------------------------------------------------------------------------------ oriented box collision queries
+static_assert(SE_HIP_ORIENTED_SUB == SE_ORIENTED_SUB, "sub-units of se_hip_collide_oriented");
+namespace {
+int oriented_args(const int32_t* boxes, int64_t n, const se_hip_collide_test* test, const uint8_t* status) {
+  if (n < 0) return fail(SE_HIP_E_INVALID, "se_hip_collide_oriented: n < 0");
+  if (n > 0 && (!boxes || !status)) return fail(SE_HIP_E_INVALID, "se_hip_collide_oriented: null boxes or status");
+  return collide_test_args("se_hip_collide_oriented", test, nullptr);
+}
+void launch_oriented(se_hip_pipeline* p, const int32_t* boxes, int64_t n, const se_hip_collide_test* test, uint8_t* status) {
+  const OrientedArgs a{boxes, (long long)n, status, test->threshold, test->occupied_above};
+  launch_wave_per_item(p, n, k_collide_oriented<true>, k_collide_oriented<false>, a);
+}
+}  // namespace
+
+int se_hip_collide_oriented(se_hip_pipeline* p, const int32_t* device_boxes, int64_t n, const se_hip_collide_test* test, uint8_t* device_status) {
+  const BatchOuts out{1, {{device_status, 1}}};
+  return batch_device(p, device_boxes, n, out, [&] { return oriented_args(device_boxes, n, test, device_status); },
+                      [&](const void* boxes, void* const* o) { launch_oriented(p, (const int32_t*)boxes, n, test, (uint8_t*)o[0]); });
+}
+
+int se_hip_collide_oriented_host(se_hip_pipeline* p, const int32_t* host_boxes, int64_t n, const se_hip_collide_test* test, uint8_t* host_status) {
+  const BatchOuts out{1, {{host_status, 1}}};
+  return batch_host(p, host_boxes, 12 * sizeof(int32_t), n, out, [&] { return oriented_args(host_boxes, n, test, host_status); },
+                    [&](const void* boxes, void* const* o) { launch_oriented(p, (const int32_t*)boxes, n, test, (uint8_t*)o[0]); });
 }
 
 

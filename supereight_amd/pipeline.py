@@ -95,6 +95,37 @@ CLEARANCE_NONE, CLEARANCE_INVALID = -1, -2
 _CLEARANCE_R_CLAMP = 32768   # an r_max above 32767 is invalid: larger ones are passed as this one, so that they fit the int32 column
 
 
+# se_hip_collide_oriented: sub-units per voxel, and the bounds of a valid box (|c_k|, |h_ik|, in sub-units)
+ORIENTED_SUB, ORIENTED_CENTRE_LIMIT, ORIENTED_AXIS_LIMIT = 16, 1 << 20, 1 << 14
+
+
+def oriented_boxes(centres_m, rotations, half_extents_m, dim, size):
+    """The int32 [N, 12] boxes of DenseSLAMPipeline.collides_oriented from metric ones: centres_m [N, 3] in metres, rotations [N, 3, 3] (box
+    frame to world; column i is the direction of the box's axis i), half_extents_m [N, 3] in metres, for a volume of `size` voxels over `dim`
+    metres.  The centre and the scaled columns half_extents_m[i] * rotations[:, :, i] are rounded to the nearest sub-unit (1 / ORIENTED_SUB
+    voxel).  The query's answer is exact for the rounded box: each of the four vectors moves by at most sqrt(3) / 2 sub-unit, so every point
+    of the rounded box lies within 4 * sqrt(3) / 32 = sqrt(3) / 8 voxel of the corresponding point of the box asked for.  Values beyond int32
+    are clamped to it (such a box is invalid anyway)."""
+    c = np.asarray(centres_m, np.float64)
+    r = np.asarray(rotations, np.float64)
+    e = np.asarray(half_extents_m, np.float64)
+    if c.ndim != 2 or c.shape[1] != 3:
+        raise ValueError(f"oriented_boxes: centres_m must have shape [N, 3], got {list(c.shape)}")
+    n = c.shape[0]
+    if r.shape != (n, 3, 3):
+        raise ValueError(f"oriented_boxes: rotations must have shape [{n}, 3, 3], got {list(r.shape)}")
+    if e.shape != (n, 3):
+        raise ValueError(f"oriented_boxes: half_extents_m must have shape [{n}, 3], got {list(e.shape)}")
+    if not (np.isfinite(c).all() and np.isfinite(r).all() and np.isfinite(e).all()):
+        raise ValueError("oriented_boxes: non-finite input")
+    scale = ORIENTED_SUB * float(size) / float(dim)
+    out = np.empty((n, 12), np.float64)
+    out[:, 0:3] = c * scale
+    for i in range(3):
+        out[:, 3 + 3 * i:6 + 3 * i] = r[:, :, i] * e[:, i:i + 1] * scale
+    return np.clip(np.rint(out), -(2 ** 31), 2 ** 31 - 1).astype(np.int32)
+
+
 class _Edit(C.Structure):
     """se_hip_edit of include/se_hip.h (40 bytes)."""
     _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("x", C.c_float), ("y", C.c_float), ("flags", C.c_uint32), ("only", C.c_uint32)]
@@ -195,6 +226,8 @@ EXPORTS = {
     "se_hip_collide_motions_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_MotionOut)]),
     "se_hip_clearance_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_ClearanceOut)]),
     "se_hip_clearance_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_ClearanceOut)]),
+    "se_hip_collide_oriented": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_void_p]),
+    "se_hip_collide_oriented_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_void_p]),
     "se_hip_edit_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
     "se_hip_edit_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
     "se_hip_allocate_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
@@ -765,6 +798,34 @@ class DenseSLAMPipeline:
             self._device_call(torch, mo.device, self.lib.se_hip_collide_motions, mo.data_ptr() if n else None, n, C.byref(test), _MOTION_STOPS[stop_at],
                               C.byref(out))
         return (res["status"], res["t_first"]) if t_first else res["status"]
+
+    def collides_oriented(self, boxes, threshold: float = 0.0, occupied_above=None):
+        """Batched collision queries for oriented boxes (se_hip_collide_oriented, include/se_hip.h): boxes [N, 12] int32 = centre xyz, then the
+        half-axes h0, h1, h2 xyz, in sub-units of 1 / ORIENTED_SUB voxel (oriented_boxes() makes them from metric ones).  The box is the open set
+        {c + s0 h0 + s1 h1 + s2 h2 : |s_i| < 1}; the half-axes need not be orthogonal.  Exact: a voxel counts iff the box touches it (an integer
+        separating-axis test, open inequalities), and is classified as collides() classifies it in strict mode (threshold / occupied_above as
+        there; outside the volume is unseen).  Returns one status per box: the min class over the touched voxels, COLLISION_INVALID for
+        det(h0, h1, h2) == 0, |c_k| > 2^20 or |h_ik| > 2^14.
+          - numpy int32 [N, 12]: through the host entry; a numpy uint8 array out.
+          - a torch int32 tensor on this handle's GPU (contiguous, [N, 12]): through the device entry; a torch uint8 tensor on the same
+            device out.  The caller's current torch stream is synchronised first, and the handle before the tensor is returned.
+        Anything else raises TypeError / ValueError before any library call."""
+        if occupied_above is None:
+            occupied_above = self.field == OFUSION
+        if not isinstance(occupied_above, (bool, np.bool_)):
+            raise TypeError(f"collides_oriented: occupied_above must be a bool, got {type(occupied_above).__name__}")
+        thr = float(threshold)
+        if not np.isfinite(np.float32(thr)):
+            raise ValueError(f"collides_oriented: threshold must be finite as a float32, got {threshold!r}")
+        test = _CollideTest(thr, int(bool(occupied_above)))
+        torch, b, n = self._batch_input("collides_oriented", "boxes", boxes, np.int32, 12)
+        out = np.empty(n, np.uint8) if torch is None else torch.empty(n, dtype=torch.uint8, device=b.device)
+        if torch is None:
+            self._check(self.lib.se_hip_collide_oriented_host(self._h, b.ctypes.data if n else None, n, C.byref(test), out.ctypes.data if n else None))
+        else:
+            self._device_call(torch, b.device, self.lib.se_hip_collide_oriented, b.data_ptr() if n else None, n, C.byref(test),
+                              out.data_ptr() if n else None)
+        return out
 
     _CLEARANCE_OUTPUTS = (("d2", (), np.int32), ("nearest", (3,), np.int32))
 
