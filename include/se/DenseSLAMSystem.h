@@ -263,6 +263,17 @@ class DenseSLAMSystem {
     }
     return true;
   }
+  /* Not in the reference's class (an addition of this mirror): the content of another pipeline's map (same device, field type and voxel size; any
+   * volume size) folded into this one on the device, source content at voxel c meeting this map's at c + shift_voxels (multiples of 8) --
+   * se_hip_merge_map, definitions in se_hip.h.  The map afterwards is what se::merge_map (include/se/merge_map.hpp) makes of the two getMap()
+   * snapshots taken before.  rule: SE_HIP_MERGE_FUSE / _REPLACE / _FILL and the SDF weight cap (default: FUSE, 100).  counts[12] (optional):
+   * blocks combined, created, clipped, nodes combined, created, skipped, lo[3] and hi[3] of the voxel box of the blocks touched.  `other` is only
+   * read; the poses and the vertex / normal images of both pipelines stay as they are (tracking goes on). */
+  bool mergeMap(DenseSLAMSystem& other, const Eigen::Vector3i& shift_voxels = Eigen::Vector3i(0, 0, 0),
+                const se_hip_merge_rule& rule = se_hip_merge_rule{SE_HIP_MERGE_FUSE, 100.f}, int64_t* counts = nullptr) {
+    const int32_t s[3] = {shift_voxels.x(), shift_voxels.y(), shift_voxels.z()};
+    return ok(se_hip_merge_map(h_, other.h_, s, &rule, counts));
+  }
   /* Not in the reference's class (an addition of this mirror): the per-pixel body of raycastKernel for n rays of the caller's
    * (host_rays[n][8]: origin xyz, direction xyz, near, far in metres) answered on the device map without getMap() --
    * se_hip_cast_rays_host, definitions in se_hip.h.  host_out.hit[n][4], .normal[n][3], .status[n]; a null pointer: not wanted. */

@@ -582,6 +582,48 @@ int se_hip_load_map(se_hip_pipeline* p, const char* filename);
  *      sharded sweep) each hold the whole map: the same call goes to every one of them. */
 int se_hip_shift_map(se_hip_pipeline* p, const int32_t shift_voxels[3], int64_t* host_counts);
 
+/* ---- map merge: the content of one resident map (src) folded into another (dst) on the device, optionally moved by a whole number of blocks (no
+ *      reference counterpart: the reference holds one map).  The executable definition is se::merge_map / se::merge_value of
+ *      include/se/merge_map.hpp on two getMap() snapshots.  s = shift_voxels: source content at voxel c meets destination content at c + s.
+ *        arguments  SE_HIP_E_INVALID, both maps untouched (a held-back raycast of either handle may have been launched by then): dst == src; different
+ *                   devices; different field types; different voxel size (dim / size, a binary32 division, not bit-equal); a component of s that is
+ *                   not a multiple of 8 or lies outside [-2^30, 2^30]; a null rule, an unknown mode, a max_weight that is not an integer in
+ *                   [1, 255] (checked for both field types, used by SDF only).  The volume sizes may differ.  A source with a sticky
+ *                   SE_HIP_E_CAPACITY is refused with that code: it is not the map the reference would hold
+ *        unseen     a value v with v.x == initValue().x && v.y == initValue().y (y compared as float), as the collision queries mean it
+ *        values     a = destination value, b = source value, for block voxels and node value_[j] alike:
+ *                     b unseen                   a stays, bit for bit, in every mode
+ *                     a unseen, or REPLACE       b, bit for bit; SDF: y = fminf(b.y, max_weight)
+ *                     FILL                       a stays
+ *                     FUSE, SDF                  b.y == 0: a stays; a.y == 0: as "a unseen"; else w = a.y + b.y,
+ *                                                x = clamp((a.y * a.x + b.y * b.x) / w, -1, 1), y = fminf(w, max_weight) -- sdf_update's running mean with the
+ *                                                second sample weighing b.y instead of 1; binary32 in that order, no contraction, IEEE division; the
+ *                                                weights are added as floats, never as bytes (200 + 100 gives max_weight)
+ *                     FUSE, OFusion              x = clamp(a.x + b.x, -1000, 1000) (BOTTOM_CLAMP, TOP_CLAMP of volume_traits.hpp: the prior is log-odds 0,
+ *                                                independent evidence adds), y = fmaxf(a.y, b.y)
+ *                   clamp(v, lo, hi) = std::max(lo, std::min(v, hi)), as everywhere in the library
+ *        blocks     the source block with corner c takes part iff c + s lies in [0, dst size - 8] on every axis, else it is clipped.  Its block in dst
+ *                   is created if absent, with all missing ancestors and initValue() (Octree::allocate, without the keys[0] rule); the 512 values are
+ *                   combined; active = the OR of the two flags, a created block is active, as insertion leaves it
+ *        nodes      the source node of side d (level >= 1, childless ones included) and corner c takes part iff every component of s is a multiple
+ *                   of d and c + s lies in [0, dst size - d]; its level is the one of side d in dst.  It is created if absent and its value_[8] are
+ *                   combined.  Any other source node contributes nothing (skipped).  The source root takes part only if s == 0 and the sizes are
+ *                   equal.  Coarse values meet coarse values only: a source node value is never pushed down into destination voxels
+ *        counts     (optional, host, int64[12]) blocks combined into existing blocks, blocks created, source blocks clipped, nodes combined into
+ *                   existing nodes, nodes created for source nodes, source nodes skipped, lo[3] and hi[3] of the destination voxel box that holds
+ *                   every block that took part (half open; all zero if none).  Ancestors created on the way follow from se_hip_counts
+ *      On both handles a held-back raycast is launched first and a scan on the side stream is joined; both are synchronised before the first kernel,
+ *      which runs on dst's stream, and the call returns synchronised.  src is only read.  dst's vertex_ / normal_ stay valid (its frame of reference
+ *      did not move: tracking goes on).  A destination pool that runs out raises the usual sticky SE_HIP_E_CAPACITY; a source block whose
+ *      destination found no slot is skipped.  No launch counter and no timing sum changes.  The staging is 12 bytes per source block and node.
+ *      Replicas each hold the whole map: the same call goes to every one of them.  Across devices: save, load into a scratch handle, merge. */
+#define SE_HIP_MERGE_FUSE    0   /* both observed: combine */
+#define SE_HIP_MERGE_REPLACE 1   /* source wins wherever the source is observed */
+#define SE_HIP_MERGE_FILL    2   /* destination wins; source only where destination is unseen */
+typedef struct se_hip_merge_rule { int32_t mode; float max_weight; /* SDF only; integer in [1, 255]; mirrors default to 100 */ } se_hip_merge_rule;
+int se_hip_merge_map(se_hip_pipeline* dst, se_hip_pipeline* src, const int32_t shift_voxels[3],
+                     const se_hip_merge_rule* rule, int64_t* host_counts /* optional, [12] */);
+
 /* ---- map export, second half: marching cubes over the allocated blocks
  * DenseSLAMSystem::dump_mesh (DenseSLAMSystem.cpp:302-322) = se::algorithms::marching_cube
  * (se_core/include/se/algorithms/meshing.hpp:161-208) with inside(v) = v.x < 0, select(v) = v.x, then writeVtkMesh

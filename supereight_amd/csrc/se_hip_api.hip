@@ -32,6 +32,7 @@
 #include "se_alloc_kernels.h"
 #include "se_ray_kernels.h"
 #include "se_shift_kernels.h"
+#include "se_merge_kernels.h"
 
 int flush_pending_raycast(se_hip_pipeline* p);   // (defined next to se_hip_frame)
 
@@ -2668,6 +2669,80 @@ int se_hip_shift_map(se_hip_pipeline* p, const int32_t shift_voxels[3], int64_t*
   if (host_counts) {
     host_counts[0] = (int64_t)kept[0]; host_counts[1] = (int64_t)(nb - kept[0]);
     host_counts[2] = (int64_t)kept[1]; host_counts[3] = (int64_t)(nn - kept[1]);   // (the root gave up its values: dropped)
+  }
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------ map merge
+static_assert(SE_HIP_MERGE_FUSE == SE_MERGE_FUSE && SE_HIP_MERGE_REPLACE == SE_MERGE_REPLACE && SE_HIP_MERGE_FILL == SE_MERGE_FILL, "modes of se_hip_merge_rule");
+// The steps of se_merge_kernels.h on dst's stream, between two synchronisations of both handles: both maps are quiescent when the first kernel starts
+// (held-back raycasts launched by check(), scans joined, all four streams idle); src is only read.
+int se_hip_merge_map(se_hip_pipeline* dst, se_hip_pipeline* src, const int32_t shift_voxels[3], const se_hip_merge_rule* rule, int64_t* host_counts) {
+  if (!dst || !src) return fail(SE_HIP_E_INVALID, "null handle");
+  if (dst == src) return fail(SE_HIP_E_INVALID, "se_hip_merge_map: dst == src");
+  if (dst->device != src->device) return fail(SE_HIP_E_INVALID, "se_hip_merge_map: the handles live on different devices (save, load into a scratch handle on dst's device, merge)");
+  if (dst->cfg.field_type != src->cfg.field_type) return fail(SE_HIP_E_INVALID, "se_hip_merge_map: different field types");
+  {
+    const float va = dst->map.dim / (float)dst->map.size, vb = src->map.dim / (float)src->map.size;
+    if (std::memcmp(&va, &vb, sizeof va) != 0) return fail(SE_HIP_E_INVALID, "se_hip_merge_map: different voxel sizes (dim / size)");
+  }
+  if (!shift_voxels) return fail(SE_HIP_E_INVALID, "se_hip_merge_map: null shift");
+  for (int k = 0; k < 3; ++k) {
+    if (shift_voxels[k] < -SE_SHIFT_LIMIT || shift_voxels[k] > SE_SHIFT_LIMIT) return fail(SE_HIP_E_INVALID, "se_hip_merge_map: a component outside [-2^30, 2^30]");
+    if (shift_voxels[k] & 7) return fail(SE_HIP_E_INVALID, "se_hip_merge_map: a component is not a multiple of 8 (the block side)");
+  }
+  if (!rule) return fail(SE_HIP_E_INVALID, "se_hip_merge_map: null rule");
+  if (rule->mode != SE_HIP_MERGE_FUSE && rule->mode != SE_HIP_MERGE_REPLACE && rule->mode != SE_HIP_MERGE_FILL) return fail(SE_HIP_E_INVALID, "se_hip_merge_map: unknown mode");
+  if (!(rule->max_weight >= 1.f && rule->max_weight <= 255.f && rule->max_weight == (float)(int)rule->max_weight))
+    return fail(SE_HIP_E_INVALID, "se_hip_merge_map: max_weight is not an integer in [1, 255]");
+  if (int r = check(src)) return r;
+  if (int r = check(dst)) return r;
+  if (int r = fetch_counters(src)) return r;   // (joins a scan, synchronises the main stream; a sticky overflow of the source refuses the call)
+  if (src->side) HIP_TRY(hipStreamSynchronize(src->side));
+  if (int r = fetch_counters(dst)) return r;
+  if (dst->side) HIP_TRY(hipStreamSynchronize(dst->side));
+  src->gate_armed = false; dst->gate_armed = false;
+  const DevMap& d = dst->map;
+  const DevMap& m = src->map;
+  const size_t nb = std::min<size_t>(src->ctr_host[C_BLOCKS], src->cap_blocks), nn = std::min<size_t>(src->ctr_host[C_NODES], src->cap_nodes);
+  const uint32_t nb0 = dst->ctr_host[C_BLOCKS];
+  // staging (dst's): [block keys][node keys][nodes created][source positions of the blocks][... of the nodes][box]
+  const size_t bytes[6] = {(nb + 1) * 8, (nn + 1) * 8, 8, nb * sizeof(uint32_t), nn * sizeof(uint32_t), 6 * sizeof(int)};
+  size_t off[6];
+  if (int r = reserve_staging(dst, staging_layout(bytes, 6, off))) return r;
+  unsigned char* b = dst->staging;
+  MergeArgs a{};
+  for (int k = 0; k < 3; ++k) a.s[k] = shift_voxels[k];
+  a.mode = rule->mode; a.max_weight = rule->max_weight;
+  a.dlevel = d.max_level - m.max_level;
+  a.nb = (uint32_t)nb; a.nn = (uint32_t)nn;
+  a.blist = (unsigned long long*)(b + off[0]); a.nlist = (unsigned long long*)(b + off[1]); a.ncreated = (unsigned long long*)(b + off[2]);
+  a.bsrc = (uint32_t*)(b + off[3]); a.nsrc = (uint32_t*)(b + off[4]); a.box = (int*)(b + off[5]);
+  const int box0[6] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN};
+  hipStream_t st = dst->stream;
+  HIP_TRY(hipMemsetAsync(a.blist, 0, sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(a.nlist, 0, sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(a.ncreated, 0, sizeof(unsigned long long), st));
+  HIP_TRY(hipMemcpyAsync(a.box, box0, sizeof box0, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_merge_select, dim3(grid_for(std::max(nb, nn), SE_WG, 2048)), dim3(SE_WG), 0, st, d, m, a);
+  hipLaunchKernelGGL(k_alloc_commit, dim3(256, 1), dim3(SE_WG), 0, st, d, a.nlist, 1, (long long)(nn + 1));
+  hipLaunchKernelGGL(k_alloc_commit, dim3(256, 1), dim3(SE_WG), 0, st, d, a.blist, 1, (long long)(nb + 1));
+  const int waves_grid = grid_for(std::max(nb * 64, nn * 8), SE_WG, 8192);
+  if (dst->cfg.field_type == SE_HIP_FIELD_OFUSION) hipLaunchKernelGGL(k_merge_bricks<true>, dim3(waves_grid), dim3(SE_WG), 0, st, d, m, a);
+  else hipLaunchKernelGGL(k_merge_bricks<false>, dim3(waves_grid), dim3(SE_WG), 0, st, d, m, a);
+  HIP_TRY(hipGetLastError());
+  unsigned long long took[3] = {0, 0, 0};
+  int box[6] = {0, 0, 0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(&took[0], a.blist, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&took[1], a.nlist, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&took[2], a.ncreated, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(box, a.box, sizeof box, hipMemcpyDeviceToHost, st));
+  const int rc = fetch_counters(dst);   // (the counter mirror refreshed in stream order; synchronises; a pool that ran out: SE_HIP_E_CAPACITY, sticky)
+  if (host_counts) {
+    const int64_t created = (int64_t)std::min<uint32_t>(dst->ctr_host[C_BLOCKS], (uint32_t)dst->cap_blocks) - (int64_t)nb0;   // (only source blocks insert leaves)
+    host_counts[0] = (int64_t)took[0] - created; host_counts[1] = created; host_counts[2] = (int64_t)(nb - took[0]);
+    host_counts[3] = (int64_t)(took[1] - took[2]); host_counts[4] = (int64_t)took[2]; host_counts[5] = (int64_t)(nn - took[1]);
+    for (int k = 0; k < 6; ++k) host_counts[6 + k] = took[0] ? (int64_t)box[k] : 0;
   }
   return rc;
 }

@@ -155,6 +155,10 @@ class _Config(C.Structure):
                 ("max_blocks", C.c_int64), ("row_begin", C.c_int32), ("row_end", C.c_int32)]
 
 
+class _MergeRule(C.Structure):      # se_hip_merge_rule
+    _fields_ = [("mode", C.c_int32), ("max_weight", C.c_float)]
+
+
 EXPORTS = {
     "se_hip_create": (C.c_int, [C.POINTER(_Config), C.POINTER(C.c_void_p)]),
     "se_hip_destroy": (C.c_int, [C.c_void_p]),
@@ -207,6 +211,7 @@ EXPORTS = {
     "se_hip_save_map": (C.c_int, [C.c_void_p, C.c_char_p]),
     "se_hip_load_map": (C.c_int, [C.c_void_p, C.c_char_p]),
     "se_hip_shift_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "se_hip_merge_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "se_hip_create_replicas": (C.c_int, [C.POINTER(_Config), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]),
     "se_hip_mesh_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "se_hip_mesh_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
@@ -1238,6 +1243,51 @@ class DenseSLAMPipeline:
         pose[:3, 3] += s.astype(np.float32) * (np.float32(self.dim) / np.float32(self.size))
         self.pose_ = pose
         return out
+
+    MERGE_MODES = {"fuse": 0, "replace": 1, "fill": 2}      # SE_HIP_MERGE_*
+    MERGE_COUNTS = ("blocks_combined", "blocks_created", "blocks_clipped", "nodes_combined", "nodes_created", "nodes_skipped")
+
+    def _merge_arguments(self, src, shift, mode, max_weight):
+        """The arguments of merge(), checked (TypeError / ValueError) before any library call: (int32 shift [3], rule)."""
+        if not isinstance(src, DenseSLAMPipeline):
+            raise TypeError(f"merge: src must be a DenseSLAMPipeline, got {type(src).__name__}")
+        if src is self:
+            raise ValueError("merge: src is the destination itself")
+        if src.field != self.field:
+            raise ValueError("merge: the two maps hold different field types")
+        if src._device != self._device:
+            raise ValueError("merge: the two maps live on different devices (save, load into a scratch handle on this device, merge)")
+        if np.float32(src.dim) / np.float32(src.size) != np.float32(self.dim) / np.float32(self.size):
+            raise ValueError(f"merge: different voxel sizes ({src.dim} / {src.size} and {self.dim} / {self.size})")
+        try:
+            s = self._shift_argument(shift)
+        except (TypeError, ValueError) as e:
+            raise type(e)(str(e).replace("shift:", "merge:", 1)) from None
+        if not isinstance(mode, str):
+            raise TypeError(f"merge: mode must be one of {sorted(self.MERGE_MODES)}, got {type(mode).__name__}")
+        if mode not in self.MERGE_MODES:
+            raise ValueError(f"merge: mode must be one of {sorted(self.MERGE_MODES)}, got {mode!r}")
+        if isinstance(max_weight, (bool, np.bool_)) or not isinstance(max_weight, (int, float, np.integer, np.floating)):
+            raise TypeError(f"merge: max_weight must be a number, got {type(max_weight).__name__}")
+        if not (1 <= max_weight <= 255 and float(max_weight) == int(max_weight)):
+            raise ValueError(f"merge: max_weight must be an integer in [1, 255], got {max_weight}")
+        return s, _MergeRule(self.MERGE_MODES[mode], float(max_weight))
+
+    def merge(self, src, shift=(0, 0, 0), mode: str = "fuse", max_weight=100) -> dict:
+        """The content of `src` (another handle on the same device: same field type and voxel size, any volume size) folded into this map on
+        the device (se_hip_merge_map, include/se_hip.h): source content at voxel c meets this map's content at c + shift (multiples of 8).
+        mode "fuse" combines where both are observed (SDF: weighted mean, weights added and capped at max_weight; OFusion: log-odds added,
+        the later time), "replace" lets the source win wherever it is observed, "fill" takes the source only where this map is unseen.
+        `src` is only read; this map's vertex / normal images stay valid.  Returns the counts as a dict: blocks_combined, blocks_created,
+        blocks_clipped, nodes_combined, nodes_created, nodes_skipped and region = (lo, hi), the half-open voxel box of this map that holds
+        every block touched (zeros if none; a LiveMesh is brought up to date with update(pipe, region=(lo - 1, hi)), as after an edit).
+        Wrong arguments raise before any library call."""
+        s, rule = self._merge_arguments(src, shift, mode, max_weight)
+        out = np.zeros(12, np.int64)
+        self._check(self.lib.se_hip_merge_map(self._h, src._h, s.ctypes.data, C.addressof(rule), out.ctypes.data))
+        res = {k: int(v) for k, v in zip(self.MERGE_COUNTS, out[:6])}
+        res["region"] = (tuple(int(v) for v in out[6:9]), tuple(int(v) for v in out[9:12]))
+        return res
 
     # ------------------------------------------------------------------ measurement
     def enable_timing(self, on: bool = True):
