@@ -579,7 +579,12 @@ int se_hip_load_map(se_hip_pipeline* p, const char* filename);
  *      se_hip_frame_tracked return SE_HIP_E_INVALID ("vertex / normal images predate a map shift") until a raycast has run; se_hip_render_volume
  *      casts its own rays until then.  Poses are the caller's: after the call it passes poses translated by s * dim / size.
  *      A node pool that runs out while the ancestors are rebuilt raises the usual sticky SE_HIP_E_CAPACITY.  Replicas (row-sharded,
- *      sharded sweep) each hold the whole map: the same call goes to every one of them. */
+ *      sharded sweep) each hold the whole map: the same call goes to every one of them.
+ *      Between the scan and the sweep of a frame (se_hip_alloc_scan ... se_hip_integrate_sweep) the call is allowed: the scan is joined, so the
+ *      blocks it inserted exist, are active and move with the map like any other; their occupancy bits and beam-start marks come from the
+ *      rebuild above, and the sweep owes the scan no commit any more.  The sweep that follows takes the pose
+ *      the caller passes -- translated by s * dim / size -- and integrates the frame into the shifted map (tests/test_gpu_op_programs.py,
+ *      program staged_shift_merge, against the oracle). */
 int se_hip_shift_map(se_hip_pipeline* p, const int32_t shift_voxels[3], int64_t* host_counts);
 
 /* ---- map merge: the content of one resident map (src) folded into another (dst) on the device, optionally moved by a whole number of blocks (no
@@ -616,7 +621,12 @@ int se_hip_shift_map(se_hip_pipeline* p, const int32_t shift_voxels[3], int64_t*
  *      which runs on dst's stream, and the call returns synchronised.  src is only read.  dst's vertex_ / normal_ stay valid (its frame of reference
  *      did not move: tracking goes on).  A destination pool that runs out raises the usual sticky SE_HIP_E_CAPACITY; a source block whose
  *      destination found no slot is skipped.  No launch counter and no timing sum changes.  The staging is 12 bytes per source block and node.
- *      Replicas each hold the whole map: the same call goes to every one of them.  Across devices: save, load into a scratch handle, merge. */
+ *      Replicas each hold the whole map: the same call goes to every one of them.  Across devices: save, load into a scratch handle, merge.
+ *      Between the scan and the sweep of a frame (se_hip_alloc_scan ... se_hip_integrate_sweep), on dst or on src, the call is allowed: the scan is
+ *      joined, so the blocks it inserted take part like any other (on dst they are combined with, on src they are merged from, holding
+ *      initValue()); joining publishes the occupancy bits and beam-start marks of the scan's keys at once (as every entry point does that joins
+ *      a scan), the merge inserts its own blocks in place, and the sweep that follows owes the scan nothing and integrates the frame into the
+ *      merged map (same test: program staged_shift_merge for dst, test_a_merge_from_a_source_between_its_scan_and_its_sweep for src). */
 #define SE_HIP_MERGE_FUSE    0   /* both observed: combine */
 #define SE_HIP_MERGE_REPLACE 1   /* source wins wherever the source is observed */
 #define SE_HIP_MERGE_FILL    2   /* destination wins; source only where destination is unseen */

@@ -88,6 +88,7 @@ def _declare(lib):
         "so_pipe_scan": (C.c_uint, [vp, c_f32p, c_f32p, c_f32p, f32, C.c_uint]),
         "so_pipe_get_keys": (None, [vp, c_u64p, C.c_uint]),
         "so_pipe_allocate_keys": (None, [vp, c_u64p, C.c_uint]),
+        "so_pipe_insert_octants": (None, [vp, c_u64p, C.c_uint]),
         "so_pipe_activate": (i32, [vp, c_i32p, i32]),
         "so_pipe_sweep": (None, [vp, c_f32p, c_f32p, c_f32p, f32, C.c_uint]),
         "so_pipe_counts": (None, [vp, C.POINTER(i32), C.POINTER(i32)]),
@@ -179,6 +180,13 @@ class OraclePipeline:
     def allocate_keys(self, keys):
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
         self.lib.so_pipe_allocate_keys(self.h, keys, len(keys))
+
+    def insert_octants(self, keys):
+        """Octree::insert per key (code | level): these octants and their ancestors exist afterwards, new blocks active; unlike allocate_keys
+        without the keys[0] rule of unique_multiscale, so any map can be seeded."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        if len(keys):
+            self.lib.so_pipe_insert_octants(self.h, keys, len(keys))
 
     def activate(self, coords) -> int:
         c = np.ascontiguousarray(coords, dtype=np.int32).reshape(-1, 3)
