@@ -274,6 +274,37 @@ class DenseSLAMSystem {
     const int32_t s[3] = {shift_voxels.x(), shift_voxels.y(), shift_voxels.z()};
     return ok(se_hip_merge_map(h_, other.h_, s, &rule, counts));
   }
+  /* Not in the reference's class (an addition of this mirror): the pull transform of se_hip_merge_map_rigid (src_from_dst, row-major 3 x 4, in
+   * voxels) from the metric pose of the source map's frame in the destination's, x_dst = T_dst_src x_src, at voxel size dim / size: inverted and
+   * scaled in double, rounded once.  False if the rotation part has no inverse. */
+  static bool rigidPull(const Eigen::Matrix4f& T_dst_src, float dim, int size, float pull[12]) {
+    double R[3][3], adj[3][3];
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) R[r][c] = (double)T_dst_src(r, c);
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j)
+        adj[j][i] = R[(i + 1) % 3][(j + 1) % 3] * R[(i + 2) % 3][(j + 2) % 3] - R[(i + 1) % 3][(j + 2) % 3] * R[(i + 2) % 3][(j + 1) % 3];
+    const double det = (R[0][0] * adj[0][0] + R[0][1] * adj[1][0]) + R[0][2] * adj[2][0];
+    if (!(det != 0.0)) return false;
+    const double scale = (double)size / (double)dim;
+    for (int r = 0; r < 3; ++r) {
+      double t = 0.0;
+      for (int c = 0; c < 3; ++c) { pull[4 * r + c] = (float)(adj[r][c] / det); t += adj[r][c] / det * (double)T_dst_src(c, 3); }
+      pull[4 * r + 3] = (float)(-t * scale);
+    }
+    return true;
+  }
+  /* Not in the reference's class (an addition of this mirror): the content of another pipeline's map (same device, field type and voxel size)
+   * resampled into this one's lattice under a rigid transform and combined by `rule` -- se_hip_merge_map_rigid, definitions in se_hip.h.
+   * T_dst_src is the metric pose of the other map's frame in this map's.  The map afterwards is what se::merge_map_rigid
+   * (include/se/merge_rigid.hpp) makes of the two getMap() snapshots taken before, with the pull transform of rigidPull.  counts[10] (optional):
+   * blocks that existed and received a sample, blocks created, voxels with a sample, of those observed before, lo[3] and hi[3] of the voxel box
+   * of the blocks that received samples.  `other` is only read; poses and images of both pipelines stay as they are. */
+  bool mergeMapRigid(DenseSLAMSystem& other, const Eigen::Matrix4f& T_dst_src,
+                     const se_hip_merge_rule& rule = se_hip_merge_rule{SE_HIP_MERGE_FUSE, 100.f}, int64_t* counts = nullptr) {
+    float pull[12];
+    if (!rigidPull(T_dst_src, volume_dimension_(0), (int)volume_resolution_(0), pull)) return false;
+    return ok(se_hip_merge_map_rigid(h_, other.h_, pull, &rule, counts));
+  }
   /* Not in the reference's class (an addition of this mirror): the per-pixel body of raycastKernel for n rays of the caller's
    * (host_rays[n][8]: origin xyz, direction xyz, near, far in metres) answered on the device map without getMap() --
    * se_hip_cast_rays_host, definitions in se_hip.h.  host_out.hit[n][4], .normal[n][3], .status[n]; a null pointer: not wanted. */

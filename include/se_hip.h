@@ -634,6 +634,45 @@ typedef struct se_hip_merge_rule { int32_t mode; float max_weight; /* SDF only; 
 int se_hip_merge_map(se_hip_pipeline* dst, se_hip_pipeline* src, const int32_t shift_voxels[3],
                      const se_hip_merge_rule* rule, int64_t* host_counts /* optional, [12] */);
 
+/* ---- map merge under a rigid transform: the content of src resampled into dst's lattice under a rotation and any translation, then combined with
+ *      the same value-pair rule (no reference counterpart).  The executable definition is se::rigid_sample / se::merge_map_rigid of
+ *      include/se/merge_rigid.hpp on two getMap() snapshots.  src_from_dst is the PULL transform, row-major 3 x 4, in voxels: R = its first
+ *      three columns, t = the fourth.  The call never inverts it, so the result is exact for the twelve floats passed (the mirrors build them from
+ *      a metric pose: rigid_pull / rigidPull).
+ *        convention a voxel with integer coordinates v holds the field at position v, in voxels (the library's interp convention: the cell's lower
+ *                   corner is floor(q)); there is no half-voxel offset
+ *        position   for a destination voxel v: q_k = ((R_k0 * vx + R_k1 * vy) + R_k2 * vz) + t_k, binary32 in that order, no contraction;
+ *                   l = floor(q), f = q - floorf(q)
+ *        validity   the sample is valid iff 0 <= l_k and l_k + 1 <= src size - 1 on every axis and none of the eight corner voxels l + {0,1}^3 is
+ *                   unseen.  Corners are read as get_fine reads them (initValue() where the source has no block); "unseen" as above.  A cell with
+ *                   any unseen corner contributes nothing: no extrapolation, no empty() substitution
+ *        value      b.x = the trilinear blend of the corner x values p[i + 2j + 4k] in Octree::interp's term order,
+ *                     ((p0 (1-fx) + p1 fx) (1-fy) + (p2 (1-fx) + p3 fx) fy) (1-fz) + ((p4 (1-fx) + p5 fx) (1-fy) + (p6 (1-fx) + p7 fx) fy) fz;
+ *                   SDF: b.y = the minimum of the eight corner weights (an integer in 0 .. 255); OFusion: b.y = the maximum of the eight corner
+ *                   times.  The sample is observed iff it is valid and b itself is not unseen
+ *        values     every destination voxel with an observed sample becomes merge_value(a, b, mode, max_weight), the table above; every other
+ *                   voxel keeps its bits
+ *        blocks     an absent destination block is created iff at least one of its 512 voxels has an observed sample, with all missing ancestors
+ *                   and initValue() (without the keys[0] rule); no other block is created.  Every destination block that receives at least one
+ *                   observed sample is active afterwards, as insertion leaves a new block
+ *        nodes      source node values never take part (coarse values cannot be resampled); destination node values are untouched; ancestors
+ *                   created on the way hold initValue()
+ *        counts     (optional, host, int64[10]) blocks that existed and received an observed sample, blocks created, voxels with an observed
+ *                   sample, of those the voxels whose destination value was observed before, lo[3] and hi[3] of the half-open destination voxel
+ *                   box over the blocks that received samples (all zero if none)
+ *        arguments  SE_HIP_E_INVALID, both maps untouched: everything se_hip_merge_map refuses (dst == src, devices, field types, voxel sizes,
+ *                   the rule); a null transform or a non-finite entry; |t_k| > 2^20; max |R^T R - I| > 1e-3 or det R <= 0, both evaluated in
+ *                   double (the transform must be rigid: no scale, no mirror; a binary32 rotation from a normalised quaternion is off by about
+ *                   1e-6).  A source with a sticky SE_HIP_E_CAPACITY is refused with that code
+ *      Non-finite source values: the library never produces them; the result for them is unspecified.
+ *      Schedule, pool exhaustion and staging ownership are those of se_hip_merge_map: a held-back raycast of either handle is launched first,
+ *      scans are joined, all streams are synchronised before the first kernel, which runs on dst's stream, and the call returns synchronised;
+ *      a destination pool that runs out raises the sticky SE_HIP_E_CAPACITY and a block that found no slot is skipped; dst's images stay valid
+ *      and tracking goes on; no launch counter or timing sum moves.  The staging (dst's) is one bit per destination block plus 12 bytes per
+ *      candidate block (at most 64 per source block, at most the destination's block grid). */
+int se_hip_merge_map_rigid(se_hip_pipeline* dst, se_hip_pipeline* src, const float src_from_dst[12],
+                           const se_hip_merge_rule* rule, int64_t* host_counts /* optional, [10] */);
+
 /* ---- map export, second half: marching cubes over the allocated blocks
  * DenseSLAMSystem::dump_mesh (DenseSLAMSystem.cpp:302-322) = se::algorithms::marching_cube
  * (se_core/include/se/algorithms/meshing.hpp:161-208) with inside(v) = v.x < 0, select(v) = v.x, then writeVtkMesh

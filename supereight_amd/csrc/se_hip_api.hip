@@ -33,6 +33,7 @@
 #include "se_ray_kernels.h"
 #include "se_shift_kernels.h"
 #include "se_merge_kernels.h"
+#include "se_resample_kernels.h"
 
 int flush_pending_raycast(se_hip_pipeline* p);   // (defined next to se_hip_frame)
 
@@ -2743,6 +2744,100 @@ int se_hip_merge_map(se_hip_pipeline* dst, se_hip_pipeline* src, const int32_t s
     host_counts[0] = (int64_t)took[0] - created; host_counts[1] = created; host_counts[2] = (int64_t)(nb - took[0]);
     host_counts[3] = (int64_t)(took[1] - took[2]); host_counts[4] = (int64_t)took[2]; host_counts[5] = (int64_t)(nn - took[1]);
     for (int k = 0; k < 6; ++k) host_counts[6 + k] = took[0] ? (int64_t)box[k] : 0;
+  }
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------ map merge under a rigid transform
+// The steps of se_resample_kernels.h on dst's stream, between two synchronisations of both handles, as se_hip_merge_map; src is only read.
+int se_hip_merge_map_rigid(se_hip_pipeline* dst, se_hip_pipeline* src, const float src_from_dst[12], const se_hip_merge_rule* rule, int64_t* host_counts) {
+  if (!dst || !src) return fail(SE_HIP_E_INVALID, "null handle");
+  if (dst == src) return fail(SE_HIP_E_INVALID, "se_hip_merge_map_rigid: dst == src");
+  if (dst->device != src->device) return fail(SE_HIP_E_INVALID, "se_hip_merge_map_rigid: the handles live on different devices (save, load into a scratch handle on dst's device, merge)");
+  if (dst->cfg.field_type != src->cfg.field_type) return fail(SE_HIP_E_INVALID, "se_hip_merge_map_rigid: different field types");
+  {
+    const float va = dst->map.dim / (float)dst->map.size, vb = src->map.dim / (float)src->map.size;
+    if (std::memcmp(&va, &vb, sizeof va) != 0) return fail(SE_HIP_E_INVALID, "se_hip_merge_map_rigid: different voxel sizes (dim / size)");
+  }
+  if (!src_from_dst) return fail(SE_HIP_E_INVALID, "se_hip_merge_map_rigid: null transform");
+  for (int k = 0; k < 12; ++k) if (!std::isfinite(src_from_dst[k])) return fail(SE_HIP_E_INVALID, "se_hip_merge_map_rigid: a non-finite entry in the transform");
+  double R[3][3], t[3], inv[3][3];
+  for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) R[r][c] = (double)src_from_dst[4 * r + c]; t[r] = (double)src_from_dst[4 * r + 3]; }
+  for (int k = 0; k < 3; ++k) if (std::fabs(t[k]) > 1048576.0) return fail(SE_HIP_E_INVALID, "se_hip_merge_map_rigid: a translation component beyond 2^20 voxels");
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double g = (R[0][i] * R[0][j] + R[1][i] * R[1][j]) + R[2][i] * R[2][j];
+      if (std::fabs(g - (i == j ? 1.0 : 0.0)) > 1e-3) return fail(SE_HIP_E_INVALID, "se_hip_merge_map_rigid: the transform is not rigid (max |R^T R - I| > 1e-3)");
+    }
+  for (int i = 0; i < 3; ++i)     // cofactors: inv = adj(R) / det
+    for (int j = 0; j < 3; ++j) inv[j][i] = R[(i + 1) % 3][(j + 1) % 3] * R[(i + 2) % 3][(j + 2) % 3] - R[(i + 1) % 3][(j + 2) % 3] * R[(i + 2) % 3][(j + 1) % 3];
+  const double det = (R[0][0] * inv[0][0] + R[0][1] * inv[1][0]) + R[0][2] * inv[2][0];
+  if (!(det > 0.0)) return fail(SE_HIP_E_INVALID, "se_hip_merge_map_rigid: the transform mirrors (det R <= 0)");
+  if (!rule) return fail(SE_HIP_E_INVALID, "se_hip_merge_map_rigid: null rule");
+  if (rule->mode != SE_HIP_MERGE_FUSE && rule->mode != SE_HIP_MERGE_REPLACE && rule->mode != SE_HIP_MERGE_FILL) return fail(SE_HIP_E_INVALID, "se_hip_merge_map_rigid: unknown mode");
+  if (!(rule->max_weight >= 1.f && rule->max_weight <= 255.f && rule->max_weight == (float)(int)rule->max_weight))
+    return fail(SE_HIP_E_INVALID, "se_hip_merge_map_rigid: max_weight is not an integer in [1, 255]");
+  if (int r = check(src)) return r;
+  if (int r = check(dst)) return r;
+  if (int r = fetch_counters(src)) return r;   // (joins a scan, synchronises the main stream; a sticky overflow of the source refuses the call)
+  if (src->side) HIP_TRY(hipStreamSynchronize(src->side));
+  if (int r = fetch_counters(dst)) return r;
+  if (dst->side) HIP_TRY(hipStreamSynchronize(dst->side));
+  src->gate_armed = false; dst->gate_armed = false;
+  const DevMap& d = dst->map;
+  const DevMap& m = src->map;
+  const size_t nb = std::min<size_t>(src->ctr_host[C_BLOCKS], src->cap_blocks);
+  if (nb == 0) {
+    if (host_counts) for (int k = 0; k < 10; ++k) host_counts[k] = 0;
+    return SE_HIP_OK;
+  }
+  const uint32_t nb0 = dst->ctr_host[C_BLOCKS];
+  const size_t cells = (size_t)1 << (3 * d.leaf_level), words = (cells + 31) / 32;
+  const size_t cap = std::min(cells, nb * 64);   // (a source block's image touches at most 3 destination blocks per axis)
+  // staging (dst's): [block keys][voxel counts][candidates][candidate bitmap][box]
+  const size_t bytes[5] = {(cap + 1) * 8, 16, (cap + 1) * sizeof(uint32_t), words * sizeof(uint32_t), 6 * sizeof(int)};
+  size_t off[5];
+  if (int r = reserve_staging(dst, staging_layout(bytes, 5, off))) return r;
+  unsigned char* b = dst->staging;
+  RigidArgs a{};
+  for (int k = 0; k < 12; ++k) a.pull[k] = src_from_dst[k];
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) a.push[4 * r + c] = inv[r][c] / det;
+    a.push[4 * r + 3] = -((inv[r][0] * t[0] + inv[r][1] * t[1]) + inv[r][2] * t[2]) / det;
+  }
+  a.mode = rule->mode; a.max_weight = rule->max_weight;
+  a.nb = (uint32_t)nb; a.cap = (uint32_t)cap; a.words = (uint32_t)words;
+  a.blist = (unsigned long long*)(b + off[0]); a.nvox = (unsigned long long*)(b + off[1]);
+  a.cand = (uint32_t*)(b + off[2]); a.cbm = (uint32_t*)(b + off[3]); a.box = (int*)(b + off[4]);
+  const int box0[6] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN};
+  hipStream_t st = dst->stream;
+  HIP_TRY(hipMemsetAsync(a.blist, 0, sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(a.nvox, 0, 2 * sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(a.cand, 0, sizeof(uint32_t), st));
+  HIP_TRY(hipMemsetAsync(a.cbm, 0, words * sizeof(uint32_t), st));
+  HIP_TRY(hipMemcpyAsync(a.box, box0, sizeof box0, hipMemcpyHostToDevice, st));
+  const bool of = dst->cfg.field_type == SE_HIP_FIELD_OFUSION;
+  const int waves_grid = grid_for(cap * 64, SE_WG, 8192);
+  hipLaunchKernelGGL(k_rigid_candidates<0>, dim3(grid_for(nb, SE_WG, 2048)), dim3(SE_WG), 0, st, d, m, a);
+  hipLaunchKernelGGL(k_rigid_list<0>, dim3(grid_for(words, SE_WG, 2048)), dim3(SE_WG), 0, st, d, a);
+  if (of) hipLaunchKernelGGL(k_rigid_eval<true>, dim3(waves_grid), dim3(SE_WG), 0, st, d, m, a);
+  else hipLaunchKernelGGL(k_rigid_eval<false>, dim3(waves_grid), dim3(SE_WG), 0, st, d, m, a);
+  hipLaunchKernelGGL(k_alloc_commit, dim3(256, 1), dim3(SE_WG), 0, st, d, a.blist, 1, (long long)(cap + 1));
+  if (of) hipLaunchKernelGGL(k_rigid_write<true>, dim3(waves_grid), dim3(SE_WG), 0, st, d, m, a);
+  else hipLaunchKernelGGL(k_rigid_write<false>, dim3(waves_grid), dim3(SE_WG), 0, st, d, m, a);
+  HIP_TRY(hipGetLastError());
+  unsigned long long took = 0, nvox[2] = {0, 0};
+  int box[6] = {0, 0, 0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(&took, a.blist, sizeof took, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(nvox, a.nvox, sizeof nvox, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(box, a.box, sizeof box, hipMemcpyDeviceToHost, st));
+  const int rc = fetch_counters(dst);   // (the counter mirror refreshed in stream order; synchronises; a pool that ran out: SE_HIP_E_CAPACITY, sticky)
+  if (host_counts) {
+    const int64_t created = (int64_t)std::min<uint32_t>(dst->ctr_host[C_BLOCKS], (uint32_t)dst->cap_blocks) - (int64_t)nb0;   // (only this call's blocks insert leaves)
+    took = std::min<unsigned long long>(took, cap);
+    host_counts[0] = (int64_t)took - created; host_counts[1] = created;
+    host_counts[2] = (int64_t)nvox[0]; host_counts[3] = (int64_t)nvox[1];
+    for (int k = 0; k < 6; ++k) host_counts[4 + k] = took ? (int64_t)box[k] : 0;
   }
   return rc;
 }

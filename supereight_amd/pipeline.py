@@ -212,6 +212,7 @@ EXPORTS = {
     "se_hip_load_map": (C.c_int, [C.c_void_p, C.c_char_p]),
     "se_hip_shift_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "se_hip_merge_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "se_hip_merge_map_rigid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "se_hip_create_replicas": (C.c_int, [C.POINTER(_Config), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]),
     "se_hip_mesh_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "se_hip_mesh_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
@@ -242,6 +243,44 @@ EXPORTS = {
     "se_hip_mesh_blocks": (C.c_int, [C.c_void_p, C.POINTER(_MeshSelect), C.POINTER(_MeshOut)]),
     "se_hip_mesh_blocks_host": (C.c_int, [C.c_void_p, C.POINTER(_MeshSelect), C.POINTER(_MeshOut)]),
 }
+
+
+def _check_rigid(m, what):
+    """A 3x4 (or 4x4) float64 transform in voxels: finite, |t| <= 2^20, max |R^T R - I| <= 1e-3, det R > 0 -- what se_hip_merge_map_rigid asks."""
+    if not np.isfinite(m).all():
+        raise ValueError(f"{what}: a non-finite entry")
+    R, t = m[:3, :3], m[:3, 3]
+    if (np.abs(t) > 2.0 ** 20).any():
+        raise ValueError(f"{what}: a translation component beyond 2^20 voxels")
+    if np.abs(R.T @ R - np.eye(3)).max() > 1e-3:
+        raise ValueError(f"{what}: not rigid (max |R^T R - I| > 1e-3: no scale, no shear)")
+    if not np.linalg.det(R) > 0:
+        raise ValueError(f"{what}: a mirror (det R <= 0)")
+
+
+def rigid_pull(T_dst_src, dim, size) -> np.ndarray:
+    """The pull transform of DenseSLAMPipeline.merge_rigid / se_hip_merge_map_rigid, float32 [12] (row-major 3 x 4, voxels), from the
+    metric 4x4 pose of the source map's frame in the destination's: x_dst = T_dst_src x_src in metres, voxel = dim / size on both sides.
+    Inverted and scaled in float64, rounded once.  Raises TypeError / ValueError for anything that is not a finite rigid pose."""
+    T = np.asarray(T_dst_src)
+    if T.dtype.kind not in "fiu":
+        raise TypeError(f"rigid_pull: T_dst_src must be a 4x4 array of numbers, got dtype {T.dtype}")
+    if T.shape != (4, 4):
+        raise ValueError(f"rigid_pull: T_dst_src must be 4x4, got {T.shape}")
+    T = T.astype(np.float64)
+    if not np.isfinite(T).all():
+        raise ValueError("rigid_pull: a non-finite entry")
+    if not (T[3] == (0, 0, 0, 1)).all():
+        raise ValueError("rigid_pull: the last row must be (0, 0, 0, 1)")
+    if not (dim > 0 and size > 0):
+        raise ValueError("rigid_pull: dim and size must be positive")
+    R, t = T[:3, :3], T[:3, 3]
+    if np.abs(R.T @ R - np.eye(3)).max() > 1e-3 or not np.linalg.det(R) > 0:
+        raise ValueError("rigid_pull: T_dst_src is not rigid (max |R^T R - I| > 1e-3, or a mirror)")
+    Ri = np.linalg.inv(R)
+    pull = np.concatenate([Ri, (-(Ri @ t) * (float(size) / float(dim)))[:, None]], 1)
+    _check_rigid(pull, "rigid_pull")
+    return np.ascontiguousarray(pull, np.float32).reshape(12)
 
 
 def _share_torch_hip_runtime() -> None:
@@ -1287,6 +1326,34 @@ class DenseSLAMPipeline:
         self._check(self.lib.se_hip_merge_map(self._h, src._h, s.ctypes.data, C.addressof(rule), out.ctypes.data))
         res = {k: int(v) for k, v in zip(self.MERGE_COUNTS, out[:6])}
         res["region"] = (tuple(int(v) for v in out[6:9]), tuple(int(v) for v in out[9:12]))
+        return res
+
+    MERGE_RIGID_COUNTS = ("blocks_combined", "blocks_created", "voxels_observed", "voxels_both")
+
+    def merge_rigid(self, src, T_dst_src=None, pull=None, mode: str = "fuse", max_weight=100) -> dict:
+        """The content of `src` resampled into this map's lattice under a rigid transform and combined as merge() combines
+        (se_hip_merge_map_rigid, include/se_hip.h): every voxel of this map reads `src` at a rotated position, blended from the eight voxels
+        around it; cells with an unseen corner contribute nothing.  Give either T_dst_src, the metric 4x4 pose of the source map's frame
+        in this map's (rigid_pull turns it into the pull transform), or `pull` itself: src_from_dst as float32 [12] or [3, 4], in voxels.
+        Node values do not take part.  `src` is only read; this map's vertex / normal images stay valid.  Returns blocks_combined (existed
+        and received a sample), blocks_created, voxels_observed (voxels that received a sample), voxels_both (of those, observed here before)
+        and region = (lo, hi), the half-open voxel box of the blocks that received samples (zeros if none), fit for
+        LiveMesh.update(pipe, region=...).  Wrong arguments raise before any library call."""
+        if (T_dst_src is None) == (pull is None):
+            raise TypeError("merge_rigid: give exactly one of T_dst_src and pull")
+        _, rule = self._merge_arguments(src, (0, 0, 0), mode, max_weight)
+        if pull is None:
+            p = rigid_pull(T_dst_src, self.dim, self.size)
+        else:
+            p = np.asarray(pull)
+            if p.dtype.kind not in "fiu" or p.size != 12 or p.shape not in ((12,), (3, 4)):
+                raise (TypeError if p.dtype.kind not in "fiu" else ValueError)("merge_rigid: pull must be 12 numbers, [12] or [3, 4]")
+            p = np.ascontiguousarray(p, np.float32).reshape(12)
+            _check_rigid(p.reshape(3, 4).astype(np.float64), "merge_rigid: pull")
+        out = np.zeros(10, np.int64)
+        self._check(self.lib.se_hip_merge_map_rigid(self._h, src._h, p.ctypes.data, C.addressof(rule), out.ctypes.data))
+        res = {k: int(v) for k, v in zip(self.MERGE_RIGID_COUNTS, out[:4])}
+        res["region"] = (tuple(int(v) for v in out[4:7]), tuple(int(v) for v in out[7:10]))
         return res
 
     # ------------------------------------------------------------------ measurement
