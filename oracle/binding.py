@@ -104,6 +104,10 @@ def _declare(lib):
         "so_vertex2normal": (None, [c_f32p, c_f32p, i32, i32, i32]),
         "so_se3_exp": (None, [c_f32p, c_f32p]),
         "so_solve6": (i32, [c_f32p, c_f32p]),
+        "so_solve6_col": (i32, [c_f32p, c_f32p]),
+        "so_sincos_f32": (None, [c_f32p, i32, c_f32p, c_f32p]),
+        "so_set_track_trace": (None, [C.c_void_p, i32]),
+        "so_track_trace_count": (i32, []),
         "so_tracking": (i32, [c_f32p, i32, i32, c_f32p, c_i32p, i32, f32, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, c_f32p, C.POINTER(i32)]),
         "so_render_depth": (None, [c_u8p, c_f32p, i32, i32]),
         "so_render_track": (None, [c_u8p, C.c_void_p, i32, i32]),
@@ -300,9 +304,40 @@ def oracle_half_sample(depth, e_d: float, r: int = 1):
     return out
 
 
-def oracle_tracking(depth, k, pose, raycast_pose, ref_vertex, ref_normal, icp_threshold=1e-5, pyramid=(10, 5, 4), fma=False):
+def oracle_sincos(x):
+    """The sine and cosine the tracker is DEFINED with (so_sincos, libm switch off) of float32 arguments: (sin, cos), float32."""
+    lib = load()
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    s, c = np.empty_like(x), np.empty_like(x)
+    if x.size:
+        lib.so_sincos_f32(x, x.size, s, c)
+    return s, c
+
+
+def oracle_solve6(vals27):
+    """makeJTJ + LLT solve of one system (b[6], upper triangle[21]): (x[6], the column at which the factorisation gave up or 6)."""
+    lib = load()
+    x = np.zeros(6, np.float32)
+    col = lib.so_solve6_col(np.ascontiguousarray(vals27, np.float32).reshape(27), x)
+    return x, col
+
+
+def oracle_se3_exp(twist6):
+    """Sophus::SE3f::exp of (upsilon, omega) as the tracker defines it: row-major 4x4 float32."""
+    lib = load()
+    out = np.zeros(16, np.float32)
+    lib.so_se3_exp(np.ascontiguousarray(twist6, np.float32).reshape(6), out)
+    return out.reshape(4, 4)
+
+
+TRACE_DTYPE = np.dtype([("level", np.float32), ("fail_col", np.float32), ("x", np.float32, 6), ("sums", np.float32, 32)])
+
+
+def oracle_tracking(depth, k, pose, raycast_pose, ref_vertex, ref_normal, icp_threshold=1e-5, pyramid=(10, 5, 4), fma=False, trace=None):
     """DenseSLAMSystem::tracking on the oracle.  Returns (tracked, new_pose 4x4, TrackData image, reduce row, iterations).
-    fma=True: the noise-floor build (-ffp-contract=fast), see oracle/Makefile."""
+    fma=True: the noise-floor build (-ffp-contract=fast), see oracle/Makefile.
+    trace: a list that receives one TRACE_DTYPE record array, a row per iteration that ran (level, the column at which the solve gave up
+    or 6, the update x, the 32 sums)."""
     from supereight_amd.synthetic import to_colmajor
     lib = load(fma=fma)
     H, W = depth.shape
@@ -313,9 +348,17 @@ def oracle_tracking(depth, k, pose, raycast_pose, ref_vertex, ref_normal, icp_th
     # the ICP is thousands of small parallel regions: on a 256-thread box the OpenMP barriers cost more than the work
     nthr = lib.so_num_threads()
     lib.so_set_num_threads(min(nthr, 16))
+    rec = None
+    if trace is not None:
+        rec = np.zeros(max(1, int(np.sum(pyramid))), TRACE_DTYPE)
+        lib.so_set_track_trace(rec.ctypes.data, len(rec))
     ok = lib.so_tracking(np.ascontiguousarray(depth, np.float32).reshape(-1), W, H, np.asarray(k, np.float32),
                          np.asarray(pyramid, np.int32), len(pyramid), icp_threshold,
                          np.ascontiguousarray(ref_vertex, np.float32).reshape(-1), np.ascontiguousarray(ref_normal, np.float32).reshape(-1),
                          to_colmajor(raycast_pose), pose_cm, track.ctypes.data, red, C.byref(it))
+    if rec is not None:
+        n = lib.so_track_trace_count()
+        lib.so_set_track_trace(None, 0)
+        trace.append(rec[:n].copy())
     lib.so_set_num_threads(nthr)
     return bool(ok), pose_cm.reshape(4, 4).T.copy(), track.reshape(H, W), red, it.value

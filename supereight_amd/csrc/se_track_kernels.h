@@ -225,7 +225,8 @@ struct IcpHostRecord { float pose[16]; float reduce0[32]; int iterations; int tr
 
 // sin / cos of a float, DEFINED (oracle and device alike, see oracle/se_oracle.cpp so_sincos) as the correctly rounded result:
 // evaluated in double -- Cody-Waite reduction by pi/2 in two parts, the fdlibm kernel polynomials -- and rounded once.  Plain
-// IEEE double arithmetic in source order (no FMA contraction), so host and device agree bit for bit; it equals
+// IEEE double arithmetic in source order (no FMA contraction), so host and device agree bit for bit (tests/test_gpu_icp_math.py: 4.5e6 arguments in
+// all four quadrants); it equals
 // (float)sin((double)x) of glibc for every one of 7.3e6 random arguments tried, and glibc's own sinf / cosf on 99.6 - 99.8 %
 // (they are 1 ulp off the correctly rounded value elsewhere).  Valid for |x| < 2^20 (ICP angle updates are << pi).
 __host__ __device__ inline void se_sincos_f32(float xf, float* s, float* c) {
@@ -252,7 +253,7 @@ __host__ __device__ inline void se_sincos_f32(float xf, float* s, float* c) {
 // Cholesky factor (lane r owns row r: one column step = one multiply-add chain, ONE division), the two sincos calls, the four quaternion divisions, the
 // sixteen entries of the pose product.  Every float operation has the operands and the order it has in the oracle's solve6 / se3_exp
 // (oracle/se_oracle.cpp: sums left to right, true divisions, the same sqrtf): the results are bit-identical, which tests/test_gpu_tracking.py checks
-// against the oracle frame by frame.
+// against the oracle frame by frame and tests/test_gpu_icp_math.py system by system and twist by twist (tests/cpp/icp_math_check.hip calls these functions).
 __device__ __forceinline__ float se_lane(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
 // vals: b[6], upper triangle[21] (LDS); x: the solution, in every lane.  (Eigen::LLT is defined as the unblocked Cholesky with left-to-right inner sums.)
 __device__ __forceinline__ void se_solve6_wave(const float* vals, float x[6], int lane) {
@@ -456,13 +457,14 @@ __global__ __launch_bounds__(SE_TRACK_LANES) void k_icp_iter(const IcpState* __r
   const long npx = (long)rows * W;
   const long seg_len = (npx + SE_TRACK_SEGMENTS - 1) / SE_TRACK_SEGMENTS;
   const long lo = g * seg_len, hi = min(npx, (g + 1) * seg_len);
+  const int y0 = rows > 0 ? b : 0;     // (a level of fewer than 8 rows has strips without a row: their lanes, which have no pixel, read pixel 0 of the level)
   f3 inN0[SE_TRACK_BATCH], inV0[SE_TRACK_BATCH];
   if (!stop_cur) {
 #pragma unroll
     for (int j = 0; j < SE_TRACK_BATCH; ++j) {
       const long i = lo + t + (long)j * SE_TRACK_LANES;
       const long ii = i < hi ? i : (lo < npx ? lo : 0);   // (a lane without a pixel reads some pixel of the strip)
-      const int y = b + 8 * (int)(ii / W), x = (int)(ii % W);
+      const int y = y0 + 8 * (int)(ii / W), x = (int)(ii % W);
       inN0[j] = ld3(inNormal, x + y * a.inW);
       inV0[j] = ld3(inVertex, x + y * a.inW);
     }
@@ -498,7 +500,7 @@ __global__ __launch_bounds__(SE_TRACK_LANES) void k_icp_iter(const IcpState* __r
       const long i = base + (long)j * SE_TRACK_LANES;
       const bool live = i < hi;
       const long ii = live ? i : (lo < npx ? lo : 0);
-      const int y = b + 8 * (int)(ii / W), x = (int)(ii % W);
+      const int y = y0 + 8 * (int)(ii / W), x = (int)(ii % W);
       if (base == lo + t) { inN[j] = inN0[j]; inV[j] = inV0[j]; }     // (fetched before the prologue)
       else { inN[j] = ld3(inNormal, x + y * a.inW); inV[j] = ld3(inVertex, x + y * a.inW); }
       res[j] = live ? 0 : 2;              // 2: no pixel
