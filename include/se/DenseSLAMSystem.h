@@ -263,6 +263,15 @@ class DenseSLAMSystem {
     }
     return true;
   }
+  /* Not in the reference's class (an addition of this mirror): octants that lie wholly inside a box handed back on the device -- se_hip_release_boxes,
+   * definitions in se_hip.h: SE_HIP_RELEASE_ALL forgets the region, SE_HIP_RELEASE_UNSEEN drops only what holds nothing but initValue().  The map
+   * afterwards is what se::release_map (include/se/release_map.hpp) makes of the getMap() snapshot taken before.  counts[5] (optional): blocks
+   * kept, released, nodes kept, released, released blocks that held an observed voxel; touched[6] (optional): lo and hi of the voxel box of the
+   * released blocks.  The poses and the vertex / normal images stay as they are (tracking goes on).  A block that holds nothing but is still in
+   * view and in the allocation band comes back with the next integrate(). */
+  bool releaseMap(const std::vector<se_hip_release_box>& boxes, int64_t* counts = nullptr, int32_t* touched = nullptr) {
+    return ok(se_hip_release_boxes(h_, boxes.empty() ? nullptr : boxes.data(), (int64_t)boxes.size(), counts, touched));
+  }
   /* Not in the reference's class (an addition of this mirror): the content of another pipeline's map (same device, field type and voxel size; any
    * volume size) folded into this one on the device, source content at voxel c meeting this map's at c + shift_voxels (multiples of 8) --
    * se_hip_merge_map, definitions in se_hip.h.  The map afterwards is what se::merge_map (include/se/merge_map.hpp) makes of the two getMap()

@@ -587,6 +587,45 @@ int se_hip_load_map(se_hip_pipeline* p, const char* filename);
  *      program staged_shift_merge, against the oracle). */
 int se_hip_shift_map(se_hip_pipeline* p, const int32_t shift_voxels[3], int64_t* host_counts);
 
+/* ---- release: octants that lie wholly inside a box handed back on the device -- all of them (the region is forgotten) or only those that hold
+ *      nothing (no reference counterpart: nothing in the reference's octree is ever freed).  The executable definition is se::release_map of
+ *      include/se/release_map.hpp on the getMap() snapshot.
+ *        arguments  host records; 0 <= n <= 4096; per record the box is [lo, lo + side) per axis, in voxels, side >= 1, lo and lo + side within
+ *                   [-2^30, 2^30], what one of the two codes, reserved 0; a null host_boxes with n > 0 or anything else: SE_HIP_E_INVALID and the
+ *                   map is untouched (as with every other entry, a raycast that was held back has been launched by then).  Boxes need not be
+ *                   multiples of 8: a record contains the octant with corner c and side d iff c >= lo and c + d <= lo + side on every axis
+ *                   (partial forgetting is se_hip_edit_boxes' reset).  n = 0 is valid, changes nothing and returns the counts of the map as it is
+ *        blocks     released iff some record contains the block and that record is ALL, or is UNSEEN and all 512 voxels equal initValue() in x
+ *                   and y bit for bit, as se_hip_download_blocks returns them (the SDF weight byte converted to float)
+ *        nodes      releasable iff some record contains the node and that record is ALL or all eight value_[i] equal initValue() bit for bit;
+ *                   released iff releasable and every block and node beneath it is released.  The root always stays.  An ancestor of a
+ *                   survivor is never released: nothing is created
+ *        parents    for every released octant whose parent stays, the parent's value_[child] becomes initValue().  Nothing else in a survivor
+ *                   changes: 512 values, value_[8] and the active flag bit for bit.  So Octree::get(v) is initValue() for every voxel of a released
+ *                   block: a call with UNSEEN records only changes the answer of get at no voxel and the strict status of no box; an ALL
+ *                   record turns its blocks unseen
+ *        counts     (optional, host, int64[5]) blocks kept, blocks released, nodes kept (the root included), nodes released, released blocks
+ *                   that held at least one observed voxel
+ *        touched    (optional, host, int32[6]) lo[3] and hi[3] of the voxel box that holds every released block (half open, as se_hip_merge_map
+ *                   reports its box; all zero if none)
+ *      A call that releases nothing changes nothing: no rebuild, no pool compaction.  Otherwise everything derived from the block set -- index,
+ *      occupancy and beam-start bitmaps, lists, counters -- is rebuilt for the survivors as se_hip_shift_map rebuilds it: the pools are compact
+ *      afterwards (used slots = survivors), every free slot and every vacated dense brick reads initValue(), the count words of the new-key
+ *      lists and the statistics counters of se_hip_get_stats are zeroed.  A held-back raycast is launched first, a scan on the side stream is
+ *      joined, and the call returns synchronised.  The work is per block and per record, not per cell of the volume; the survivors pass through
+ *      the shift's staging (4 KiB per block, released again when it is larger than 64 MiB).  No pool can run out: nothing is created.
+ *      vertex_ / normal_ stay valid (the frame of reference did not move: tracking goes on).  Replicas each hold the whole map: the same call
+ *      goes to every one of them.  Between the scan and the sweep of a frame (se_hip_alloc_scan ... se_hip_integrate_sweep) the call is
+ *      allowed: it acts on the state after the join, where the scan's fresh blocks are ordinary all-unseen blocks, and the sweep owes the scan
+ *      no commit any more.  A block that holds nothing but is still in view and inside the allocation band is created again by the next
+ *      allocation scan: the lasting gain is in regions the camera has left, before a save or a merge, and under a pooled budget. */
+#define SE_HIP_RELEASE_ALL    1   /* every octant wholly inside the box: the region is forgotten */
+#define SE_HIP_RELEASE_UNSEEN 2   /* only octants that hold nothing */
+#define SE_HIP_RELEASE_MAX_BOXES 4096
+typedef struct se_hip_release_box { int32_t lo[3]; int32_t side[3]; int32_t what; int32_t reserved; } se_hip_release_box;
+int se_hip_release_boxes(se_hip_pipeline* p, const se_hip_release_box* host_boxes, int64_t n,
+                         int64_t* host_counts /* [5], optional */, int32_t* host_touched /* lo xyz, hi xyz, optional */);
+
 /* ---- map merge: the content of one resident map (src) folded into another (dst) on the device, optionally moved by a whole number of blocks (no
  *      reference counterpart: the reference holds one map).  The executable definition is se::merge_map / se::merge_value of
  *      include/se/merge_map.hpp on two getMap() snapshots.  s = shift_voxels: source content at voxel c meets destination content at c + s.

@@ -54,7 +54,7 @@ struct DevMap {
                                   // before it touches a brick or the index: 32 KB at 512^3, 256 KB at 1024^3, 2 MB at 2048^3 -- L2-resident)
   uint32_t* cbits;                // beam start of the raycast: one bit per cell of the COARSE grid (level clevel, linear x + (y << clevel) + (z << 2 clevel)),
                                   // set for every cell within one cell (27-neighbourhood) of an allocated block: 4 KB at level 5.  A clear bit = no block anywhere
-                                  // within one coarse cell of any point of this cell.  Only ever set (blocks are never freed; se_hip_shift_map clears the bitmaps and marks the survivors anew).  The second
+                                  // within one coarse cell of any point of this cell.  Only ever set (blocks are never freed one by one; se_hip_shift_map and se_hip_release_boxes clear the bitmaps and mark the survivors anew).  The second
                                   // half of the allocation holds the same grid undilated ("a block exists in this cell": se_mark_coarse).
   int clevel;
   uint32_t* fbits;                // the same on a finer grid, level se_flevel(m) = min(leaf_level, 6) (7.5 cm cells at 4.8 m: the margin an 8x8-pixel beam of a 640x480 camera

@@ -34,6 +34,7 @@
 #include "se_shift_kernels.h"
 #include "se_merge_kernels.h"
 #include "se_resample_kernels.h"
+#include "se_release_kernels.h"
 
 int flush_pending_raycast(se_hip_pipeline* p);   // (defined next to se_hip_frame)
 
@@ -2620,6 +2621,22 @@ int se_hip_load_map(se_hip_pipeline* p, const char* filename) {
 }
 
 // ------------------------------------------------------------------------------------ map shift
+// What follows the select step of se_hip_shift_map and of se_hip_release_boxes: the survivors' bricks gathered into the staging (every old slot
+// rewritten with the init pattern), the index structures cleared, the two key lists inserted (nodes, then blocks), bricks, flags and node values
+// scattered to the new slots.
+static int rebuild_from_lists(se_hip_pipeline* p, const ShiftArgs& a, size_t nb, size_t nn) {
+  const DevMap& m = p->map;
+  const int waves_grid = grid_for(nb * 64, SE_WG, 8192);
+  if (nb) hipLaunchKernelGGL(k_shift_gather, dim3(waves_grid), dim3(SE_WG), 0, p->stream, m, a);
+  p->scan_pending = false; p->occ_commit_due = false; p->occ_lists = OccLists{nullptr, 0, 0};
+  clear_map_index(p, nb, nn);
+  hipLaunchKernelGGL(k_alloc_commit, dim3(256, 1), dim3(SE_WG), 0, p->stream, m, a.nlist, 1, (long long)(nn + 1));
+  hipLaunchKernelGGL(k_alloc_commit, dim3(256, 1), dim3(SE_WG), 0, p->stream, m, a.blist, 1, (long long)(nb + 1));
+  hipLaunchKernelGGL(k_shift_scatter, dim3(waves_grid), dim3(SE_WG), 0, p->stream, m, a);
+  HIP_TRY(hipGetLastError());
+  return SE_HIP_OK;
+}
+
 // The steps of se_shift_kernels.h on the main stream, between two synchronisations: the map is quiescent when the first kernel starts (scan joined,
 // deferred raycast launched by check(), both streams idle) and complete when the call returns.
 int se_hip_shift_map(se_hip_pipeline* p, const int32_t shift_voxels[3], int64_t* host_counts) {
@@ -2651,15 +2668,8 @@ int se_hip_shift_map(se_hip_pipeline* p, const int32_t shift_voxels[3], int64_t*
   a.dst = (uint32_t*)(b + off[4]); a.bact = b + off[5];
   HIP_TRY(hipMemsetAsync(a.blist, 0, sizeof(unsigned long long), p->stream));
   HIP_TRY(hipMemsetAsync(a.nlist, 0, sizeof(unsigned long long), p->stream));
-  const int waves_grid = grid_for(nb * 64, SE_WG, 8192);
   hipLaunchKernelGGL(k_shift_select, dim3(grid_for(std::max(nb, nn), SE_WG, 2048)), dim3(SE_WG), 0, p->stream, m, a);
-  if (nb) hipLaunchKernelGGL(k_shift_gather, dim3(waves_grid), dim3(SE_WG), 0, p->stream, m, a);
-  p->scan_pending = false; p->occ_commit_due = false; p->occ_lists = OccLists{nullptr, 0, 0};
-  clear_map_index(p, nb, nn);
-  hipLaunchKernelGGL(k_alloc_commit, dim3(256, 1), dim3(SE_WG), 0, p->stream, m, a.nlist, 1, (long long)(nn + 1));
-  hipLaunchKernelGGL(k_alloc_commit, dim3(256, 1), dim3(SE_WG), 0, p->stream, m, a.blist, 1, (long long)(nb + 1));
-  hipLaunchKernelGGL(k_shift_scatter, dim3(waves_grid), dim3(SE_WG), 0, p->stream, m, a);
-  HIP_TRY(hipGetLastError());
+  if (int r = rebuild_from_lists(p, a, nb, nn)) return r;
   unsigned long long kept[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(&kept[0], a.blist, sizeof(unsigned long long), hipMemcpyDeviceToHost, p->stream));
   HIP_TRY(hipMemcpyAsync(&kept[1], a.nlist, sizeof(unsigned long long), hipMemcpyDeviceToHost, p->stream));
@@ -2671,6 +2681,91 @@ int se_hip_shift_map(se_hip_pipeline* p, const int32_t shift_voxels[3], int64_t*
     host_counts[0] = (int64_t)kept[0]; host_counts[1] = (int64_t)(nb - kept[0]);
     host_counts[2] = (int64_t)kept[1]; host_counts[3] = (int64_t)(nn - kept[1]);   // (the root gave up its values: dropped)
   }
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------ release of regions and of blocks that hold nothing
+static_assert(SE_HIP_RELEASE_ALL == SE_RELEASE_ALL && SE_HIP_RELEASE_UNSEEN == SE_RELEASE_UNSEEN, "codes of se_hip_release_box");
+static_assert(sizeof(se_hip_release_box) == sizeof(ReleaseRec), "se_hip_release_box");
+// The steps of se_release_kernels.h on the main stream, then -- only when something is released -- the shift's tail with s = 0.  The map is
+// quiescent when the first kernel starts (scan joined, deferred raycast launched by check(), both streams idle) and complete when the call returns.
+int se_hip_release_boxes(se_hip_pipeline* p, const se_hip_release_box* host_boxes, int64_t n, int64_t* host_counts, int32_t* host_touched) {
+  if (int r = check(p)) return r;
+  if (n < 0 || n > SE_HIP_RELEASE_MAX_BOXES) return fail(SE_HIP_E_INVALID, "se_hip_release_boxes: n outside [0, 4096]");
+  if (n > 0 && !host_boxes) return fail(SE_HIP_E_INVALID, "se_hip_release_boxes: null records");
+  std::vector<ReleaseRec> recs((size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    const se_hip_release_box& b = host_boxes[i];
+    for (int k = 0; k < 3; ++k) {
+      if (b.side[k] < 1) return fail(SE_HIP_E_INVALID, "se_hip_release_boxes: a side below 1");
+      if (b.lo[k] < -SE_SHIFT_LIMIT || (int64_t)b.lo[k] + b.side[k] > SE_SHIFT_LIMIT) return fail(SE_HIP_E_INVALID, "se_hip_release_boxes: a box outside [-2^30, 2^30]");
+      recs[i].lo[k] = b.lo[k]; recs[i].hi[k] = b.lo[k] + b.side[k];
+    }
+    if (b.what != SE_HIP_RELEASE_ALL && b.what != SE_HIP_RELEASE_UNSEEN) return fail(SE_HIP_E_INVALID, "se_hip_release_boxes: unknown code in `what`");
+    if (b.reserved != 0) return fail(SE_HIP_E_INVALID, "se_hip_release_boxes: reserved is not 0");
+    recs[i].what = b.what; recs[i].reserved = 0;
+  }
+  if (int r = fetch_counters(p)) return r;   // (joins a scan on the side stream, synchronises the main stream, reports a sticky overflow)
+  if (p->side) HIP_TRY(hipStreamSynchronize(p->side));
+  p->gate_armed = false;
+  const DevMap& m = p->map;
+  const size_t nb = std::min<size_t>(p->ctr_host[C_BLOCKS], p->cap_blocks), nn = std::min<size_t>(p->ctr_host[C_NODES], p->cap_nodes);
+  const auto nothing = [&] {
+    if (host_counts) { host_counts[0] = (int64_t)nb; host_counts[1] = 0; host_counts[2] = (int64_t)nn; host_counts[3] = 0; host_counts[4] = 0; }
+    if (host_touched) for (int k = 0; k < 6; ++k) host_touched[k] = 0;
+    return SE_HIP_OK;
+  };
+  if (n == 0) return nothing();
+  // staging: the shift's [bricks 4 KiB each][node values 64 B each][block keys][node keys], [records], the shift's [destinations], [counts][box],
+  // the shift's [active flags], [block decisions, a byte per brick slot][node marks]
+  const size_t bytes[11] = {nb * 4096, nn * 16 * sizeof(float), (nb + 1) * 8, (nn + 1) * 8, (size_t)n * sizeof(ReleaseRec), nb * sizeof(uint32_t),
+                            4 * sizeof(uint32_t), 6 * sizeof(int), nb, p->slots, nn};
+  size_t off[11];
+  if (int r = reserve_staging(p, staging_layout(bytes, 11, off))) return r;
+  unsigned char* b = p->staging;
+  ReleaseArgs a{};
+  a.sh.nb = (uint32_t)nb; a.sh.nn = (uint32_t)nn;
+  a.sh.bricks = (uint4*)(b + off[0]); a.sh.nval = (float*)(b + off[1]);
+  a.sh.blist = (unsigned long long*)(b + off[2]); a.sh.nlist = (unsigned long long*)(b + off[3]);
+  ReleaseRec* d_rec = (ReleaseRec*)(b + off[4]);
+  a.rec = d_rec; a.n = (uint32_t)n; a.nslots = (uint32_t)p->slots;
+  a.sh.dst = (uint32_t*)(b + off[5]); a.cnt = (uint32_t*)(b + off[6]); a.box = (int*)(b + off[7]);
+  a.sh.bact = b + off[8]; a.brel = b + off[9]; a.nstay = b + off[10];
+  const int box0[6] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN};
+  HIP_TRY(hipMemsetAsync(a.sh.blist, 0, sizeof(unsigned long long), p->stream));
+  HIP_TRY(hipMemsetAsync(a.sh.nlist, 0, sizeof(unsigned long long), p->stream));
+  HIP_TRY(hipMemsetAsync(a.cnt, 0, 4 * sizeof(uint32_t), p->stream));
+  HIP_TRY(hipMemsetAsync(a.nstay, 0, nn, p->stream));
+  HIP_TRY(hipMemsetAsync(a.nstay, 1, 1, p->stream));   // the root stays
+  HIP_TRY(hipMemcpyAsync(a.box, box0, sizeof box0, hipMemcpyHostToDevice, p->stream));
+  HIP_TRY(hipMemcpyAsync(d_rec, recs.data(), (size_t)n * sizeof(ReleaseRec), hipMemcpyHostToDevice, p->stream));
+  if (nb) hipLaunchKernelGGL(k_release_blocks, dim3(grid_for(nb * 64, SE_WG, 8192)), dim3(SE_WG), 0, p->stream, m, a);
+  hipLaunchKernelGGL(k_release_nodes_mark, dim3(grid_for(nn, SE_WG, 2048)), dim3(SE_WG), 0, p->stream, m, a);
+  hipLaunchKernelGGL(k_release_select, dim3(grid_for(std::max(nb, nn), SE_WG, 2048)), dim3(SE_WG), 0, p->stream, m, a);
+  HIP_TRY(hipGetLastError());
+  uint32_t cnt[4] = {0, 0, 0, 0};
+  int box[6] = {0, 0, 0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(cnt, a.cnt, sizeof cnt, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipMemcpyAsync(box, a.box, sizeof box, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  if (cnt[0] == 0u && cnt[1] == 0u) {   // (nothing was written to the map)
+    if (p->staging.size() > p->shift_keep_bytes) p->staging.reset();
+    return nothing();
+  }
+  // the entries of the root above released octants, in place (the root is not listed); every other node slot reads initValue() until the scatter
+  hipLaunchKernelGGL(k_release_root, dim3(1), dim3(64), 0, p->stream, m, a);
+  if (nn > 1) {
+    hipLaunchKernelGGL(k_fill, dim3(grid_for((nn - 1) * 8, 256, 256)), dim3(256), 0, p->stream, m.nx + 8, m.init_x, (nn - 1) * 8);
+    hipLaunchKernelGGL(k_fill, dim3(grid_for((nn - 1) * 8, 256, 256)), dim3(256), 0, p->stream, m.ny + 8, m.init_y, (nn - 1) * 8);
+  }
+  if (int r = rebuild_from_lists(p, a.sh, nb, nn)) return r;
+  const int rc = fetch_counters(p);   // (synchronises)
+  if (p->staging.size() > p->shift_keep_bytes) p->staging.reset();
+  if (host_counts) {
+    host_counts[0] = (int64_t)(nb - cnt[0]); host_counts[1] = (int64_t)cnt[0];
+    host_counts[2] = (int64_t)(nn - cnt[1]); host_counts[3] = (int64_t)cnt[1]; host_counts[4] = (int64_t)cnt[2];
+  }
+  if (host_touched) for (int k = 0; k < 6; ++k) host_touched[k] = cnt[0] ? box[k] : 0;
   return rc;
 }
 

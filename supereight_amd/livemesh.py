@@ -34,6 +34,15 @@ class LiveMesh:
                 self.blocks[tuple(c)] = tris[first:first + count].copy()
             else:
                 self.blocks.pop(tuple(c), None)
+        if views is None and self.blocks:
+            # the region alone decided: every block of the map that intersects it was listed, so an entry there that was not is of a block
+            # the map no longer holds (DenseSLAMPipeline.release handed it back)
+            listed = set(map(tuple, coords.tolist()))
+            lo, hi = ((0, 0, 0), (self.size or 0,) * 3) if region is None else (tuple(int(v) for v in region[0]), tuple(int(v) for v in region[1]))
+            gone = [c for c in self.blocks if c not in listed and all(c[k] < hi[k] and c[k] + 8 > lo[k] for k in range(3))]
+            for c in gone:
+                del self.blocks[c]
+            return len(coords) + len(gone)
         return len(coords)
 
     def shift(self, shift_voxels) -> int:

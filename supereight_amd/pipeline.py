@@ -147,6 +147,8 @@ class _AllocBox(C.Structure):
 
 # se_hip_alloc_box as a numpy record (the host entry's input) -- on the device the same 32 bytes are a torch int32 [N, 8] tensor
 ALLOC_DTYPE = np.dtype([("lo", np.int32, 3), ("hi", np.int32, 3), ("level", np.int32), ("reserved", np.uint32)])
+# se_hip_release_box
+RELEASE_DTYPE = np.dtype([("lo", np.int32, 3), ("side", np.int32, 3), ("what", np.int32), ("reserved", np.int32)])
 
 
 class _Config(C.Structure):
@@ -211,6 +213,7 @@ EXPORTS = {
     "se_hip_save_map": (C.c_int, [C.c_void_p, C.c_char_p]),
     "se_hip_load_map": (C.c_int, [C.c_void_p, C.c_char_p]),
     "se_hip_shift_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "se_hip_release_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "se_hip_merge_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "se_hip_merge_map_rigid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "se_hip_create_replicas": (C.c_int, [C.POINTER(_Config), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]),
@@ -1282,6 +1285,63 @@ class DenseSLAMPipeline:
         pose[:3, 3] += s.astype(np.float32) * (np.float32(self.dim) / np.float32(self.size))
         self.pose_ = pose
         return out
+
+    RELEASE_WHAT = {"all": 1, "unseen": 2}                  # SE_HIP_RELEASE_*
+    RELEASE_COUNTS = ("blocks_kept", "blocks_released", "nodes_kept", "nodes_released", "blocks_released_observed")
+    RELEASE_MAX_BOXES = 4096
+
+    def _release_arguments(self, boxes, what) -> np.ndarray:
+        """The records of release() as RELEASE_DTYPE [N], checked (TypeError / ValueError) before any library call."""
+        def code(w):
+            if not isinstance(w, str):
+                raise TypeError(f"release: what must be one of {sorted(self.RELEASE_WHAT)}, got {type(w).__name__}")
+            if w not in self.RELEASE_WHAT:
+                raise ValueError(f"release: what must be one of {sorted(self.RELEASE_WHAT)}, got {w!r}")
+            return self.RELEASE_WHAT[w]
+        default = code(what)
+        if boxes is None:
+            boxes = [((0, 0, 0), (self.size,) * 3)]
+        if isinstance(boxes, (str, bytes, np.ndarray)) or not hasattr(boxes, "__len__"):
+            raise TypeError(f"release: boxes must be None or a list of (lo, side) or (lo, side, what), got {type(boxes).__name__}")
+        if len(boxes) > self.RELEASE_MAX_BOXES:
+            raise ValueError(f"release: at most {self.RELEASE_MAX_BOXES} boxes, got {len(boxes)}")
+        rec = np.zeros(len(boxes), RELEASE_DTYPE)
+        for i, b in enumerate(boxes):
+            if not isinstance(b, (tuple, list)) or len(b) not in (2, 3):
+                raise TypeError(f"release: box {i} must be (lo, side) or (lo, side, what)")
+            lo, side = np.asarray(b[0]), np.asarray(b[1])
+            if lo.dtype.kind not in "iu" or side.dtype.kind not in "iu":
+                raise TypeError(f"release: box {i}: lo and side must be integers (voxels), got {lo.dtype} and {side.dtype}")
+            if side.ndim == 0:
+                side = np.repeat(side, 3)
+            if lo.shape != (3,) or side.shape != (3,):
+                raise ValueError(f"release: box {i}: lo must have shape (3,) and side be a scalar or have shape (3,)")
+            lo, side = lo.astype(np.int64), side.astype(np.int64)
+            if (side < 1).any() or (side >= 1 << 31).any():
+                raise ValueError(f"release: box {i}: every side must lie in [1, 2^31), got {side.tolist()}")
+            if (lo < -(1 << 30)).any() or (lo + side > 1 << 30).any():
+                raise ValueError(f"release: box {i}: lo and lo + side must lie in [-2^30, 2^30], got {lo.tolist()} + {side.tolist()}")
+            rec[i]["lo"], rec[i]["side"], rec[i]["what"] = lo, side, code(b[2]) if len(b) == 3 else default
+        return rec
+
+    def release(self, boxes=None, what: str = "unseen") -> dict:
+        """Hands octants back on the device (se_hip_release_boxes, include/se_hip.h): every block and node that lies wholly inside a box
+        [lo, lo + side) and -- what "unseen" -- holds nothing but initValue(), or -- what "all" -- whatever it holds (the region is
+        forgotten).  boxes: None (the whole volume) or a list of (lo, side) or (lo, side, what), lo three integers in voxels, side one or
+        three; a box need not be a multiple of 8, an octant cut by its border stays (partial forgetting is reset()).  A node goes only with
+        everything beneath it; the root stays; the entry of a surviving parent above a released octant becomes initValue(), so get()
+        answers initValue() at every released voxel and "unseen" changes no answer anywhere.  Survivors keep values and active flags; the
+        pools are compact afterwards.  pose_ and the vertex / normal images are untouched: tracking goes on.  A block that holds nothing
+        but is still in view and in the allocation band comes back with the next allocation scan.  Returns a dict: blocks_kept,
+        blocks_released, nodes_kept, nodes_released, blocks_released_observed and region = (lo, hi), the half-open voxel box of the
+        released blocks (zeros if none; a LiveMesh is brought up to date with update(pipe, region=region)).  Wrong arguments raise before
+        any library call."""
+        rec = self._release_arguments(boxes, what)
+        out, box = np.zeros(5, np.int64), np.zeros(6, np.int32)
+        self._check(self.lib.se_hip_release_boxes(self._h, rec.ctypes.data if len(rec) else None, len(rec), out.ctypes.data, box.ctypes.data))
+        res = {k: int(v) for k, v in zip(self.RELEASE_COUNTS, out)}
+        res["region"] = (tuple(int(v) for v in box[:3]), tuple(int(v) for v in box[3:]))
+        return res
 
     MERGE_MODES = {"fuse": 0, "replace": 1, "fill": 2}      # SE_HIP_MERGE_*
     MERGE_COUNTS = ("blocks_combined", "blocks_created", "blocks_clipped", "nodes_combined", "nodes_created", "nodes_skipped")
