@@ -214,6 +214,13 @@ class DenseSLAMSystem {
   bool clearanceOf(const int32_t* host_queries, size_t n, const se_hip_collide_test& test, int32_t stop_at, se_hip_clearance_out& host_out) {
     return ok(se_hip_clearance_boxes_host(h_, host_queries, (int64_t)n, &test, stop_at, &host_out));
   }
+  /* Not in the reference's class: column projections of the map -- per cell of a 2D footprint and per interval along request.axis the min
+   * class, the first and the last blocking voxel and the number of blocking voxels -- se_hip_project_columns_host, definitions in
+   * se_hip.h.  The arrays of host_out are [n_layers][side[1]][side[0]]; host_out.status is required, a null first / last / count means "not
+   * wanted".  The answers are those of se::geometry::project_columns (include/se/project_columns.hpp) on the getMap() snapshot. */
+  bool projectColumns(const se_hip_project_request& request, const se_hip_collide_test& test, se_hip_project_out& host_out) {
+    return ok(se_hip_project_columns_host(h_, &request, &test, &host_out));
+  }
   /* Not in the reference's class: collision queries for n oriented boxes (host_boxes[n][12]: centre xyz, then the half-axes h0, h1, h2 xyz, in
    * sub-units of 1 / SE_HIP_ORIENTED_SUB voxel), exact for the box given -- se_hip_collide_oriented_host, definitions in se_hip.h.
    * host_status[n] receives 0 occupied, 1 unseen, 2 empty, 255 invalid box.  The answers are those of se::geometry::oriented_status

@@ -455,6 +455,56 @@ int se_hip_clearance_boxes(se_hip_pipeline* p, const int32_t* device_queries, in
 int se_hip_clearance_boxes_host(se_hip_pipeline* p, const int32_t* host_queries, int64_t n, const se_hip_collide_test* test, int32_t stop_at,
                                 const se_hip_clearance_out* host_out);
 
+/* ---- column projections: "give me the 2D grid" -- the occupancy of a height band per cell (a costmap), the highest occupied voxel per cell
+ *      (an elevation map), the lowest one above some height (a ceiling map), the cells whose band still holds unseen voxels (a 2D frontier)
+ *      -- in one call, without getMap().  Not in the reference; built on its Octree::get and on the classification above.  The host
+ *      restatement and the literal definition are include/se/project_columns.hpp.
+ * Request (se_hip_project_request, a host struct that is copied into the launch), in voxels:
+ *   axis      0, 1 or 2: the axis w the columns run along.  The two remaining axes, in ascending order, are u (the fastest output index) and
+ *             v:  axis 2: u = x, v = y;  axis 1: u = x, v = z;  axis 0: u = y, v = z.
+ *   lo, side  the footprint [lo[0], lo[0] + side[0]) on u and [lo[1], lo[1] + side[1]) on v.
+ *   n_layers  L, 1 .. SE_HIP_PROJECT_MAX_LAYERS; layers[l] = {a_l, b_l}: the half-open interval [a_l, b_l) along w.  Layers may overlap.
+ *   stop_at   SE_HIP_COLLISION_OCCUPIED or SE_HIP_COLLISION_UNSEEN, with the meaning it has in se_hip_collide_motions.
+ * Definition, per voxel of Z^3 and independent of how the tree happens to be subdivided: cell (l, j, i) is the set of voxels with
+ *   u-coordinate lo[0] + i, v-coordinate lo[1] + j and w in [a_l, b_l).  Classification is exactly that of se_hip_collide_boxes in strict mode
+ *   -- `test` applied to Octree::get(v) (the voxel, or value_[child] of the deepest existing node; a pending index entry counts as absent);
+ *   every voxel outside [0, size)^3 is unseen.  A voxel blocks when its class is <= stop_at.
+ * Outputs (se_hip_project_out), each [L][side[1]][side[0]]; status is required, a null pointer for another array means "not wanted":
+ *   status  (uint8) the min class over the cell's voxels, SE_HIP_COLLISION_*: the strict status of the cell's 1 x 1 x (b - a) box.
+ *   first   (int32) the smallest w of a blocking voxel of the cell;  last  (int32) the largest;  both SE_HIP_PROJECT_NONE (INT32_MIN) when no
+ *           voxel of the cell blocks.  Along z with stop_at occupied, last is the elevation map and first the ceiling.
+ *   count   (int32) the number of blocking voxels of the cell.
+ *   Blocking voxels outside the volume are included: a cell may stick out of the volume, or lie wholly outside it.  Those parts are
+ *   answered in closed form, so a layer [-2^20, 2^20) costs no more than the volume's own height.
+ * The whole call is refused with SE_HIP_E_INVALID, and reads no map memory, for: a null request, test, out or status pointer; an axis outside
+ * 0 .. 2; a side < 1; a_l >= b_l; any of lo, lo + side, a_l, b_l outside [-2^20, 2^20]; L outside 1 .. 16; L * side[0] * side[1] > 2^28; a
+ * stop_at other than the two above; a non-finite threshold; occupied_above other than 0 / 1.  Nothing is written to the outputs then.
+ * Both entries answer for the map after everything enqueued before them (a scan that ran on the side stream included), report a sticky
+ * SE_HIP_E_CAPACITY like the other read-back calls, and leave the map, the images and the launch counters (SE_HIP_K_*) alone.
+ *   se_hip_project_columns       device output arrays; enqueued on the handle's stream, asynchronous like the stage calls.
+ *   se_hip_project_columns_host  host output arrays; staged through a device buffer the handle keeps (and grows); synchronises before it
+ *                                returns. */
+#define SE_HIP_PROJECT_NONE INT32_MIN
+#define SE_HIP_PROJECT_MAX_LAYERS 16
+typedef struct se_hip_project_request {
+  int32_t axis;
+  int32_t lo[2];        /* u, v */
+  int32_t side[2];      /* u, v */
+  int32_t n_layers;
+  int32_t layers[SE_HIP_PROJECT_MAX_LAYERS][2];
+  int32_t stop_at;
+} se_hip_project_request;
+typedef struct se_hip_project_out {
+  uint8_t* status;  /* [L][side[1]][side[0]] */
+  int32_t* first;
+  int32_t* last;
+  int32_t* count;
+} se_hip_project_out;
+int se_hip_project_columns(se_hip_pipeline* p, const se_hip_project_request* request, const se_hip_collide_test* test,
+                           const se_hip_project_out* device_out);
+int se_hip_project_columns_host(se_hip_pipeline* p, const se_hip_project_request* request, const se_hip_collide_test* test,
+                                const se_hip_project_out* host_out);
+
 /* ---- batched collision queries for oriented boxes: "does this robot, at this attitude, touch anything?" for N boxes at once, without
  *      getMap().  Not in the reference; built on its Octree::get and on the classification above.  The host restatement and the literal
  *      definition are include/se/oriented_collision.hpp.

@@ -28,6 +28,7 @@
 #include "se_motion_kernels.h"
 #include "se_oriented_kernels.h"
 #include "se_clearance_kernels.h"
+#include "se_project_kernels.h"
 #include "se_edit_kernels.h"
 #include "se_alloc_kernels.h"
 #include "se_ray_kernels.h"
@@ -2263,6 +2264,71 @@ int se_hip_clearance_boxes_host(se_hip_pipeline* p, const int32_t* host_queries,
                                 const se_hip_clearance_out* host_out) {
   return batch_host(p, host_queries, 7 * sizeof(int32_t), n, clearance_outs(host_out), [&] { return clearance_args(host_queries, n, test, stop_at, host_out); },
                     [&](const void* q, void* const* o) { launch_clearance(p, (const int32_t*)q, n, test, stop_at, o); });
+}
+
+
+// ------------------------------------------------------------------------------------ column projections
+static_assert(SE_HIP_PROJECT_NONE == SE_PROJECT_NONE && SE_HIP_PROJECT_MAX_LAYERS == SE_PROJECT_MAX_LAYERS, "constants of se_hip_project_columns");
+namespace {
+int project_args(const se_hip_project_request* rq, const se_hip_collide_test* test, const se_hip_project_out* out) {
+  const char* who = "se_hip_project_columns: ";
+  if (!rq) return fail(SE_HIP_E_INVALID, std::string(who) + "null request");
+  if (!out || !out->status) return fail(SE_HIP_E_INVALID, std::string(who) + "null out or status");
+  if (int r = collide_test_args("se_hip_project_columns", test, &rq->stop_at)) return r;
+  if (rq->axis < 0 || rq->axis > 2) return fail(SE_HIP_E_INVALID, std::string(who) + "axis must be 0, 1 or 2");
+  if (rq->n_layers < 1 || rq->n_layers > SE_PROJECT_MAX_LAYERS) return fail(SE_HIP_E_INVALID, std::string(who) + "n_layers must lie in 1 .. 16");
+  auto in_limit = [](int64_t v) { return v >= -SE_PROJECT_LIMIT && v <= SE_PROJECT_LIMIT; };
+  for (int k = 0; k < 2; ++k)
+    if (rq->side[k] < 1 || !in_limit(rq->lo[k]) || !in_limit((int64_t)rq->lo[k] + rq->side[k]))
+      return fail(SE_HIP_E_INVALID, std::string(who) + "side < 1, or lo / lo + side beyond +-2^20");
+  for (int l = 0; l < rq->n_layers; ++l)
+    if (!in_limit(rq->layers[l][0]) || !in_limit(rq->layers[l][1]) || rq->layers[l][0] >= rq->layers[l][1])
+      return fail(SE_HIP_E_INVALID, std::string(who) + "a layer with a >= b, or beyond +-2^20");
+  if ((int64_t)rq->n_layers * rq->side[0] * rq->side[1] > ((int64_t)1 << 28)) return fail(SE_HIP_E_INVALID, std::string(who) + "more than 2^28 cells");
+  return SE_HIP_OK;
+}
+// One wave per (tile, layer), grid-stride beyond 2^20 workgroups; one instantiation per brick layout and axis.
+void launch_project(se_hip_pipeline* p, const se_hip_project_request* rq, const se_hip_collide_test* test, uint8_t* status, int32_t* first, int32_t* last, int32_t* count) {
+  ProjectArgs a{};
+  a.lo_u = rq->lo[0]; a.lo_v = rq->lo[1]; a.side_u = rq->side[0]; a.side_v = rq->side[1];
+  a.n_layers = rq->n_layers;
+  for (int l = 0; l < rq->n_layers; ++l) { a.layers[l][0] = rq->layers[l][0]; a.layers[l][1] = rq->layers[l][1]; }
+  a.status = status; a.first = first; a.last = last; a.count = count;
+  a.thr = test->threshold; a.above = test->occupied_above; a.stop_at = (uint32_t)rq->stop_at;
+  const int64_t ntu = ((a.lo_u + a.side_u - 1) >> 3) - (a.lo_u >> 3) + 1, ntv = ((a.lo_v + a.side_v - 1) >> 3) - (a.lo_v >> 3) + 1;
+  const int grid = (int)std::min<int64_t>(ntu * ntv * a.n_layers, 1 << 20);
+  typedef void (*Kernel)(DevMap, ProjectArgs);
+  static const Kernel k[2][3] = {{k_project_columns<false, 0>, k_project_columns<false, 1>, k_project_columns<false, 2>},
+                                 {k_project_columns<true, 0>, k_project_columns<true, 1>, k_project_columns<true, 2>}};
+  hipLaunchKernelGGL(k[p->map.dense ? 1 : 0][rq->axis], dim3(grid), dim3(SE_WG_COLLIDE), 0, p->stream, p->map, a);
+}
+}  // namespace
+
+int se_hip_project_columns(se_hip_pipeline* p, const se_hip_project_request* request, const se_hip_collide_test* test, const se_hip_project_out* device_out) {
+  if (int r = query_prologue(p, [&] { return project_args(request, test, device_out); })) return r;
+  if (int r = check_overflow(p)) return r;
+  launch_project(p, request, test, device_out->status, device_out->first, device_out->last, device_out->count);
+  HIP_TRY(hipGetLastError());
+  return SE_HIP_OK;
+}
+
+int se_hip_project_columns_host(se_hip_pipeline* p, const se_hip_project_request* request, const se_hip_collide_test* test, const se_hip_project_out* host_out) {
+  if (int r = query_prologue(p, [&] { return project_args(request, test, host_out); })) return r;
+  // staging = [first][last][count] (4-byte items, those asked for), then [status]
+  const size_t cells = (size_t)request->n_layers * (size_t)request->side[0] * (size_t)request->side[1];
+  void* const host[4] = {host_out->first, host_out->last, host_out->count, host_out->status};
+  size_t bytes[4], off[4];
+  for (int k = 0; k < 4; ++k) bytes[k] = host[k] ? cells * (k < 3 ? sizeof(int32_t) : 1) : 0;
+  if (int r = reserve_staging(p, staging_layout(bytes, 4, off))) return r;
+  unsigned char* b = p->staging;
+  void* dev[4];
+  for (int k = 0; k < 4; ++k) dev[k] = bytes[k] ? b + off[k] : nullptr;
+  launch_project(p, request, test, (uint8_t*)dev[3], (int32_t*)dev[0], (int32_t*)dev[1], (int32_t*)dev[2]);
+  HIP_TRY(hipGetLastError());
+  for (int k = 0; k < 4; ++k)
+    if (bytes[k]) HIP_TRY(hipMemcpyAsync(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost, p->stream));
+  // (synchronises; a sticky overflow is reported as the other read-back calls report it)
+  return fetch_counters(p);
 }
 
 

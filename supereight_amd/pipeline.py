@@ -95,6 +95,21 @@ CLEARANCE_NONE, CLEARANCE_INVALID = -1, -2
 _CLEARANCE_R_CLAMP = 32768   # an r_max above 32767 is invalid: larger ones are passed as this one, so that they fit the int32 column
 
 
+class _ProjectRequest(C.Structure):
+    """se_hip_project_request of include/se_hip.h."""
+    _fields_ = [("axis", C.c_int32), ("lo", C.c_int32 * 2), ("side", C.c_int32 * 2), ("n_layers", C.c_int32), ("layers", (C.c_int32 * 2) * 16),
+                ("stop_at", C.c_int32)]
+
+
+class _ProjectOut(C.Structure):
+    """se_hip_project_out of include/se_hip.h: output addresses, 0 = not wanted (status is required)."""
+    _fields_ = [("status", C.c_void_p), ("first", C.c_void_p), ("last", C.c_void_p), ("count", C.c_void_p)]
+
+
+# first / last of se_hip_project_columns for a cell without a blocking voxel; the bounds of a valid request
+PROJECT_NONE, PROJECT_LIMIT, PROJECT_MAX_LAYERS, PROJECT_MAX_CELLS = -(1 << 31), 1 << 20, 16, 1 << 28
+
+
 # se_hip_collide_oriented: sub-units per voxel, and the bounds of a valid box (|c_k|, |h_ik|, in sub-units)
 ORIENTED_SUB, ORIENTED_CENTRE_LIMIT, ORIENTED_AXIS_LIMIT = 16, 1 << 20, 1 << 14
 
@@ -235,6 +250,8 @@ EXPORTS = {
     "se_hip_collide_motions_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_MotionOut)]),
     "se_hip_clearance_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_ClearanceOut)]),
     "se_hip_clearance_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_ClearanceOut)]),
+    "se_hip_project_columns": (C.c_int, [C.c_void_p, C.POINTER(_ProjectRequest), C.POINTER(_CollideTest), C.POINTER(_ProjectOut)]),
+    "se_hip_project_columns_host": (C.c_int, [C.c_void_p, C.POINTER(_ProjectRequest), C.POINTER(_CollideTest), C.POINTER(_ProjectOut)]),
     "se_hip_collide_oriented": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_void_p]),
     "se_hip_collide_oriented_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_void_p]),
     "se_hip_edit_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
@@ -926,6 +943,81 @@ class DenseSLAMPipeline:
             self._device_call(torch, q.device, self.lib.se_hip_clearance_boxes, q.data_ptr() if n else None, n, C.byref(test), _MOTION_STOPS[stop_at],
                               C.byref(out))
         return (res["d2"], res["nearest"]) if nearest else res["d2"]
+
+    _PROJECT_OUTPUTS = (("status", np.uint8), ("first", np.int32), ("last", np.int32), ("count", np.int32))
+
+    def project(self, axis, lo, side, layers, stop_at: str = "occupied", threshold: float = 0.0, occupied_above=None, first: bool = True,
+                last: bool = True, count: bool = True, device: bool = False) -> dict:
+        """Column projections of the map (se_hip_project_columns, include/se_hip.h): the 2D grids of a footprint.  axis 0 / 1 / 2: the axis w
+        the columns run along; the two remaining axes in ascending order are u (the fastest index) and v (axis 2: u = x, v = y; axis 1:
+        u = x, v = z; axis 0: u = y, v = z).  lo, side: two integers each, the footprint [lo, lo + side) on (u, v) in voxels; layers: 1 .. 16
+        pairs (a, b), the half-open intervals [a, b) along w.  Cell (l, j, i) holds the voxels with u = lo[0] + i, v = lo[1] + j, w in
+        [a_l, b_l), each classified as collides() classifies it in strict mode (threshold / occupied_above as there; outside the volume is
+        unseen); a voxel blocks when it is occupied (stop_at "occupied") or occupied or unseen ("unseen").  Returns a dict of arrays
+        [L, side[1], side[0]]: "status" (uint8, the min class over the cell: COLLISION_OCCUPIED / _UNSEEN / _EMPTY) and, where asked for,
+        "first" and "last" (int32, the smallest and the largest w of a blocking voxel, PROJECT_NONE where none blocks) and "count" (int32,
+        the number of blocking voxels).  Along z with stop_at "occupied", last is the elevation map and first the ceiling.
+          - device=False: through the host entry; numpy arrays out.
+          - device=True: through the device entry; torch tensors on this handle's GPU out, the handle synchronised before they are returned.
+        A side < 1, an empty layer, a coordinate beyond +-2^20, more than 16 layers or more than 2^28 cells raise ValueError, wrong types
+        TypeError, before any library call."""
+        def ints(name, v, k):
+            a = np.asarray(v)
+            if isinstance(v, (bool, np.bool_)) or a.dtype.kind not in "iu":
+                raise TypeError(f"project: {name} must hold integers, got {a.dtype}")
+            if a.shape != k:
+                raise ValueError(f"project: {name} must have shape {list(k)}, got {list(a.shape)}")
+            return a.astype(np.int64)
+
+        if isinstance(axis, (bool, np.bool_)) or not isinstance(axis, (int, np.integer)):
+            raise TypeError(f"project: axis must be an int, got {type(axis).__name__}")
+        if axis not in (0, 1, 2):
+            raise ValueError(f"project: axis must be 0, 1 or 2, got {axis}")
+        if stop_at not in _MOTION_STOPS:
+            raise ValueError(f"project: stop_at must be one of {sorted(_MOTION_STOPS)}, got {stop_at!r}")
+        if occupied_above is None:
+            occupied_above = self.field == OFUSION
+        if not isinstance(occupied_above, (bool, np.bool_)):
+            raise TypeError(f"project: occupied_above must be a bool, got {type(occupied_above).__name__}")
+        thr = float(threshold)
+        if not np.isfinite(np.float32(thr)):
+            raise ValueError(f"project: threshold must be finite as a float32, got {threshold!r}")
+        lo, side = ints("lo", lo, (2,)), ints("side", side, (2,))
+        if isinstance(layers, (bool, np.bool_)) or layers is None:
+            raise TypeError(f"project: layers must be pairs of integers, got {type(layers).__name__}")
+        lay = np.asarray(layers)
+        if lay.ndim != 2 or lay.shape[1] != 2 or not 1 <= lay.shape[0] <= PROJECT_MAX_LAYERS:
+            raise ValueError(f"project: layers must have shape [L, 2] with L in 1 .. {PROJECT_MAX_LAYERS}, got {list(lay.shape)}")
+        lay = ints("layers", lay, lay.shape)
+        if (side < 1).any():
+            raise ValueError(f"project: side must be >= 1, got {side.tolist()}")
+        if (lay[:, 0] >= lay[:, 1]).any():
+            raise ValueError("project: every layer needs a < b")
+        if (np.abs(np.concatenate([lo, lo + side, lay.reshape(-1)])) > PROJECT_LIMIT).any():
+            raise ValueError("project: lo, lo + side and the layers must lie within +-2^20")
+        n_l, cells = len(lay), len(lay) * int(side[0]) * int(side[1])
+        if cells > PROJECT_MAX_CELLS:
+            raise ValueError(f"project: {cells} cells, more than 2^28")
+        rq = _ProjectRequest()
+        rq.axis, rq.n_layers, rq.stop_at = int(axis), n_l, _MOTION_STOPS[stop_at]
+        for k in range(2):
+            rq.lo[k], rq.side[k] = int(lo[k]), int(side[k])
+        for l in range(n_l):
+            rq.layers[l][0], rq.layers[l][1] = int(lay[l, 0]), int(lay[l, 1])
+        test = _CollideTest(thr, int(bool(occupied_above)))
+        want = {"status": True, "first": bool(first), "last": bool(last), "count": bool(count)}
+        shape = (n_l, int(side[1]), int(side[0]))
+        if not device:
+            res = {k: np.empty(shape, dt) for k, dt in self._PROJECT_OUTPUTS if want[k]}
+            out = _ProjectOut(*(res[k].ctypes.data if k in res else None for k, _ in self._PROJECT_OUTPUTS))
+            self._check(self.lib.se_hip_project_columns_host(self._h, C.byref(rq), C.byref(test), C.byref(out)))
+            return res
+        import torch
+        dev = torch.device("cuda", self._device if self._device is not None else torch.cuda.current_device())
+        res = {k: torch.empty(shape, dtype=getattr(torch, np.dtype(dt).name), device=dev) for k, dt in self._PROJECT_OUTPUTS if want[k]}
+        out = _ProjectOut(*(res[k].data_ptr() if k in res else None for k, _ in self._PROJECT_OUTPUTS))
+        self._device_call(torch, dev, self.lib.se_hip_project_columns, C.byref(rq), C.byref(test), C.byref(out))
+        return res
 
     @staticmethod
     def _edit_only(only) -> int:
