@@ -136,7 +136,21 @@ int se_hip_set_image_ring(se_hip_pipeline* p, float* device_ring, int32_t slots)
  * scan, one thread per pixel; or a one-kernel conversion in front of se_hip_track / se_hip_render_depth / a row-sharded scan) reads the pinned image over
  * PCIe and writes the device image on its way.  No DMA packet, no second queue, no wait for the previous frame: on a streaming handle the input of frame
  * f+1 crosses PCIe inside the launch that raycasts frame f.  The call waits (on the host) only if all three slots are still in flight, i.e. if the caller
- * is three uploads ahead of the device. */
+ * is three uploads ahead of the device.
+ * The depth domain (this call, se_hip_set_depth_device, se_hip_frame, se_hip_frame_tracked, pinned input): ANY float is accepted, and each value does
+ * what the reference's arithmetic does with it (tests/test_gpu_depth_domain.py, bit for bit against the oracle):
+ *   - 0 and -0 are holes ("no measurement") everywhere.
+ *   - A NaN or -inf pixel is a hole for SDF.  A negative pixel is a hole for both sweeps (`depthSample <= 0`), but both allocation scans test
+ *     `== 0` only: its band, mirrored behind the camera, still allocates the blocks it crosses inside the volume, and they stay unwritten.
+ *   - Under OFusion a NaN or +inf pixel allocates nothing and MARKS THE VOXELS THAT PROJECT ONTO IT FREE (`!(depthSample <= 0)` passes, H(NaN)
+ *     clamps to 0.03).  Advice to callers: send 0, not NaN, for "no return" under OFusion.
+ *   - +inf and any depth beyond the far side of the volume carve free space along the pixel (sdf = 1; OFusion: free).
+ *   - Denormals are depths like any other (not flushed): a band around the camera itself.
+ *   - Finite depths must stay below 1000 m in magnitude: the OFusion scan walks the whole ray from the surface back to the camera, dist / step
+ *     trips, and beyond some 2^24 steps the reference's own loop no longer advances.  Nothing refuses or clamps a value (yet).
+ *   - The reference is undefined (it casts NaN to a pixel index or to int) for +inf depth under se_hip_track / se_hip_frame_tracked and for NaN
+ *     under se_hip_render_depth, and so is this library: the tracker forms the same index and READS OUTSIDE THE REFERENCE IMAGES.  Do not hand
+ *     +inf to a tracked frame.  NaN, -inf, negative and -0 pixels under tracking are defined: they have no vertex (`d > 0`). */
 int se_hip_upload_depth(se_hip_pipeline* p, const float* host_depth_m);
 /* mm2metersKernel (se_denseslam/src/preprocessing.cpp:161-188) applied where the image is first read on the device:
  * uint16 millimetres of size (in_w, in_h), an integer multiple of the computation size ("Invalid ratio." = SE_HIP_E_INVALID). */

@@ -311,9 +311,11 @@ __device__ __forceinline__ void se_scan_sdf_wg(const DevMap& m, const float* __r
       int nb = 0;
       // floor(s) as an integer in one instruction (v_cvt_flr_i32_f32 saturates, so a coordinate beyond +-2^31 stays outside);
       // 0 <= floor(s.a) < size on all three axes <=> the OR of the three integers has no bit at or above log2(size) (size is a
-      // power of two; a negative integer has its sign bit set).  The reference's float tests are false for NaN, the conversion
-      // gives 0: a ray with a non-finite origin or step (depth = inf / NaN) is skipped up front, as the reference's tests would
-      // skip every one of its steps -- with finite origin and step no position is NaN.
+      // power of two; a negative integer has its sign bit set).  The reference's float tests are false for NaN; what the conversion
+      // makes of a NaN is not part of the contract (measured on gfx950: +-(2^31 - 1) by the NaN's sign, outside as well -- v_cvt_i32_f32
+      // would give 0, inside), so a ray with a non-finite origin or step (depth = inf / NaN) is skipped up front, as the reference's
+      // tests would skip every one of its steps -- with finite origin and step no position is NaN.  (tests/test_gpu_depth_domain.py
+      // sends such rays; on this hardware they pass with and without the guard.)
       const bool finite = fabsf(origin.x) < INFINITY && fabsf(origin.y) < INFINITY && fabsf(origin.z) < INFINITY &&
                           fabsf(step.x) < INFINITY && fabsf(step.y) < INFINITY && fabsf(step.z) < INFINITY;
       const uint32_t hi_mask = ~(uint32_t)(m.size - 1);

@@ -12,8 +12,8 @@ from oracle.binding import OFUSION, SDF
 from supereight_amd import synthetic as S
 
 
-def render_room_mm(frame: int, width: int, height: int, dim: float, k) -> np.ndarray:
-    """uint16 millimetre depth image of the room + sphere scene seen with intrinsics k = (fx, fy, cx, cy) from synthetic.pose(frame)."""
+def _render_room(frame: int, width: int, height: int, dim: float, k) -> np.ndarray:
+    """float64 z-depth in metres of the room + sphere scene seen with intrinsics k = (fx, fy, cx, cy) from synthetic.pose(frame)."""
     k = np.asarray(k, np.float32).astype(np.float64)
     T = S.pose(frame, dim).astype(np.float64)
     xs = (np.arange(width) + 0.5 - k[2]) / k[0]
@@ -34,8 +34,18 @@ def render_room_mm(frame: int, width: int, height: int, dim: float, k) -> np.nda
     disc = B * B - 4 * A * C
     t_s = (-B - np.sqrt(np.maximum(disc, 0.0))) / (2 * A)
     t_s = np.where((disc >= 0) & (t_s > 0), t_s, np.inf)
-    mm = np.floor(np.minimum(t_room, t_s) * 1000.0)
+    return np.minimum(t_room, t_s)
+
+
+def render_room_mm(frame: int, width: int, height: int, dim: float, k) -> np.ndarray:
+    """uint16 millimetre depth image of the room + sphere scene seen with intrinsics k = (fx, fy, cx, cy) from synthetic.pose(frame)."""
+    mm = np.floor(_render_room(frame, width, height, dim, k) * 1000.0)
     return np.clip(mm, 0, 65535).astype(np.uint16)
+
+
+def render_room_m(frame: int, width: int, height: int, dim: float, k) -> np.ndarray:
+    """The same image in float32 metres WITHOUT the millimetre floor: depths no uint16 millimetre image holds (tests/depth_domain_frames.py)."""
+    return np.ascontiguousarray(_render_room(frame, width, height, dim, k).astype(np.float32))
 
 
 class RoomStream:
