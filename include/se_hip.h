@@ -282,7 +282,9 @@ int se_hip_frame_tracked(se_hip_pipeline* p, const float* device_depth_m, const 
                          const int32_t* pyramid, int32_t n_levels, float pose_inout[16], uint32_t integration_rate, float mu, uint32_t frame);
 /* preprocessing(..., filterInput) (DenseSLAMSystem.cpp:128-141): when on, se_hip_track works on
  * bilateralFilterKernel(float_depth_) (preprocessing.cpp:41-89, gaussian_ of DenseSLAMSystem.cpp:111-118)
- * instead of float_depth_ itself; integration always uses the unfiltered image, as in the reference. */
+ * instead of float_depth_ itself; integration always uses the unfiltered image, as in the reference.
+ * The reference's expf (libm-specific in its last bit) is defined as the correctly rounded exponential, in the kernel and in the
+ * Gaussian table, so the filtered image is the parity oracle's bit for bit, NaN, infinite, negative and denormal pixels included. */
 int se_hip_filter_depth(se_hip_pipeline* p, int32_t on);
 /* scaled_depth_[level] as built by the last se_hip_track ((width >> level) x (height >> level) floats). */
 int se_hip_download_scaled_depth(se_hip_pipeline* p, int32_t level, float* host_out);

@@ -118,6 +118,8 @@ def _declare(lib):
         "so_set_num_threads": (None, [i32]),
         "so_set_sophus_quat": (None, [i32]),
         "so_set_libm_sincos": (None, [i32]),
+        "so_set_libm_exp": (None, [i32]),
+        "so_exp_f32_n": (None, [c_f32p, i32, c_f32p, i32]),
         "so_fp_contract": (i32, []),
     }
     for name, (res, args) in sig.items():
@@ -312,6 +314,22 @@ def oracle_sincos(x):
     if x.size:
         lib.so_sincos_f32(x, x.size, s, c)
     return s, c
+
+
+def oracle_exp(x, libm: bool = False):
+    """The exponential the bilateral filter is DEFINED with (so_exp_f32) of float32 arguments x <= 0 or NaN, float32; libm=True: this
+    host's expf of them, what the filter calls under oracle_set_libm_exp(True)."""
+    lib = load()
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    out = np.empty_like(x)
+    if x.size:
+        lib.so_exp_f32_n(x, x.size, out, int(libm))
+    return out
+
+
+def oracle_set_libm_exp(on: bool):
+    """so_set_libm_exp: the bilateral filter and its Gaussian table call this host's expf (the reference's own arithmetic) instead of so_exp_f32."""
+    load().so_set_libm_exp(int(on))
 
 
 def oracle_solve6(vals27):

@@ -1617,7 +1617,7 @@ int se_hip_track(se_hip_pipeline* p, const float k[4], float icp_threshold, uint
   const float* d0 = p->depth;
   if (p->filter_input) {   // DenseSLAMSystem.cpp:132-135; gaussian_: DenseSLAMSystem.cpp:111-118
     Gauss5 G;
-    for (unsigned int i = 0; i < 5; i++) { const int x = (int)i - 2; G.g[i] = expf(-(x * x) / (2 * 4.0f * 4.0f)); }
+    for (unsigned int i = 0; i < 5; i++) { const int x = (int)i - 2; G.g[i] = se_exp_f32(-(x * x) / (2 * 4.0f * 4.0f)); }
     hipLaunchKernelGGL(k_bilateral_filter, dim3((W + 255) / 256, H), dim3(256), 0, s, p->pyr_depth[0], d0, W, H, G, 0.1f);
     d0 = p->pyr_depth[0];
   }

@@ -12,9 +12,31 @@
 
 struct TrackData { int result; float error; float J[6]; };   // se_denseslam/include/se/commons.h:249-253
 
-// bilateralFilterKernel (preprocessing.cpp:41-89), radius 2.  The reference's expf is its C library's;
-// here it is the correctly rounded one (double exp, rounded once), which differs from a given libm
-// in the last bit of a small fraction of arguments -- the one stage with a stated tolerance.
+// exp of a float x <= 0 (or NaN), DEFINED (oracle and device alike, see oracle/se_oracle.cpp so_exp_f32) as the correctly rounded result: the
+// reference's expf is its C library's, libm-specific in the last bit.  Evaluated in double -- k = rint(x / ln2), r = x - k ln2 with fdlibm's two-part
+// ln2 (k * LN2_HI is exact for |k| <= 151), the Taylor polynomial of degree 13 by Horner, the product with 2^k (a normal double for k >= -151) -- and
+// rounded once, so float denormals are correctly rounded too.  Plain IEEE double arithmetic in source order (no FMA contraction, no device library
+// call), so host and device agree bit for bit (tests/test_gpu_icp_math.py); tests/test_exp_host.py holds the definition to exp at 120 bits.
+__host__ __device__ inline float se_exp_f32(float xf) {
+  if (xf != xf) return xf;
+  if (xf < -104.0f) return 0.0f;
+  if (xf == 0.0f) return 1.0f;
+  const double INV_LN2 = 1.44269504088896338700e+00, LN2_HI = 6.93147180369123816490e-01, LN2_LO = 1.90821492927058770002e-10;
+  const double E2 = 5.00000000000000000000e-01, E3 = 1.66666666666666657415e-01, E4 = 4.16666666666666643537e-02, E5 = 8.33333333333333321769e-03,
+               E6 = 1.38888888888888894189e-03, E7 = 1.98412698412698412526e-04, E8 = 2.48015873015873015658e-05, E9 = 2.75573192239858925110e-06,
+               E10 = 2.75573192239858882758e-07, E11 = 2.50521083854417202239e-08, E12 = 2.08767569878681001866e-09, E13 = 1.60590438368216133409e-10;
+  const double x = (double)xf;
+  const double kd = rint(x * INV_LN2);
+  const double r = (x - kd * LN2_HI) - kd * LN2_LO;
+  const double p = 1.0 + r * (1.0 + r * (E2 + r * (E3 + r * (E4 + r * (E5 + r * (E6 + r * (E7 + r * (E8 + r * (E9 + r * (E10 + r * (E11 + r * (E12 + r * E13))))))))))));
+  const unsigned long long sb = (unsigned long long)(1023 + (long long)kd) << 52;
+  double s;
+  memcpy(&s, &sb, sizeof s);
+  return (float)(p * s);
+}
+
+// bilateralFilterKernel (preprocessing.cpp:41-89), radius 2.  The reference's expf is se_exp_f32 here and so_exp_f32 in the oracle, the Gaussian
+// table's too (se_hip_track), so the filtered image is the oracle's bit for bit (tests/test_gpu_bilateral.py).
 struct Gauss5 { float g[5]; };
 __global__ void k_bilateral_filter(float* __restrict__ out, const float* __restrict__ in, int width, int height, Gauss5 G, float e_d) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
@@ -32,7 +54,7 @@ __global__ void k_bilateral_filter(float* __restrict__ out, const float* __restr
       const float curPix = in[ux + uy * width];
       if (curPix > 0) {
         const float mod = (curPix - center) * (curPix - center);
-        const float factor = G.g[i + 2] * G.g[j + 2] * (float)exp((double)(-mod / e_d_squared_2));
+        const float factor = G.g[i + 2] * G.g[j + 2] * se_exp_f32(-mod / e_d_squared_2);
         t += factor * curPix;
         sum += factor;
       }

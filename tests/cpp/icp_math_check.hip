@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE (not part of the product library): the scalar core of the device-resident ICP -- se_sincos_f32, se_solve6_wave and
-// se_icp_finalize of supereight_amd/csrc/se_track_kernels.h, the production functions themselves -- run on argument lists of the caller's
+// se_icp_finalize, and the bilateral filter's se_exp_f32, of supereight_amd/csrc/se_track_kernels.h, the production functions themselves -- run on argument lists of the caller's
 // choice, so that tests/test_gpu_icp_math.py can compare them with the oracle where no scene takes them.
-// Built on demand by that test with the library's own flags.  Every pointer of the three entries is a host pointer.
+// Built on demand by that test with the library's own flags.  Every pointer of the entries is a host pointer.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -10,6 +10,9 @@
 namespace {
 __global__ void k_chk_sincos(const float* __restrict__ x, int n, float* __restrict__ s, float* __restrict__ c) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) se_sincos_f32(x[i], s + i, c + i);
+}
+__global__ void k_chk_exp(const float* __restrict__ x, int n, float* __restrict__ e) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) e[i] = se_exp_f32(x[i]);
 }
 
 // one wave per system: the 27 values go to LDS (where k_icp_iter keeps them), x[6] comes out of lane 0; agree = every lane holds the same x
@@ -69,6 +72,17 @@ extern "C" int se_icp_math_sincos(const float* x, int n, float* s, float* c) {
   hipLaunchKernelGGL(k_chk_sincos, dim3(2048), dim3(256), 0, 0, dx.as<float>(), n, ds.as<float>(), dc.as<float>());
   if (int r = finish()) return r;
   return ds.get(s, bytes) && dc.get(c, bytes) ? 0 : -3;
+}
+
+// se_exp_f32, the bilateral filter's exponential: arguments <= 0 or NaN
+extern "C" int se_icp_math_exp(const float* x, int n, float* e) {
+  if (n <= 0) return 0;
+  const size_t bytes = (size_t)n * sizeof(float);
+  DevBuf dx(bytes, x), de(bytes);
+  if (!dx.ok || !de.ok) return -1;
+  hipLaunchKernelGGL(k_chk_exp, dim3(2048), dim3(256), 0, 0, dx.as<float>(), n, de.as<float>());
+  if (int r = finish()) return r;
+  return de.get(e, bytes) ? 0 : -3;
 }
 
 extern "C" int se_icp_math_solve6(const float* vals27, int n, float* x6, int* agree) {

@@ -1,5 +1,6 @@
 """The scalar core of the device-resident ICP against the oracle where no scene takes it: se_sincos_f32, se_solve6_wave and se_icp_finalize
-(strip and segment sums, solve, SE(3) exponential, pose product, convergence test) of supereight_amd/csrc/se_track_kernels.h, called
+(strip and segment sums, solve, SE(3) exponential, pose product, convergence test), and the bilateral filter's se_exp_f32, of
+supereight_amd/csrc/se_track_kernels.h, called
 through tests/cpp/icp_math_check.hip on the argument lists of tests/icp_edge_util.py.  Everything is compared bit for bit; where the oracle's
 value is a NaN the device's must be a NaN (payload and sign are not part of the contract).  tests/test_icp_math_host.py asserts, on the oracle
 alone, that the lists reach what they are there for: every failing column of the factorisation, every quadrant of the sine, both small-angle
@@ -11,7 +12,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from oracle.binding import oracle_sincos
+from oracle.binding import oracle_exp, oracle_sincos
+from tests import bilateral_util as B
 from tests import icp_edge_util as U
 
 pytestmark = pytest.mark.gpu
@@ -36,6 +38,7 @@ def chk():
     f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
     i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
     lib.se_icp_math_sincos.argtypes = [f32p, C.c_int, f32p, f32p]
+    lib.se_icp_math_exp.argtypes = [f32p, C.c_int, f32p]
     lib.se_icp_math_solve6.argtypes = [f32p, C.c_int, f32p, i32p]
     lib.se_icp_math_finalize.argtypes = [f32p, f32p, f32p, C.c_int, f32p, f32p, i32p]
     assert lib.se_icp_math_segments() == U.SEGMENTS
@@ -55,6 +58,18 @@ def test_sine_and_cosine_in_every_quadrant(chk):
     same = U.same_bits(s_g, s_c) & U.same_bits(c_g, c_c)
     print(f"{x.size} arguments, {(~same).sum()} differ")
     assert same.all(), _first_bad(same, x, s_g, s_c, c_g, c_c)
+
+
+def test_exponential_of_the_bilateral_filter(chk):
+    """se_exp_f32 on the device against so_exp_f32 on every argument tests/test_exp_host.py holds the definition to: the ends of the float
+    range of the result, denormal results, every scale 2^k, the filter's own arguments, NaN."""
+    x = B.exp_arguments()
+    e_c = oracle_exp(x)
+    e_g = np.full_like(x, -1.0)
+    assert chk.se_icp_math_exp(x, x.size, e_g) == 0
+    same = U.same_bits(e_g, e_c)
+    print(f"{x.size} arguments, {(~same).sum()} differ")
+    assert same.all(), _first_bad(same, x, e_g, e_c)
 
 
 def test_wave_solve_gives_up_where_the_oracle_does(chk):
