@@ -221,6 +221,13 @@ class DenseSLAMSystem {
   bool projectColumns(const se_hip_project_request& request, const se_hip_collide_test& test, se_hip_project_out& host_out) {
     return ok(se_hip_project_columns_host(h_, &request, &test, &host_out));
   }
+  /* Not in the reference's class: the distance field of a region -- for every voxel v of [lo, lo + side) what clearanceOf answers for the box
+   * [v, v + robot) with request.r_max and request.stop_at -- se_hip_distance_field_host, definitions in se_hip.h.  The arrays of host_out are
+   * [side z][side y][side x] (nearest: [3] more); host_out.d2 is required, a null host_out.nearest means "not wanted".  The answers are those
+   * of se::geometry::distance_field (include/se/distance_field.hpp) on the getMap() snapshot. */
+  bool distanceField(const se_hip_field_request& request, const se_hip_collide_test& test, se_hip_field_out& host_out) {
+    return ok(se_hip_distance_field_host(h_, &request, &test, &host_out));
+  }
   /* Not in the reference's class: collision queries for n oriented boxes (host_boxes[n][12]: centre xyz, then the half-axes h0, h1, h2 xyz, in
    * sub-units of 1 / SE_HIP_ORIENTED_SUB voxel), exact for the box given -- se_hip_collide_oriented_host, definitions in se_hip.h.
    * host_status[n] receives 0 occupied, 1 unseen, 2 empty, 255 invalid box.  The answers are those of se::geometry::oriented_status

@@ -521,6 +521,55 @@ int se_hip_project_columns(se_hip_pipeline* p, const se_hip_project_request* req
 int se_hip_project_columns_host(se_hip_pipeline* p, const se_hip_project_request* request, const se_hip_collide_test* test,
                                 const se_hip_project_out* host_out);
 
+/* ---- the distance field of a region: "how far is every position of this region from the nearest obstacle?" -- the ESDF a gradient-based
+ *      planner differentiates, or the C-space map of a box robot -- in one call, without getMap().  Not in the reference; it is the answer of
+ *      se_hip_clearance_boxes for every voxel of the region, bit for bit.  The host restatement and the literal definition are
+ *      include/se/distance_field.hpp.
+ * Request (se_hip_field_request, a host struct that is copied into the launch), in voxels:
+ *   lo, side  the region [lo, lo + side) per axis (x, y, z).
+ *   robot     the side of the box whose min corner is placed at each voxel of the region; (1, 1, 1) gives the plain voxel field.
+ *   r_max, stop_at  as in se_hip_clearance_boxes (r_max at most 255 here).
+ * Outputs (se_hip_field_out; a null nearest means "not wanted", d2 is required):
+ *   d2[side z][side y][side x]          (int32) entry (k, j, i) is exactly the d2 that se_hip_clearance_boxes returns for the query
+ *                                       (lo + (i, j, k), robot, r_max) under the same test and stop_at, SE_HIP_CLEARANCE_NONE included.
+ *                                       Blocking voxels outside the region count, and so do those outside the volume (unseen): the region
+ *                                       may stick out of the volume or lie wholly outside it.
+ *   nearest[side z][side y][side x][3]  (int32, x y z) that query's nearest, with the same (z, y, x) tie rule; INT32_MIN three times for NONE.
+ *   Classification, the gap formula, "a pending index entry counts as absent" and the independence of how the tree happens to be subdivided
+ *   are as in se_hip_clearance_boxes.
+ * The whole call is refused with SE_HIP_E_INVALID, and then reads no map memory and writes nothing, for: a null request, test, out or d2
+ * pointer; a side or robot entry < 1; a robot entry > 256; r_max outside [0, 255]; any of lo, lo + side + robot outside [-2^19, 2^19] (so
+ * that every voxel's query is a valid clearance query); side[0] * side[1] * side[2] > 2^24; side[0] * D1 * D2 > 2^28 with D_k = side[k] +
+ * robot[k] + 2 r_max + 1 (the entries of the x pass's work buffer: the call keeps side[0] * D1 * D2 * 2 + side[0] * side[1] * D2 * 4 bytes
+ * in the handle's staging buffer, at most 512 MiB + 1 GiB); a stop_at, threshold or occupied_above that se_hip_clearance_boxes refuses.
+ * A third work buffer, the blocking bits, is not bounded by a refusal of its own: one bit per voxel of the block-aligned hull of the
+ * D0 x D1 x D2 domain, rows along x padded to 8 bytes, i.e. at most ((D0 + 14) / 8 + 8) * (D1 + 14) * (D2 + 14) bytes.  For regions that are
+ * not thin along x it is the smallest of the three; for a thin one with a large robot and r_max it is the largest -- side (1, 4096, 4096)
+ * with robot 256 and r_max 255 is a valid request that needs 2.3 GB of bits, and under the refusals above the worst case (side[0] = 1, D0 =
+ * 768, D1 * D2 = 2^28) stays below 32 GiB.  A staging buffer the device cannot provide fails the call with SE_HIP_E_DEVICE before anything
+ * is launched or written.
+ * Both entries answer for the map after everything enqueued before them (a scan that ran on the side stream included), report a sticky
+ * SE_HIP_E_CAPACITY like the other read-back calls, and leave the map, the images and the launch counters (SE_HIP_K_*) alone.
+ *   se_hip_distance_field       device output arrays; enqueued on the handle's stream, asynchronous like the stage calls -- but for one
+ *                               thing: when the work buffers need a larger staging buffer than the handle holds, growing it waits for the
+ *                               work enqueued before (the old buffer may still be read).
+ *   se_hip_distance_field_host  host output arrays; staged through the same buffer; synchronises before it returns. */
+typedef struct se_hip_field_request {
+  int32_t lo[3];      /* x, y, z */
+  int32_t side[3];
+  int32_t robot[3];
+  int32_t r_max;
+  int32_t stop_at;
+} se_hip_field_request;
+typedef struct se_hip_field_out {
+  int32_t* d2;       /* [side z][side y][side x]    */
+  int32_t* nearest;  /* [side z][side y][side x][3] */
+} se_hip_field_out;
+int se_hip_distance_field(se_hip_pipeline* p, const se_hip_field_request* request, const se_hip_collide_test* test,
+                          const se_hip_field_out* device_out);
+int se_hip_distance_field_host(se_hip_pipeline* p, const se_hip_field_request* request, const se_hip_collide_test* test,
+                               const se_hip_field_out* host_out);
+
 /* ---- batched collision queries for oriented boxes: "does this robot, at this attitude, touch anything?" for N boxes at once, without
  *      getMap().  Not in the reference; built on its Octree::get and on the classification above.  The host restatement and the literal
  *      definition are include/se/oriented_collision.hpp.

@@ -29,6 +29,7 @@
 #include "se_oriented_kernels.h"
 #include "se_clearance_kernels.h"
 #include "se_project_kernels.h"
+#include "se_field_kernels.h"
 #include "se_edit_kernels.h"
 #include "se_alloc_kernels.h"
 #include "se_ray_kernels.h"
@@ -2327,6 +2328,92 @@ int se_hip_project_columns_host(se_hip_pipeline* p, const se_hip_project_request
   HIP_TRY(hipGetLastError());
   for (int k = 0; k < 4; ++k)
     if (bytes[k]) HIP_TRY(hipMemcpyAsync(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost, p->stream));
+  // (synchronises; a sticky overflow is reported as the other read-back calls report it)
+  return fetch_counters(p);
+}
+
+
+// ------------------------------------------------------------------------------------ distance field of a region
+static_assert(SE_HIP_CLEARANCE_NONE == SE_FIELD_NONE, "d2 code of se_hip_distance_field");
+namespace {
+int field_args(const se_hip_field_request* rq, const se_hip_collide_test* test, const se_hip_field_out* out) {
+  const std::string who = "se_hip_distance_field: ";
+  if (!rq) return fail(SE_HIP_E_INVALID, who + "null request");
+  if (!out || !out->d2) return fail(SE_HIP_E_INVALID, who + "null out or d2");
+  if (int r = collide_test_args("se_hip_distance_field", test, &rq->stop_at)) return r;
+  if (rq->r_max < 0 || rq->r_max > SE_FIELD_RMAX) return fail(SE_HIP_E_INVALID, who + "r_max must lie in 0 .. 255");
+  int64_t voxels = 1;
+  for (int k = 0; k < 3; ++k) {
+    if (rq->side[k] < 1 || rq->robot[k] < 1 || rq->robot[k] > SE_FIELD_ROBOT) return fail(SE_HIP_E_INVALID, who + "side < 1, or robot outside 1 .. 256");
+    const int64_t a = rq->lo[k], b = (int64_t)rq->lo[k] + rq->side[k] + rq->robot[k];
+    if (a < -SE_FIELD_LIMIT || a > SE_FIELD_LIMIT || b < -SE_FIELD_LIMIT || b > SE_FIELD_LIMIT) return fail(SE_HIP_E_INVALID, who + "lo or lo + side + robot beyond +-2^19");
+    voxels *= rq->side[k];   // (each side <= 2^20: the product of three stays inside int64)
+  }
+  if (voxels > SE_FIELD_MAX_VOXELS) return fail(SE_HIP_E_INVALID, who + "more than 2^24 voxels");
+  const int64_t d1 = (int64_t)rq->side[1] + rq->robot[1] + 2 * rq->r_max + 1, d2 = (int64_t)rq->side[2] + rq->robot[2] + 2 * rq->r_max + 1;
+  if ((int64_t)rq->side[0] * d1 * d2 > SE_FIELD_MAX_WORK) return fail(SE_HIP_E_INVALID, who + "side[0] * D1 * D2 beyond 2^28");
+  return SE_HIP_OK;
+}
+// The launch arguments of a checked request but the buffers, and the bytes of the three work buffers: bit rows, y pass, x pass (in the order
+// staging_layout wants them: 8-byte, 4-byte, 2-byte items).
+FieldArgs field_plan(const se_hip_field_request* rq, const se_hip_collide_test* test, size_t bytes[3]) {
+  FieldArgs a{};
+  a.r_max = rq->r_max;
+  for (int k = 0; k < 3; ++k) {
+    a.lo[k] = rq->lo[k]; a.side[k] = rq->side[k]; a.robot[k] = rq->robot[k];
+    a.D[k] = rq->side[k] + rq->robot[k] + 2 * rq->r_max + 1;
+    const int first = rq->lo[k] - 1 - rq->r_max;
+    a.b0[k] = first >> 3;   // (>> 3 floors for negative coordinates too)
+    a.nb[k] = ((first + a.D[k] - 1) >> 3) - a.b0[k] + 1;
+  }
+  a.words = (a.nb[0] + 7) / 8;
+  a.thr = test->threshold; a.above = test->occupied_above; a.stop_at = (uint32_t)rq->stop_at;
+  bytes[0] = (size_t)a.nb[2] * 8u * (size_t)a.nb[1] * 8u * (size_t)a.words * sizeof(unsigned long long);
+  bytes[1] = (size_t)a.D[2] * (size_t)a.side[1] * (size_t)a.side[0] * sizeof(uint32_t);
+  bytes[2] = (size_t)a.D[2] * (size_t)a.D[1] * (size_t)a.side[0] * sizeof(int16_t);
+  return a;
+}
+// Four plain launches; every grid is bounded and its kernel strides over the rest.
+void launch_field(se_hip_pipeline* p, const FieldArgs& a) {
+  auto grid = [](size_t lanes, size_t wg) { return dim3((unsigned)std::min<size_t>((lanes + wg - 1) / wg, (size_t)1 << 20)); };
+  const size_t cells = (size_t)a.nb[0] * (size_t)a.nb[1] * (size_t)a.nb[2], s0 = (size_t)a.side[0], s1 = (size_t)a.side[1];
+  hipLaunchKernelGGL(p->map.dense ? k_field_classify<true> : k_field_classify<false>, grid(cells, 1), dim3(SE_WG_COLLIDE), 0, p->stream, p->map, a);
+  hipLaunchKernelGGL(k_field_x, grid(s0 * (size_t)a.D[1] * (size_t)a.D[2], SE_WG_FIELD), dim3(SE_WG_FIELD), 0, p->stream, a);
+  hipLaunchKernelGGL(k_field_y, grid(s0 * s1 * (size_t)a.D[2], SE_WG_FIELD), dim3(SE_WG_FIELD), 0, p->stream, a);
+  hipLaunchKernelGGL(k_field_z, grid(s0 * s1 * (size_t)a.side[2], SE_WG_FIELD), dim3(SE_WG_FIELD), 0, p->stream, a);
+}
+}  // namespace
+
+int se_hip_distance_field(se_hip_pipeline* p, const se_hip_field_request* request, const se_hip_collide_test* test, const se_hip_field_out* device_out) {
+  if (int r = query_prologue(p, [&] { return field_args(request, test, device_out); })) return r;
+  if (int r = check_overflow(p)) return r;
+  // staging = [bit rows][y pass][x pass]: the work buffers only
+  size_t bytes[3], off[3];
+  FieldArgs a = field_plan(request, test, bytes);
+  if (int r = reserve_staging(p, staging_layout(bytes, 3, off))) return r;
+  unsigned char* b = p->staging;
+  a.bits = (unsigned long long*)(b + off[0]); a.ay = (uint32_t*)(b + off[1]); a.ax = (int16_t*)(b + off[2]);
+  a.d2 = device_out->d2; a.nearest = device_out->nearest;
+  launch_field(p, a);
+  HIP_TRY(hipGetLastError());
+  return SE_HIP_OK;
+}
+
+int se_hip_distance_field_host(se_hip_pipeline* p, const se_hip_field_request* request, const se_hip_collide_test* test, const se_hip_field_out* host_out) {
+  if (int r = query_prologue(p, [&] { return field_args(request, test, host_out); })) return r;
+  // staging = [bit rows][y pass][d2][nearest, if asked for][x pass]: 8-byte, then 4-byte, then 2-byte items
+  size_t work[3], bytes[5], off[5];
+  FieldArgs a = field_plan(request, test, work);
+  const size_t voxels = (size_t)a.side[0] * (size_t)a.side[1] * (size_t)a.side[2];
+  bytes[0] = work[0]; bytes[1] = work[1]; bytes[2] = voxels * sizeof(int32_t); bytes[3] = host_out->nearest ? 3 * voxels * sizeof(int32_t) : 0; bytes[4] = work[2];
+  if (int r = reserve_staging(p, staging_layout(bytes, 5, off))) return r;
+  unsigned char* b = p->staging;
+  a.bits = (unsigned long long*)(b + off[0]); a.ay = (uint32_t*)(b + off[1]); a.ax = (int16_t*)(b + off[4]);
+  a.d2 = (int32_t*)(b + off[2]); a.nearest = bytes[3] ? (int32_t*)(b + off[3]) : nullptr;
+  launch_field(p, a);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(host_out->d2, a.d2, bytes[2], hipMemcpyDeviceToHost, p->stream));
+  if (bytes[3]) HIP_TRY(hipMemcpyAsync(host_out->nearest, a.nearest, bytes[3], hipMemcpyDeviceToHost, p->stream));
   // (synchronises; a sticky overflow is reported as the other read-back calls report it)
   return fetch_counters(p);
 }

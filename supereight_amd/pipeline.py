@@ -110,6 +110,20 @@ class _ProjectOut(C.Structure):
 PROJECT_NONE, PROJECT_LIMIT, PROJECT_MAX_LAYERS, PROJECT_MAX_CELLS = -(1 << 31), 1 << 20, 16, 1 << 28
 
 
+class _FieldRequest(C.Structure):
+    """se_hip_field_request of include/se_hip.h."""
+    _fields_ = [("lo", C.c_int32 * 3), ("side", C.c_int32 * 3), ("robot", C.c_int32 * 3), ("r_max", C.c_int32), ("stop_at", C.c_int32)]
+
+
+class _FieldOut(C.Structure):
+    """se_hip_field_out of include/se_hip.h: output addresses, nearest 0 = not wanted."""
+    _fields_ = [("d2", C.c_void_p), ("nearest", C.c_void_p)]
+
+
+# the bounds of a valid se_hip_distance_field request
+FIELD_LIMIT, FIELD_R_MAX, FIELD_ROBOT_MAX, FIELD_MAX_VOXELS, FIELD_MAX_WORK = 1 << 19, 255, 256, 1 << 24, 1 << 28
+
+
 # se_hip_collide_oriented: sub-units per voxel, and the bounds of a valid box (|c_k|, |h_ik|, in sub-units)
 ORIENTED_SUB, ORIENTED_CENTRE_LIMIT, ORIENTED_AXIS_LIMIT = 16, 1 << 20, 1 << 14
 
@@ -252,6 +266,8 @@ EXPORTS = {
     "se_hip_clearance_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_ClearanceOut)]),
     "se_hip_project_columns": (C.c_int, [C.c_void_p, C.POINTER(_ProjectRequest), C.POINTER(_CollideTest), C.POINTER(_ProjectOut)]),
     "se_hip_project_columns_host": (C.c_int, [C.c_void_p, C.POINTER(_ProjectRequest), C.POINTER(_CollideTest), C.POINTER(_ProjectOut)]),
+    "se_hip_distance_field": (C.c_int, [C.c_void_p, C.POINTER(_FieldRequest), C.POINTER(_CollideTest), C.POINTER(_FieldOut)]),
+    "se_hip_distance_field_host": (C.c_int, [C.c_void_p, C.POINTER(_FieldRequest), C.POINTER(_CollideTest), C.POINTER(_FieldOut)]),
     "se_hip_collide_oriented": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_void_p]),
     "se_hip_collide_oriented_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_void_p]),
     "se_hip_edit_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
@@ -1018,6 +1034,70 @@ class DenseSLAMPipeline:
         out = _ProjectOut(*(res[k].data_ptr() if k in res else None for k, _ in self._PROJECT_OUTPUTS))
         self._device_call(torch, dev, self.lib.se_hip_project_columns, C.byref(rq), C.byref(test), C.byref(out))
         return res
+
+    def distance_field(self, lo, side, r_max, robot=(1, 1, 1), stop_at: str = "occupied", threshold: float = 0.0, occupied_above=None,
+                       nearest: bool = False, device: bool = False):
+        """The distance field of a map region (se_hip_distance_field, include/se_hip.h): lo, side three integers each, the region
+        [lo, lo + side) in voxels (x, y, z); robot the side of the box whose min corner is placed at each voxel ((1, 1, 1): the plain voxel
+        field); r_max the search radius in voxels, 0 .. 255.  Returns d2 [side z, side y, side x] int32: entry (k, j, i) is exactly what
+        clearance() answers for the box (lo + (i, j, k), robot) with this r_max, stop_at, threshold and occupied_above -- the squared distance
+        to the nearest blocking voxel, 0 when they touch, CLEARANCE_NONE (-1) when none lies within r_max; blocking voxels outside the region
+        and outside the volume (unseen) count.  With nearest, (d2, nearest): that voxel [side z, side y, side x, 3] int32 x y z, among
+        equally near ones the smallest in (z, y, x) order; INT32_MIN where d2 is CLEARANCE_NONE.
+          - device=False: through the host entry; numpy arrays out.
+          - device=True: through the device entry; torch tensors on this handle's GPU out, the handle synchronised before they are returned.
+        A side or robot < 1, a robot > 256, r_max outside 0 .. 255, lo or lo + side + robot beyond +-2^19, more than 2^24 voxels or
+        side[0] * D1 * D2 > 2^28 (D_k = side[k] + robot[k] + 2 r_max + 1) raise ValueError, wrong types TypeError, before any library call."""
+        def ints(name, v):
+            a = np.asarray(v)
+            if isinstance(v, (bool, np.bool_)) or a.dtype.kind not in "iu":
+                raise TypeError(f"distance_field: {name} must hold integers, got {a.dtype}")
+            if a.shape != (3,):
+                raise ValueError(f"distance_field: {name} must have shape [3], got {list(a.shape)}")
+            return [int(x) for x in a]
+
+        if stop_at not in _MOTION_STOPS:
+            raise ValueError(f"distance_field: stop_at must be one of {sorted(_MOTION_STOPS)}, got {stop_at!r}")
+        if occupied_above is None:
+            occupied_above = self.field == OFUSION
+        if not isinstance(occupied_above, (bool, np.bool_)):
+            raise TypeError(f"distance_field: occupied_above must be a bool, got {type(occupied_above).__name__}")
+        thr = float(threshold)
+        if not np.isfinite(np.float32(thr)):
+            raise ValueError(f"distance_field: threshold must be finite as a float32, got {threshold!r}")
+        if isinstance(r_max, (bool, np.bool_)) or not isinstance(r_max, (int, np.integer)):
+            raise TypeError(f"distance_field: r_max must be an int, got {type(r_max).__name__}")
+        lo, side, robot, r = ints("lo", lo), ints("side", side), ints("robot", robot), int(r_max)
+        if min(side) < 1 or min(robot) < 1 or max(robot) > FIELD_ROBOT_MAX:
+            raise ValueError(f"distance_field: side must be >= 1 and robot in 1 .. {FIELD_ROBOT_MAX}, got {side}, {robot}")
+        if not 0 <= r <= FIELD_R_MAX:
+            raise ValueError(f"distance_field: r_max must lie in 0 .. {FIELD_R_MAX}, got {r}")
+        if any(abs(v) > FIELD_LIMIT for k in range(3) for v in (lo[k], lo[k] + side[k] + robot[k])):
+            raise ValueError("distance_field: lo and lo + side + robot must lie within +-2^19")
+        if side[0] * side[1] * side[2] > FIELD_MAX_VOXELS:
+            raise ValueError(f"distance_field: {side[0] * side[1] * side[2]} voxels, more than 2^24")
+        work = side[0] * (side[1] + robot[1] + 2 * r + 1) * (side[2] + robot[2] + 2 * r + 1)
+        if work > FIELD_MAX_WORK:
+            raise ValueError(f"distance_field: side[0] * D1 * D2 = {work}, more than 2^28")
+        rq = _FieldRequest()
+        rq.r_max, rq.stop_at = r, _MOTION_STOPS[stop_at]
+        for k in range(3):
+            rq.lo[k], rq.side[k], rq.robot[k] = lo[k], side[k], robot[k]
+        test = _CollideTest(thr, int(bool(occupied_above)))
+        shape = (side[2], side[1], side[0])
+        if not device:
+            d2 = np.empty(shape, np.int32)
+            near = np.empty(shape + (3,), np.int32) if nearest else None
+            out = _FieldOut(d2.ctypes.data, near.ctypes.data if nearest else None)
+            self._check(self.lib.se_hip_distance_field_host(self._h, C.byref(rq), C.byref(test), C.byref(out)))
+            return (d2, near) if nearest else d2
+        import torch
+        dev = torch.device("cuda", self._device if self._device is not None else torch.cuda.current_device())
+        d2 = torch.empty(shape, dtype=torch.int32, device=dev)
+        near = torch.empty(shape + (3,), dtype=torch.int32, device=dev) if nearest else None
+        out = _FieldOut(d2.data_ptr(), near.data_ptr() if nearest else None)
+        self._device_call(torch, dev, self.lib.se_hip_distance_field, C.byref(rq), C.byref(test), C.byref(out))
+        return (d2, near) if nearest else d2
 
     @staticmethod
     def _edit_only(only) -> int:
