@@ -1506,8 +1506,8 @@ class DenseSLAMPipeline:
         pools are compact afterwards.  pose_ and the vertex / normal images are untouched: tracking goes on.  A block that holds nothing
         but is still in view and in the allocation band comes back with the next allocation scan.  Returns a dict: blocks_kept,
         blocks_released, nodes_kept, nodes_released, blocks_released_observed and region = (lo, hi), the half-open voxel box of the
-        released blocks (zeros if none; a LiveMesh is brought up to date with update(pipe, region=region)).  Wrong arguments raise before
-        any library call."""
+        released blocks (zeros if none; a LiveMesh is brought up to date with update(pipe, region=(lo - 1, hi)), as after an edit: the
+        last cells of the blocks below a released one read its first voxel layer).  Wrong arguments raise before any library call."""
         rec = self._release_arguments(boxes, what)
         out, box = np.zeros(5, np.int64), np.zeros(6, np.int32)
         self._check(self.lib.se_hip_release_boxes(self._h, rec.ctypes.data if len(rec) else None, len(rec), out.ctypes.data, box.ctypes.data))
@@ -1569,8 +1569,8 @@ class DenseSLAMPipeline:
         in this map's (rigid_pull turns it into the pull transform), or `pull` itself: src_from_dst as float32 [12] or [3, 4], in voxels.
         Node values do not take part.  `src` is only read; this map's vertex / normal images stay valid.  Returns blocks_combined (existed
         and received a sample), blocks_created, voxels_observed (voxels that received a sample), voxels_both (of those, observed here before)
-        and region = (lo, hi), the half-open voxel box of the blocks that received samples (zeros if none), fit for
-        LiveMesh.update(pipe, region=...).  Wrong arguments raise before any library call."""
+        and region = (lo, hi), the half-open voxel box of the blocks that received samples (zeros if none; a LiveMesh is brought up to
+        date with update(pipe, region=(lo - 1, hi)), as after an edit).  Wrong arguments raise before any library call."""
         if (T_dst_src is None) == (pull is None):
             raise TypeError("merge_rigid: give exactly one of T_dst_src and pull")
         _, rule = self._merge_arguments(src, (0, 0, 0), mode, max_weight)

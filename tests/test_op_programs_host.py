@@ -65,9 +65,10 @@ CASES = [(name, f) for name in P.PROGRAMS for f in FIELDS]
 
 @pytest.mark.parametrize("name,field", CASES, ids=[f"{n}-{FIELD_IDS[f]}" for n, f in CASES])
 def test_every_program_engages(name, field):
-    recs, summary = P.model_run(name, field, False)
+    recs, summary = P.model_run(name, field)
     steps = P.PROGRAMS[name][1]
     print(name, FIELD_IDS[field], P.figures(recs, summary))
+    releases, has_all = [], False
     assert len(recs) == len(steps) <= 14 and [r["kind"] for r in recs] == [s[0] for s in steps]
     assert steps[-1] == ("frame",) and steps[-2] == ("frame",)
     seen = set()
@@ -87,6 +88,20 @@ def test_every_program_engages(name, field):
             assert o["counts"][0] + o["counts"][1] > 0 and o["counts"][3] == 0, (j, o["counts"])
         elif o["kind"] == "allocate":
             assert o["counts"][0] > 0 and o["counts"][3] == 0, (j, o["counts"])
+        elif o["kind"] == "release":
+            kept, released, nodes_kept, nodes_released, observed = (int(v) for v in o["counts"][:5])
+            assert released > 0, (j, o["counts"])
+            if any(what == "all" for _, _, what in o["rows"]):
+                has_all = True
+                assert observed > 0, (j, o["counts"])
+            if r["kind"] == "staged":                           # the "unseen" release takes blocks the scan had just created with it
+                assert o["fresh_released"] > 0, (j, o["fresh_released"])
+            releases.append((nodes_released, o["info"]["reset_valued"]))
+        elif o["kind"] == "merge_rigid":
+            combined, created, observed, both = (int(v) for v in o["counts"][:4])
+            assert created > 0 and combined > 0 and observed > 0, (j, o["counts"])
+            if o["mode"] != "replace":
+                assert both > 0, (j, o["counts"])
         for kind, changed in r.get("changed_inside", []):
             assert changed > 0, (j, kind)                       # the frame after an operation meets what the operation touched
         if r["image"][0] and (r["kind"] in ("frame", "staged") or r["fused_before"]):
@@ -95,8 +110,29 @@ def test_every_program_engages(name, field):
             assert r["image"][0] == (r["number"] > 2)
     assert seen == P.kinds_of(steps)
     assert summary["truncated"] == 0
-    if name == "pool_churn":
+    if name in ("pool_churn", "pool_churn_release"):
         assert summary["created"] > P.POOL >= summary["peak"], summary
+    # a program that forgets observed content hands nodes back and resets a parent entry that held a value, at least once.  (Under an
+    # "unseen" release alone both depend on what the scans happened to leave empty: a node goes only if all eight entries are initValue()
+    # and everything beneath it is empty, and the entry above an empty block holds a value only if it was written before the block came.)
+    if has_all:
+        assert any(n > 0 for n, _ in releases) and any(v > 0 for _, v in releases), releases
+    _reader_conditions(name, field, recs)
+
+
+def _reader_conditions(name, field, recs):
+    truths = [r["readers"] for r in recs if "readers" in r]
+    if not truths:                                              # the staged programs: every operation stands inside a frame
+        assert all(r["kind"] in ("frame", "staged") for r in recs)
+        return
+    fig = P.reader_figures(truths)
+    print(name, FIELD_IDS[field], "readers", fig)
+    assert fig["project"] == {0, 1, 2}, fig["project"]
+    assert min(fig["field"].values()) > 0, fig["field"]
+    assert min(fig["t_first"].values()) > 0, fig["t_first"]
+    assert fig["oriented"] == {0, 1, 2}, fig["oriented"]
+    assert fig["rays"]["hits"] >= 50 and fig["rays"]["entered_missed"] >= 1, fig["rays"]
+    assert fig["query"]["allocated"] > 0 and fig["query"]["unallocated"] > 0, fig["query"]
 
 
 def test_the_table_holds_every_step_kind_in_every_position():
@@ -104,7 +140,8 @@ def test_the_table_holds_every_step_kind_in_every_position():
     for _, steps in P.PROGRAMS.values():
         kinds |= P.kinds_of(steps)
         staged |= {s[1][0] for s in steps if s[0] == "staged"}
-    assert kinds == set(P.STEP_KINDS) and staged == {"edit", "allocate", "shift", "merge"}
+    assert kinds == set(P.STEP_KINDS) == {"frame", "shift", "merge", "allocate", "edit", "save_load", "staged", "release", "merge_rigid"}
+    assert staged == {"edit", "allocate", "shift", "merge", "release", "merge_rigid"}
     assert all(purpose and "\n" not in purpose for purpose, _ in P.PROGRAMS.values())
 
 
@@ -114,6 +151,37 @@ def test_random_programs_are_stable():
         a, b = P.random_program(seed), P.random_program(seed)
         assert a == b == P.PROGRAMS[name][1] and len(a) <= 14 and a[-2:] == [("frame",), ("frame",)]
     assert P.PROGRAMS["random_a"][1] != P.PROGRAMS["random_b"][1]
+    every = P.OLD_KINDS + ("release", "merge_rigid")
+    for name, seed in P.RANDOM_SEEDS_ALL.items():
+        a, b = P.random_program(seed, every), P.random_program(seed, kinds=every)
+        assert a == b == P.PROGRAMS[name][1] and len(a) <= 14 and a[-2:] == [("frame",), ("frame",)]
+        assert {"release", "merge_rigid"} & P.kinds_of(a)
+    assert P.PROGRAMS["random_c"][1] != P.PROGRAMS["random_d"][1]
+
+
+def _kinds(steps):
+    return [s[0] if s[0] != "staged" else "staged:" + s[1][0] for s in steps]
+
+
+def test_the_programs_of_before_are_the_same():
+    """The step lists of the eight programs that existed before the release and the rigid merge became step kinds: their kinds, literally."""
+    f = "frame"
+    want = {
+        "rolling_submap": [f, f, f, f, "shift", f, f, "merge", f, "edit", "shift", f, f],
+        "declare_free": ["allocate", "edit", f, f, f, f, "edit", "merge", f, "shift", "allocate", "edit", f, f],
+        "merge_first": ["merge", f, "shift", "merge", f, f, f, "save_load", f, f],
+        "pool_churn": [f, f, "allocate", f, "shift", "merge", "allocate", f, "shift", "merge", "allocate", f, f],
+        "staged_edit_allocate": [f, f, f, f, "staged:edit", f, "staged:allocate", f, f],
+        "staged_shift_merge": [f, f, f, f, "staged:shift", f, "staged:merge", f, f],
+        "random_a": [f, f, f, "merge", f, "save_load", f, "allocate", f, "edit", f, f, f],
+        "random_b": [f, f, f, "staged:edit", "allocate", f, "edit", f, "shift", f, f, f],
+    }
+    assert {n: _kinds(P.PROGRAMS[n][1]) for n in want} == want
+    box = [((40, 48, 24), (88, 80, 56), 0)]
+    assert [s for s in P.PROGRAMS["random_a"][1] if s != ("frame",)] == [
+        ("merge", "src64", ("registered", (8, 0, -8)), "fuse"), ("save_load",), ("allocate", box), ("edit", "reset")]
+    assert [s for s in P.PROGRAMS["random_b"][1] if s != ("frame",)] == [
+        ("staged", ("edit", "boxes")), ("allocate", box), ("edit", "boxes"), ("shift", (0, 8, 8))]
 
 
 def test_the_numpy_class_grid_reads_nodes_where_blocks_are_absent():
