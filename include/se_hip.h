@@ -296,7 +296,10 @@ int se_hip_download_track(se_hip_pipeline* p, void* host_trackdata, float host_r
  *      kernels se_denseslam/src/rendering.cpp:111-283).  Output: width*height RGBW bytes (host).
  *      se_hip_render_volume: view_pose = *viewPose_ (re-raycasts with far = 2*farPlane when it is not
  *      approximately raycast_pose_, else shades vertex_/normal_); light = its translation, ambient 0.1;
- *      mu = the constructor's config.mu; returns 1 = rendered, 0 = gated off (frame % rate != 0). */
+ *      mu = the constructor's config.mu; returns 1 = rendered, 0 = gated off (frame % rate != 0).
+ *      Domain: largestep is the step the SDF march takes at a voxel of weight 0 (t += largestep, kfusion/rendering_impl.hpp:47-52), as in
+ *      the reference; it is not checked.  A largestep of 0, or below half an ulp of 2*farPlane (about 5e-7), leaves t where it is: the
+ *      march then never ends, in the reference and in this kernel alike.  Pass a largestep that advances t (the reference's: 0.75 * mu). */
 int se_hip_render_volume(se_hip_pipeline* p, uint8_t* host_rgbw, const float view_pose[16], const float k[4], float mu, float largestep,
                          uint32_t frame, uint32_t raycast_rendering_rate);
 int se_hip_render_depth(se_hip_pipeline* p, uint8_t* host_rgbw);
