@@ -228,6 +228,14 @@ class DenseSLAMSystem {
   bool distanceField(const se_hip_field_request& request, const se_hip_collide_test& test, se_hip_field_out& host_out) {
     return ok(se_hip_distance_field_host(h_, &request, &test, &host_out));
   }
+  /* Not in the reference's class: the reachability field of a region -- for every position v of [lo, lo + side) the number of moves of the
+   * box [v, v + robot) to the nearest usable seed through free positions of the region, that seed, and the first move of a shortest path
+   * -- se_hip_reach_field_host, definitions in se_hip.h.  The arrays of host_out are [side z][side y][side x]; host_out.steps is required, a
+   * null seed / next / counts means "not wanted"; request.seeds and host_out.counts are host pointers.  The answers are those of
+   * se::geometry::reach_field (include/se/reach_field.hpp) on the getMap() snapshot. */
+  bool reachField(const se_hip_reach_request& request, const se_hip_collide_test& test, se_hip_reach_out& host_out) {
+    return ok(se_hip_reach_field_host(h_, &request, &test, &host_out));
+  }
   /* Not in the reference's class: collision queries for n oriented boxes (host_boxes[n][12]: centre xyz, then the half-axes h0, h1, h2 xyz, in
    * sub-units of 1 / SE_HIP_ORIENTED_SUB voxel), exact for the box given -- se_hip_collide_oriented_host, definitions in se_hip.h.
    * host_status[n] receives 0 occupied, 1 unseen, 2 empty, 255 invalid box.  The answers are those of se::geometry::oriented_status

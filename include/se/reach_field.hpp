@@ -1,0 +1,319 @@
+/*
+ * The reachability field of a map region on the host se::Octree snapshot that DenseSLAMSystem::getMap() materialises: the executable
+ * definition of se_hip_reach_field (include/se_hip.h), without Eigen, beside distance_field.hpp.
+ *
+ * Position v of the region [lo, lo + side) is free iff no voxel of the box [v, v + robot) blocks (class <= stop_at; outside the volume is
+ * unseen).  Moves join free positions of the region that differ by one voxel on one axis.  A seed outside the region or at a position that
+ * is not free is ignored.  key(v) = steps(v) * 256 + seed(v): the smallest number of moves to a usable seed, and among the seeds at that
+ * distance the smallest index.  next(v) is the lowest direction code (0 .. 5: -x +x -y +y -z +z) whose neighbour u has key(u) + 256 == key(v).
+ *
+ * Two things are provided:
+ *   reach_field(map, request, test, stop_at, out)        (a) the definition, literally: the box of every position voxel by voxel with
+ *                                                        Octree::get, then a queue BFS on keys.  The queue starts with the usable seed
+ *                                                        positions in the order of their (lowest) index, so it is sorted by key and stays
+ *                                                        so (a pop of key k pushes k + 256): the first key a position receives is its
+ *                                                        smallest.
+ *   reach_field_tiled(map, request, test, stop_at, schedule, out)
+ *                                                        (b) a restatement of the device's scheme (supereight_amd/csrc/se_reach_kernels.h):
+ *                                                        the free bits separably (a window OR per axis over the domain [lo, lo + side +
+ *                                                        robot - 1) classified once); the region cut into tiles; per round every tile whose
+ *                                                        mark of the round's parity is set clears it, loads its keys and a one-cell halo,
+ *                                                        relaxes key = min(key, min over the six neighbours + 256) under the free bit to
+ *                                                        the local fixed point, writes back, and marks -- in the OTHER parity -- the tile
+ *                                                        across every face on which a key decreased; the rounds end with the first one that
+ *                                                        made no mark.  The schedule says in which order the tiles of one round are visited
+ *                                                        (ascending, descending, a seeded shuffle) and whether a halo is read from the keys
+ *                                                        as they are or from the snapshot taken when the round began: between them what
+ *                                                        concurrent workgroups of one launch may observe.
+ * Round bound.  After round r every position with steps <= r - 1 holds its final key.  r = 1: a usable seed holds its final key from the
+ * start.  r -> r + 1: let steps(v) = r and u a neighbour of v with key(u) + 256 == key(v); u holds its final key after round r.  If u lies
+ * in v's tile, that tile ran to its local fixed point in the round that wrote u's final key (or, u a seed, in round 1, for which the seeds'
+ * tiles are marked), and a fixed point with u final has key(v) <= key(u) + 256.  If u lies in another tile, the round r' <= r that wrote
+ * u's final key saw it decrease on the face towards v's tile and marked that tile for round r' + 1 <= r + 1 (u a seed on a face: the tile
+ * across it is marked for round 1); that round loads u's final key -- current or from the snapshot of its beginning, both hold it -- and ends
+ * with key(v) <= key(u) + 256.  Keys never fall below the final ones (every value is the length of a real path), so equality holds.  Hence
+ * every key is final after round max steps + 1, that round or an earlier one makes no mark, and rounds <= max steps + 2.
+ * Both return steps / seed / next [side z][side y][side x] in the layout of the device's outputs and counts = free positions, reached
+ * positions, the largest steps (-1: nothing reached), rounds ((a): 0); an invalid request (reach_valid: the refusals of se_hip_reach_field)
+ * returns false and leaves them empty.  (b) also returns false if its rounds exceed positions + 2, which the bound above excludes.
+ */
+#ifndef SE_HIP_REACH_FIELD_HPP
+#define SE_HIP_REACH_FIELD_HPP
+
+#include <algorithm>
+#include <cstdint>
+#include <random>
+#include <vector>
+
+#include "distance_field.hpp"
+
+namespace se {
+namespace geometry {
+
+constexpr int reach_none = -1;               /* steps of a position that is not free or not connected to a usable seed */
+constexpr int reach_at_seed = 6;             /* next where steps == 0 */
+constexpr int reach_max_seeds = 255;
+constexpr int64_t reach_max_positions = 1 << 24;
+constexpr uint32_t reach_nokey = 0xFFFFFFFFu;
+constexpr int reach_moves[6][3] = {{-1, 0, 0}, {1, 0, 0}, {0, -1, 0}, {0, 1, 0}, {0, 0, -1}, {0, 0, 1}};
+
+struct reach_request {
+  int3 lo, side, robot;
+  std::vector<int3> seeds;   /* absolute voxel coordinates */
+};
+
+struct reach_result {
+  std::vector<int32_t> steps;   /* [side z][side y][side x]; reach_none */
+  std::vector<uint8_t> seed;    /* 255 for none */
+  std::vector<uint8_t> next;    /* 0 .. 5, reach_at_seed, 255 for none */
+  int64_t counts[4] = {0, 0, -1, 0};
+};
+
+enum class reach_order { ascending, descending, shuffled };
+struct reach_schedule {
+  reach_order order = reach_order::ascending;
+  bool stale_halo = false;      /* halos from the snapshot of the round's beginning */
+  uint32_t shuffle_seed = 1;
+  int tile[3] = {32, 8, 8};     /* the device's */
+};
+
+inline bool reach_valid(const reach_request& q) {
+  if (q.seeds.empty() || q.seeds.size() > (size_t)reach_max_seeds) return false;
+  int64_t positions = 1;
+  for (int k = 0; k < 3; ++k) {
+    if (q.side(k) < 1 || q.robot(k) < 1 || q.robot(k) > field_robot_max) return false;
+    const int64_t a = q.lo(k), b = (int64_t)q.lo(k) + q.side(k) + q.robot(k);
+    if (a < -clearance_limit || a > clearance_limit || b < -clearance_limit || b > clearance_limit) return false;
+    positions *= q.side(k);
+  }
+  return positions <= reach_max_positions;
+}
+
+namespace reach_detail {
+struct grid {
+  size_t s0, s1, s2;
+  size_t at(size_t i, size_t j, size_t k) const { return (k * s1 + j) * s0 + i; }
+  size_t count() const { return s0 * s1 * s2; }
+};
+inline grid grid_of(const reach_request& q) { return {(size_t)q.side(0), (size_t)q.side(1), (size_t)q.side(2)}; }
+
+/* the keys of the usable seeds; the rest has none (the seed's offset in 64 bits: any int32 is a valid, if unusable, seed) */
+inline std::vector<uint32_t> seed_keys(const reach_request& q, const std::vector<uint8_t>& free) {
+  const grid g = grid_of(q);
+  std::vector<uint32_t> key(g.count(), reach_nokey);
+  for (size_t n = 0; n < q.seeds.size(); ++n) {
+    int64_t r[3];
+    bool in = true;
+    for (int k = 0; k < 3; ++k) { r[k] = (int64_t)q.seeds[n](k) - q.lo(k); in = in && r[k] >= 0 && r[k] < q.side(k); }
+    if (!in) continue;
+    const size_t at = g.at((size_t)r[0], (size_t)r[1], (size_t)r[2]);
+    if (free[at]) key[at] = std::min(key[at], (uint32_t)n);
+  }
+  return key;
+}
+inline uint32_t step_of(const uint32_t k) { return k < 0xFFFFFF00u ? k + 256u : reach_nokey; }
+/* the key of the neighbour of (i, j, k) in direction d; none across the region's faces */
+inline uint32_t neighbour(const grid& g, const std::vector<uint32_t>& key, size_t i, size_t j, size_t k, int d) {
+  const int64_t x = (int64_t)i + reach_moves[d][0], y = (int64_t)j + reach_moves[d][1], z = (int64_t)k + reach_moves[d][2];
+  if (x < 0 || y < 0 || z < 0 || x >= (int64_t)g.s0 || y >= (int64_t)g.s1 || z >= (int64_t)g.s2) return reach_nokey;
+  return key[g.at((size_t)x, (size_t)y, (size_t)z)];
+}
+/* steps, seed, next and the first three counts from the final keys */
+inline void finish(const reach_request& q, const std::vector<uint8_t>& free, const std::vector<uint32_t>& key, reach_result& out) {
+  const grid g = grid_of(q);
+  out.steps.assign(g.count(), reach_none); out.seed.assign(g.count(), 255); out.next.assign(g.count(), 255);
+  out.counts[0] = out.counts[1] = 0; out.counts[2] = -1;
+  for (size_t k = 0; k < g.s2; ++k)
+    for (size_t j = 0; j < g.s1; ++j)
+      for (size_t i = 0; i < g.s0; ++i) {
+        const size_t at = g.at(i, j, k);
+        out.counts[0] += free[at];
+        if (key[at] == reach_nokey) continue;
+        out.steps[at] = (int32_t)(key[at] >> 8); out.seed[at] = (uint8_t)(key[at] & 255u);
+        ++out.counts[1];
+        out.counts[2] = std::max<int64_t>(out.counts[2], out.steps[at]);
+        out.next[at] = reach_at_seed;
+        if (out.steps[at] > 0)
+          for (int d = 5; d >= 0; --d)
+            if (step_of(neighbour(g, key, i, j, k, d)) == key[at]) out.next[at] = (uint8_t)d;
+      }
+}
+inline void clear(reach_result& out) {
+  out.steps.clear(); out.seed.clear(); out.next.clear();
+  out.counts[0] = out.counts[1] = out.counts[3] = 0; out.counts[2] = -1;
+}
+}  // namespace reach_detail
+
+/* (a) the definition */
+template <typename T, typename TestF>
+bool reach_field(const Octree<T>& map, const reach_request& q, TestF test, const collision_status stop_at, reach_result& out) {
+  using namespace reach_detail;
+  clear(out);
+  if (!reach_valid(q)) return false;
+  const grid g = grid_of(q);
+  std::vector<uint8_t> free(g.count());
+  for (size_t k = 0; k < g.s2; ++k)
+    for (size_t j = 0; j < g.s1; ++j)
+      for (size_t i = 0; i < g.s0; ++i) {
+        bool blocked = false;
+        for (int z = 0; z < q.robot(2) && !blocked; ++z)
+          for (int y = 0; y < q.robot(1) && !blocked; ++y)
+            for (int x = 0; x < q.robot(0) && !blocked; ++x)
+              blocked = field_detail::blocks(map, q.lo(0) + (int)i + x, q.lo(1) + (int)j + y, q.lo(2) + (int)k + z, test, stop_at);
+        free[g.at(i, j, k)] = blocked ? 0 : 1;
+      }
+  std::vector<uint32_t> key = seed_keys(q, free);
+  /* the queue: the seeds' positions by key, then first come first served */
+  std::vector<size_t> queue;
+  for (size_t at = 0; at < key.size(); ++at)
+    if (key[at] != reach_nokey) queue.push_back(at);
+  std::sort(queue.begin(), queue.end(), [&](size_t a, size_t b) { return key[a] < key[b]; });
+  for (size_t head = 0; head < queue.size(); ++head) {
+    const size_t at = queue[head], i = at % g.s0, j = (at / g.s0) % g.s1, k = at / (g.s0 * g.s1);
+    for (int d = 0; d < 6; ++d) {
+      const int64_t x = (int64_t)i + reach_moves[d][0], y = (int64_t)j + reach_moves[d][1], z = (int64_t)k + reach_moves[d][2];
+      if (x < 0 || y < 0 || z < 0 || x >= (int64_t)g.s0 || y >= (int64_t)g.s1 || z >= (int64_t)g.s2) continue;
+      const size_t to = g.at((size_t)x, (size_t)y, (size_t)z);
+      if (!free[to] || key[to] != reach_nokey) continue;
+      key[to] = key[at] + 256u;
+      queue.push_back(to);
+    }
+  }
+  finish(q, free, key, out);
+  return true;
+}
+
+/* (b) the tile scheme */
+template <typename T, typename TestF>
+bool reach_field_tiled(const Octree<T>& map, const reach_request& q, TestF test, const collision_status stop_at, const reach_schedule& sch, reach_result& out) {
+  using namespace reach_detail;
+  clear(out);
+  if (!reach_valid(q) || sch.tile[0] < 1 || sch.tile[1] < 1 || sch.tile[2] < 1) return false;
+  const grid g = grid_of(q);
+  /* the domain, classified once; then a window OR per axis */
+  const size_t D[3] = {g.s0 + (size_t)q.robot(0) - 1, g.s1 + (size_t)q.robot(1) - 1, g.s2 + (size_t)q.robot(2) - 1};
+  std::vector<uint8_t> blk(D[0] * D[1] * D[2]);
+  for (size_t z = 0; z < D[2]; ++z)
+    for (size_t y = 0; y < D[1]; ++y)
+      for (size_t x = 0; x < D[0]; ++x)
+        blk[(z * D[1] + y) * D[0] + x] = field_detail::blocks(map, q.lo(0) + (int)x, q.lo(1) + (int)y, q.lo(2) + (int)z, test, stop_at) ? 1 : 0;
+  std::vector<uint8_t> wx(g.s0 * D[1] * D[2], 0), wy(g.s0 * g.s1 * D[2], 0), free(g.count());
+  for (size_t z = 0; z < D[2]; ++z)
+    for (size_t y = 0; y < D[1]; ++y)
+      for (size_t i = 0; i < g.s0; ++i)
+        for (int s = 0; s < q.robot(0); ++s) wx[(z * D[1] + y) * g.s0 + i] |= blk[(z * D[1] + y) * D[0] + i + (size_t)s];
+  for (size_t z = 0; z < D[2]; ++z)
+    for (size_t j = 0; j < g.s1; ++j)
+      for (size_t i = 0; i < g.s0; ++i)
+        for (int t = 0; t < q.robot(1); ++t) wy[(z * g.s1 + j) * g.s0 + i] |= wx[(z * D[1] + j + (size_t)t) * g.s0 + i];
+  for (size_t k = 0; k < g.s2; ++k)
+    for (size_t j = 0; j < g.s1; ++j)
+      for (size_t i = 0; i < g.s0; ++i) {
+        uint8_t any = 0;
+        for (int t = 0; t < q.robot(2); ++t) any |= wy[((k + (size_t)t) * g.s1 + j) * g.s0 + i];
+        free[g.at(i, j, k)] = any ? 0 : 1;
+      }
+  std::vector<uint32_t> key = seed_keys(q, free);
+  /* tiles and the marks of round 1: a seed's tile and, where the seed lies on a face of it, the tile across that face */
+  const size_t TS[3] = {(size_t)sch.tile[0], (size_t)sch.tile[1], (size_t)sch.tile[2]};
+  const size_t nt[3] = {(g.s0 + TS[0] - 1) / TS[0], (g.s1 + TS[1] - 1) / TS[1], (g.s2 + TS[2] - 1) / TS[2]};
+  const size_t tiles = nt[0] * nt[1] * nt[2];
+  auto tile_at = [&](size_t tx, size_t ty, size_t tz) { return (tz * nt[1] + ty) * nt[0] + tx; };
+  std::vector<uint8_t> dirty[2] = {std::vector<uint8_t>(tiles, 0), std::vector<uint8_t>(tiles, 0)};
+  /* the tile across face f (0 .. 5, the order of reach_moves) of tile (tx, ty, tz), or `tiles` */
+  auto across = [&](size_t tx, size_t ty, size_t tz, int f) {
+    const int64_t c[3] = {(int64_t)tx + reach_moves[f][0], (int64_t)ty + reach_moves[f][1], (int64_t)tz + reach_moves[f][2]};
+    for (int k = 0; k < 3; ++k)
+      if (c[k] < 0 || c[k] >= (int64_t)nt[k]) return tiles;
+    return tile_at((size_t)c[0], (size_t)c[1], (size_t)c[2]);
+  };
+  /* the faces of its tile that cell (i, j, k) lies on, as bits in the order of reach_moves */
+  auto faces_of = [&](size_t i, size_t j, size_t k) {
+    const size_t cx = i % TS[0], cy = j % TS[1], cz = k % TS[2];
+    return (cx == 0 ? 1u : 0u) | (cx == TS[0] - 1 ? 2u : 0u) | (cy == 0 ? 4u : 0u) | (cy == TS[1] - 1 ? 8u : 0u) | (cz == 0 ? 16u : 0u) | (cz == TS[2] - 1 ? 32u : 0u);
+  };
+  for (size_t k = 0; k < g.s2; ++k)
+    for (size_t j = 0; j < g.s1; ++j)
+      for (size_t i = 0; i < g.s0; ++i) {
+        if (key[g.at(i, j, k)] == reach_nokey) continue;
+        const size_t tx = i / TS[0], ty = j / TS[1], tz = k / TS[2];
+        dirty[1][tile_at(tx, ty, tz)] = 1;
+        const unsigned f = faces_of(i, j, k);
+        for (int d = 0; d < 6; ++d)
+          if (((f >> d) & 1u) && across(tx, ty, tz, d) != tiles) dirty[1][across(tx, ty, tz, d)] = 1;
+      }
+  std::mt19937 rng(sch.shuffle_seed);
+  std::vector<size_t> order(tiles);
+  const uint64_t cap = (uint64_t)g.count() + 2;
+  uint64_t rounds = 0;
+  std::vector<uint32_t> snapshot, local, before;
+  for (;;) {
+    if (rounds == cap) { clear(out); return false; }
+    ++rounds;
+    std::vector<uint8_t>& cur = dirty[rounds & 1u];
+    std::vector<uint8_t>& nxt = dirty[(rounds & 1u) ^ 1u];
+    for (size_t t = 0; t < tiles; ++t) order[t] = sch.order == reach_order::descending ? tiles - 1 - t : t;
+    if (sch.order == reach_order::shuffled) std::shuffle(order.begin(), order.end(), rng);
+    if (sch.stale_halo) snapshot = key;
+    const std::vector<uint32_t>& halo = sch.stale_halo ? snapshot : key;
+    uint64_t marks = 0;
+    for (const size_t t : order) {
+      if (!cur[t]) continue;
+      cur[t] = 0;
+      const size_t tx = t % nt[0], ty = (t / nt[0]) % nt[1], tz = t / (nt[0] * nt[1]);
+      const size_t o[3] = {tx * TS[0], ty * TS[1], tz * TS[2]};
+      const size_t e[3] = {std::min(o[0] + TS[0], g.s0), std::min(o[1] + TS[1], g.s1), std::min(o[2] + TS[2], g.s2)};
+      /* the tile with its halo: [e - o + 2] per axis; own cells from the keys, halo cells from `halo`, outside the region none */
+      const size_t L[3] = {e[0] - o[0] + 2, e[1] - o[1] + 2, e[2] - o[2] + 2};
+      auto lat = [&](size_t x, size_t y, size_t z) { return (z * L[1] + y) * L[0] + x; };
+      local.assign(L[0] * L[1] * L[2], reach_nokey);
+      for (size_t z = 0; z < L[2]; ++z)
+        for (size_t y = 0; y < L[1]; ++y)
+          for (size_t x = 0; x < L[0]; ++x) {
+            const int64_t c[3] = {(int64_t)(o[0] + x) - 1, (int64_t)(o[1] + y) - 1, (int64_t)(o[2] + z) - 1};
+            if (c[0] < 0 || c[1] < 0 || c[2] < 0 || c[0] >= (int64_t)g.s0 || c[1] >= (int64_t)g.s1 || c[2] >= (int64_t)g.s2) continue;
+            const bool own = x >= 1 && y >= 1 && z >= 1 && x + 1 < L[0] && y + 1 < L[1] && z + 1 < L[2];
+            local[lat(x, y, z)] = (own ? key : halo)[g.at((size_t)c[0], (size_t)c[1], (size_t)c[2])];
+          }
+      before = local;
+      /* to the local fixed point, all own cells from the keys of the sweep before (as the lanes of a workgroup do between two barriers) */
+      const size_t cells = (e[0] - o[0]) * (e[1] - o[1]) * (e[2] - o[2]);
+      std::vector<uint32_t> prev;
+      for (size_t it = 0; it <= cells; ++it) {
+        prev = local;
+        bool any = false;
+        for (size_t z = 1; z + 1 < L[2]; ++z)
+          for (size_t y = 1; y + 1 < L[1]; ++y)
+            for (size_t x = 1; x + 1 < L[0]; ++x) {
+              if (!free[g.at(o[0] + x - 1, o[1] + y - 1, o[2] + z - 1)]) continue;
+              const uint32_t n = std::min(std::min(std::min(prev[lat(x - 1, y, z)], prev[lat(x + 1, y, z)]), std::min(prev[lat(x, y - 1, z)], prev[lat(x, y + 1, z)])),
+                                          std::min(prev[lat(x, y, z - 1)], prev[lat(x, y, z + 1)]));
+              const uint32_t v = std::min(prev[lat(x, y, z)], step_of(n));
+              if (v != prev[lat(x, y, z)]) { local[lat(x, y, z)] = v; any = true; }
+            }
+        if (!any) break;
+      }
+      /* write back; the faces on which a key decreased */
+      unsigned faces = 0;
+      for (size_t z = 1; z + 1 < L[2]; ++z)
+        for (size_t y = 1; y + 1 < L[1]; ++y)
+          for (size_t x = 1; x + 1 < L[0]; ++x) {
+            if (local[lat(x, y, z)] == before[lat(x, y, z)]) continue;
+            const size_t i = o[0] + x - 1, j = o[1] + y - 1, k = o[2] + z - 1;
+            key[g.at(i, j, k)] = local[lat(x, y, z)];
+            faces |= faces_of(i, j, k);
+          }
+      for (int d = 0; d < 6; ++d)
+        if (((faces >> d) & 1u) && across(tx, ty, tz, d) != tiles) { nxt[across(tx, ty, tz, d)] = 1; ++marks; }
+    }
+    if (marks == 0) break;
+  }
+  finish(q, free, key, out);
+  out.counts[3] = (int64_t)rounds;
+  return true;
+}
+
+}  // namespace geometry
+}  // namespace se
+
+#endif /* SE_HIP_REACH_FIELD_HPP */

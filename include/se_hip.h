@@ -573,6 +573,69 @@ int se_hip_distance_field(se_hip_pipeline* p, const se_hip_field_request* reques
 int se_hip_distance_field_host(se_hip_pipeline* p, const se_hip_field_request* request, const se_hip_collide_test* test,
                                const se_hip_field_out* host_out);
 
+/* ---- the reachability field of a region: "can the robot get from here to there at all, how long is the way, and which way does it go?" --
+ *      a wavefront / NF1 navigation function over the C-space of the box robot that se_hip_distance_field models, in one call, without
+ *      getMap() and a flood fill on the host.  Not in the reference: the definition below is the contract.  Everything is integer.  The
+ *      literal definition and a host restatement of the device's tile scheme are include/se/reach_field.hpp.
+ * Request (se_hip_reach_request, a host struct), in voxels:
+ *   lo, side  the region [lo, lo + side) per axis (x, y, z).
+ *   robot     the side of the box whose min corner stands at a position.
+ *   stop_at   as in se_hip_distance_field.
+ *   n_seeds   1 .. 255.
+ *   seeds     a HOST pointer, in both entries, to [n_seeds][3] int32 (x, y, z; absolute voxel coordinates).
+ * Free positions.  Position v of the region is free iff no voxel of the box [v, v + robot) blocks: iff se_hip_collide_boxes in
+ *   SE_HIP_COLLIDE_STRICT mode answers a status > stop_at for (v, robot).  Classification, "outside the volume is unseen", "a pending index
+ *   entry counts as absent" and the independence of how the tree happens to be subdivided are those of se_hip_collide_boxes.  The region may
+ *   stick out of the volume or lie wholly outside it.
+ * Moves.  From a free position to a free position of the region that differs by one voxel on one axis (6-connectivity).  Positions outside
+ *   the region do not exist: the region's faces are walls.
+ * Seeds.  A seed that lies outside the region, or whose position is not free, is ignored.  Seed coordinates are never refused: a seed
+ *   anywhere in int32 is merely unusable.
+ * Key.  steps(v) is the smallest number of moves from v to a usable seed, seed(v) the smallest seed index among the seeds at that distance,
+ *   key(v) = steps(v) * 256 + seed(v).  key is the unique solution of: key(s_i) <= i for usable seeds, and key(v) = min(own seed index if
+ *   any, min over free neighbours u of key(u) + 256).  Unreached positions have no key.
+ * Outputs (se_hip_reach_out), each [side z][side y][side x]; steps is required, a null pointer for another array means "not wanted":
+ *   steps   (int32) steps(v), or SE_HIP_REACH_NONE for a position that is not free or not connected to a usable seed.
+ *   seed    (uint8) seed(v), or 255.
+ *   next    (uint8) the first move of a shortest path to seed seed(v): the lowest direction code d whose neighbour u has key(u) + 256 ==
+ *           key(v); codes 0 .. 5 are -x, +x, -y, +y, -z, +z; SE_HIP_REACH_AT_SEED where steps == 0; 255 where steps is NONE.  Following
+ *           next from v reaches seed seed[v] after exactly steps[v] moves.
+ *   counts  a HOST int64[4], in both entries: the number of free positions, the number of reached positions, the largest steps (-1 if
+ *           nothing is reached), and the number of relaxation rounds the call ran.  Rounds are informational; rounds <= max steps + 2.
+ * The whole call is refused with SE_HIP_E_INVALID, and then reads no map memory and writes nothing, for: a null request, test, out, steps or
+ * seeds pointer; n_seeds outside 1 .. 255; a side or robot entry < 1; a robot entry > 256; any of lo, lo + side + robot outside
+ * [-2^19, 2^19]; more than 2^24 positions; a stop_at, threshold or occupied_above that se_hip_distance_field refuses.
+ * Work buffers in the handle's staging buffer: one bit per voxel of the block-aligned hull of the domain [lo, lo + side + robot - 1), three
+ * bit arrays of at most that size, 4 bytes per position for the keys, two words per 32 x 8 x 8 tile.
+ * Both entries answer for the map after everything enqueued before them (a scan that ran on the side stream and a held-back raycast
+ * included), report a sticky SE_HIP_E_CAPACITY like the other read-back calls, and leave the map, the images and the launch counters
+ * (SE_HIP_K_*) alone.
+ * NEITHER ENTRY IS ASYNCHRONOUS.  The field is relaxed in rounds, one launch each, and the host decides after every round whether another is
+ * needed: both entries have synchronised the handle's stream when they return.
+ *   se_hip_reach_field       device output arrays (steps, seed, next); counts and seeds stay host pointers.
+ *   se_hip_reach_field_host  host output arrays, staged through the same buffer. */
+#define SE_HIP_REACH_NONE (-1)
+#define SE_HIP_REACH_AT_SEED 6
+#define SE_HIP_REACH_MAX_SEEDS 255
+typedef struct se_hip_reach_request {
+  int32_t lo[3];      /* x, y, z */
+  int32_t side[3];
+  int32_t robot[3];
+  int32_t stop_at;
+  int32_t n_seeds;
+  const int32_t* seeds;  /* host: [n_seeds][3] */
+} se_hip_reach_request;
+typedef struct se_hip_reach_out {
+  int32_t* steps;   /* [side z][side y][side x] */
+  uint8_t* seed;
+  uint8_t* next;
+  int64_t* counts;  /* host: [4] */
+} se_hip_reach_out;
+int se_hip_reach_field(se_hip_pipeline* p, const se_hip_reach_request* request, const se_hip_collide_test* test,
+                       const se_hip_reach_out* device_out);
+int se_hip_reach_field_host(se_hip_pipeline* p, const se_hip_reach_request* request, const se_hip_collide_test* test,
+                            const se_hip_reach_out* host_out);
+
 /* ---- batched collision queries for oriented boxes: "does this robot, at this attitude, touch anything?" for N boxes at once, without
  *      getMap().  Not in the reference; built on its Octree::get and on the classification above.  The host restatement and the literal
  *      definition are include/se/oriented_collision.hpp.

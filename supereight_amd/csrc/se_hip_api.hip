@@ -30,6 +30,7 @@
 #include "se_clearance_kernels.h"
 #include "se_project_kernels.h"
 #include "se_field_kernels.h"
+#include "se_reach_kernels.h"
 #include "se_edit_kernels.h"
 #include "se_alloc_kernels.h"
 #include "se_ray_kernels.h"
@@ -174,6 +175,7 @@ struct se_hip_pipeline {
   // demand (reserve_staging).  One buffer serves them all because no two are ever in use at once: a handle has one caller thread at a time
   // (include/se_hip.h) and every _host entry synchronises the stream before it returns.  A host entry that returned with work in flight would break that.
   DevBuf<> staging;
+  PinnedBuf<unsigned long long> reach_host;   // se_hip_reach_field: pinned, [0 .. 2] the counts, [3] the `changed` word of a round; allocated on first use
   DevBuf<> meshb_dev;   // se_hip_mesh_blocks: view planes [20][64] floats, then the reservation state (3 x uint64); allocated on first use
   bool filter_input = false;   // preprocessing(..., filterInput): tracking sees the bilateral-filtered depth
   bool occ_commit_due = false; // the next sweep kernel must publish the scan's occupancy bits
@@ -2414,6 +2416,136 @@ int se_hip_distance_field_host(se_hip_pipeline* p, const se_hip_field_request* r
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(host_out->d2, a.d2, bytes[2], hipMemcpyDeviceToHost, p->stream));
   if (bytes[3]) HIP_TRY(hipMemcpyAsync(host_out->nearest, a.nearest, bytes[3], hipMemcpyDeviceToHost, p->stream));
+  // (synchronises; a sticky overflow is reported as the other read-back calls report it)
+  return fetch_counters(p);
+}
+
+
+// ------------------------------------------------------------------------------------ reachability field of a region
+static_assert(SE_HIP_REACH_NONE == SE_REACH_NONE && SE_HIP_REACH_AT_SEED == SE_REACH_AT_SEED && SE_HIP_REACH_MAX_SEEDS == SE_REACH_MAX_SEEDS, "codes of se_hip_reach_field");
+namespace {
+int reach_args(const se_hip_reach_request* rq, const se_hip_collide_test* test, const se_hip_reach_out* out) {
+  const std::string who = "se_hip_reach_field: ";
+  if (!rq) return fail(SE_HIP_E_INVALID, who + "null request");
+  if (!out || !out->steps) return fail(SE_HIP_E_INVALID, who + "null out or steps");
+  if (!rq->seeds) return fail(SE_HIP_E_INVALID, who + "null seeds");
+  if (int r = collide_test_args("se_hip_reach_field", test, &rq->stop_at)) return r;
+  if (rq->n_seeds < 1 || rq->n_seeds > SE_REACH_MAX_SEEDS) return fail(SE_HIP_E_INVALID, who + "n_seeds must lie in 1 .. 255");
+  int64_t positions = 1;
+  for (int k = 0; k < 3; ++k) {
+    if (rq->side[k] < 1 || rq->robot[k] < 1 || rq->robot[k] > SE_FIELD_ROBOT) return fail(SE_HIP_E_INVALID, who + "side < 1, or robot outside 1 .. 256");
+    const int64_t a = rq->lo[k], b = (int64_t)rq->lo[k] + rq->side[k] + rq->robot[k];
+    if (a < -SE_FIELD_LIMIT || a > SE_FIELD_LIMIT || b < -SE_FIELD_LIMIT || b > SE_FIELD_LIMIT) return fail(SE_HIP_E_INVALID, who + "lo or lo + side + robot beyond +-2^19");
+    positions *= rq->side[k];   // (each side <= 2^20: the product of three stays inside int64)
+  }
+  if (positions > SE_FIELD_MAX_VOXELS) return fail(SE_HIP_E_INVALID, who + "more than 2^24 positions");
+  return SE_HIP_OK;
+}
+// The launch arguments of a checked request but the buffers, and the bytes of the work buffers in the order staging_layout wants them:
+// 8-byte items (blocking bits, x pass, y pass, free bits, counts), then 4-byte items (keys, marks + the changed word, seeds).
+enum { REACH_BITS, REACH_WX, REACH_WY, REACH_FREE, REACH_COUNTS, REACH_KEY, REACH_DIRTY, REACH_SEEDS, REACH_WORK };
+ReachArgs reach_plan(const se_hip_reach_request* rq, size_t bytes[REACH_WORK]) {
+  ReachArgs a{};
+  for (int k = 0; k < 3; ++k) {
+    a.lo[k] = rq->lo[k]; a.side[k] = rq->side[k]; a.robot[k] = rq->robot[k];
+    a.D[k] = rq->side[k] + rq->robot[k] - 1;
+    a.b0[k] = rq->lo[k] >> 3;   // (>> 3 floors for negative coordinates too)
+    a.nb[k] = ((rq->lo[k] + a.D[k] - 1) >> 3) - a.b0[k] + 1;
+  }
+  a.words = (a.nb[0] + 7) / 8;
+  a.wr = (a.side[0] + 63) / 64;
+  a.nt[0] = (a.side[0] + SE_REACH_TX - 1) / SE_REACH_TX; a.nt[1] = (a.side[1] + SE_REACH_TY - 1) / SE_REACH_TY; a.nt[2] = (a.side[2] + SE_REACH_TZ - 1) / SE_REACH_TZ;
+  a.n_seeds = rq->n_seeds;
+  const size_t wr = (size_t)a.wr, tiles = (size_t)a.nt[0] * (size_t)a.nt[1] * (size_t)a.nt[2];
+  bytes[REACH_BITS] = (size_t)a.nb[2] * 8u * (size_t)a.nb[1] * 8u * (size_t)a.words * sizeof(unsigned long long);
+  bytes[REACH_WX] = (size_t)a.D[2] * (size_t)a.D[1] * wr * sizeof(unsigned long long);
+  bytes[REACH_WY] = (size_t)a.D[2] * (size_t)a.side[1] * wr * sizeof(unsigned long long);
+  bytes[REACH_FREE] = (size_t)a.side[2] * (size_t)a.side[1] * wr * sizeof(unsigned long long);
+  bytes[REACH_COUNTS] = 4 * sizeof(unsigned long long);
+  bytes[REACH_KEY] = (size_t)a.side[2] * (size_t)a.side[1] * (size_t)a.side[0] * sizeof(uint32_t);
+  bytes[REACH_DIRTY] = (2 * tiles + 1) * sizeof(uint32_t);   // (the changed word behind the marks)
+  bytes[REACH_SEEDS] = (size_t)a.n_seeds * 3 * sizeof(int32_t);
+  return a;
+}
+// The whole call but the read-back of the arrays: bits, free bits, seeds, the rounds (one launch each; the host reads the `changed` word behind
+// every launch, as fetch_counters reads the counters, and stops at the first round that made no mark), the finish.  a.steps / seed / next and
+// every work buffer are set; `b` is the staging buffer, `off` its layout.  Synchronises.
+int run_reach(se_hip_pipeline* p, const se_hip_reach_request* rq, const se_hip_collide_test* test, ReachArgs& a, const size_t* bytes, const size_t* off, int64_t* counts) {
+  if (!p->reach_host) { if (int r = p->reach_host.alloc(4, "reach_host")) return r; }
+  unsigned char* b = p->staging;
+  a.bits = (const unsigned long long*)(b + off[REACH_BITS]); a.wx = (unsigned long long*)(b + off[REACH_WX]); a.wy = (unsigned long long*)(b + off[REACH_WY]);
+  a.free = (unsigned long long*)(b + off[REACH_FREE]); a.counts = (unsigned long long*)(b + off[REACH_COUNTS]);
+  a.key = (uint32_t*)(b + off[REACH_KEY]); a.dirty = (uint32_t*)(b + off[REACH_DIRTY]); a.seeds = (const int32_t*)(b + off[REACH_SEEDS]);
+  const size_t tiles = (size_t)a.nt[0] * (size_t)a.nt[1] * (size_t)a.nt[2], positions = (size_t)a.side[0] * (size_t)a.side[1] * (size_t)a.side[2];
+  a.changed = a.dirty + 2 * tiles;
+  auto grid = [](size_t lanes, size_t wg) { return dim3((unsigned)std::min<size_t>((lanes + wg - 1) / wg, (size_t)1 << 20)); };
+  // k_field_classify reads b0, nb, words, bits, thr, above, stop_at only
+  FieldArgs f{};
+  for (int k = 0; k < 3; ++k) { f.b0[k] = a.b0[k]; f.nb[k] = a.nb[k]; }
+  f.words = a.words; f.bits = (unsigned long long*)(b + off[REACH_BITS]);
+  f.thr = test->threshold; f.above = test->occupied_above; f.stop_at = (uint32_t)rq->stop_at;
+  HIP_TRY(hipMemcpyAsync(b + off[REACH_SEEDS], rq->seeds, bytes[REACH_SEEDS], hipMemcpyHostToDevice, p->stream));
+  HIP_TRY(hipMemsetAsync(a.counts, 0, bytes[REACH_COUNTS], p->stream));
+  HIP_TRY(hipMemsetAsync(a.key, 0xFF, bytes[REACH_KEY], p->stream));
+  HIP_TRY(hipMemsetAsync(a.dirty, 0, bytes[REACH_DIRTY], p->stream));
+  const size_t cells = (size_t)a.nb[0] * (size_t)a.nb[1] * (size_t)a.nb[2], wr = (size_t)a.wr;
+  hipLaunchKernelGGL(p->map.dense ? k_field_classify<true> : k_field_classify<false>, grid(cells, 1), dim3(SE_WG_COLLIDE), 0, p->stream, p->map, f);
+  hipLaunchKernelGGL(k_reach_free<0>, grid(wr * (size_t)a.D[1] * (size_t)a.D[2], SE_WG_REACH), dim3(SE_WG_REACH), 0, p->stream, a);
+  hipLaunchKernelGGL(k_reach_free<1>, grid(wr * (size_t)a.side[1] * (size_t)a.D[2], SE_WG_REACH), dim3(SE_WG_REACH), 0, p->stream, a);
+  hipLaunchKernelGGL(k_reach_free<2>, grid(wr * (size_t)a.side[1] * (size_t)a.side[2], SE_WG_REACH), dim3(SE_WG_REACH), 0, p->stream, a);
+  hipLaunchKernelGGL(k_reach_seed, dim3(1), dim3(SE_WG_REACH), 0, p->stream, a);
+  HIP_TRY(hipGetLastError());
+  uint32_t* changed_host = (uint32_t*)(p->reach_host.get() + 3);
+  const uint64_t cap = (uint64_t)positions + 2;
+  uint64_t rounds = 0;
+  uint32_t seen = 0;
+  for (;;) {
+    if (rounds == cap) return fail(SE_HIP_E_DEVICE, "se_hip_reach_field: internal error: the relaxation did not settle within positions + 2 rounds");
+    ++rounds;
+    hipLaunchKernelGGL(k_reach_relax, dim3((unsigned)tiles), dim3(SE_WG_REACH), 0, p->stream, a, (uint32_t)(rounds & 1u));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(changed_host, a.changed, sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (*changed_host == seen) break;   // (the word counts the marks since the call began: a round makes fewer than 2^24, so a wrap cannot hide one)
+    seen = *changed_host;
+  }
+  hipLaunchKernelGGL(k_reach_finish, grid(positions, SE_WG_REACH), dim3(SE_WG_REACH), 0, p->stream, a);
+  HIP_TRY(hipGetLastError());
+  if (counts) {
+    HIP_TRY(hipMemcpyAsync(p->reach_host.get(), a.counts, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    counts[0] = (int64_t)p->reach_host[0]; counts[1] = (int64_t)p->reach_host[1]; counts[2] = (int64_t)p->reach_host[2] - 1; counts[3] = (int64_t)rounds;
+  }
+  return SE_HIP_OK;
+}
+}  // namespace
+
+int se_hip_reach_field(se_hip_pipeline* p, const se_hip_reach_request* request, const se_hip_collide_test* test, const se_hip_reach_out* device_out) {
+  if (int r = query_prologue(p, [&] { return reach_args(request, test, device_out); })) return r;
+  if (int r = check_overflow(p)) return r;
+  size_t bytes[REACH_WORK], off[REACH_WORK];
+  ReachArgs a = reach_plan(request, bytes);
+  if (int r = reserve_staging(p, staging_layout(bytes, REACH_WORK, off))) return r;
+  a.steps = device_out->steps; a.seed = device_out->seed; a.next = device_out->next;
+  if (int r = run_reach(p, request, test, a, bytes, off, device_out->counts)) return r;
+  // (synchronises; a sticky overflow is reported as the other read-back calls report it)
+  return fetch_counters(p);
+}
+
+int se_hip_reach_field_host(se_hip_pipeline* p, const se_hip_reach_request* request, const se_hip_collide_test* test, const se_hip_reach_out* host_out) {
+  if (int r = query_prologue(p, [&] { return reach_args(request, test, host_out); })) return r;
+  // staging = [the work buffers][steps][seed, if asked for][next, if asked for]: 8-byte, then 4-byte items, then bytes
+  size_t bytes[REACH_WORK + 3], off[REACH_WORK + 3];
+  ReachArgs a = reach_plan(request, bytes);
+  const size_t positions = (size_t)a.side[0] * (size_t)a.side[1] * (size_t)a.side[2];
+  bytes[REACH_WORK] = positions * sizeof(int32_t); bytes[REACH_WORK + 1] = host_out->seed ? positions : 0; bytes[REACH_WORK + 2] = host_out->next ? positions : 0;
+  if (int r = reserve_staging(p, staging_layout(bytes, REACH_WORK + 3, off))) return r;
+  unsigned char* b = p->staging;
+  a.steps = (int32_t*)(b + off[REACH_WORK]); a.seed = bytes[REACH_WORK + 1] ? b + off[REACH_WORK + 1] : nullptr; a.next = bytes[REACH_WORK + 2] ? b + off[REACH_WORK + 2] : nullptr;
+  if (int r = run_reach(p, request, test, a, bytes, off, host_out->counts)) return r;
+  HIP_TRY(hipMemcpyAsync(host_out->steps, a.steps, bytes[REACH_WORK], hipMemcpyDeviceToHost, p->stream));
+  if (a.seed) HIP_TRY(hipMemcpyAsync(host_out->seed, a.seed, positions, hipMemcpyDeviceToHost, p->stream));
+  if (a.next) HIP_TRY(hipMemcpyAsync(host_out->next, a.next, positions, hipMemcpyDeviceToHost, p->stream));
   // (synchronises; a sticky overflow is reported as the other read-back calls report it)
   return fetch_counters(p);
 }

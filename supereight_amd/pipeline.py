@@ -124,6 +124,57 @@ class _FieldOut(C.Structure):
 FIELD_LIMIT, FIELD_R_MAX, FIELD_ROBOT_MAX, FIELD_MAX_VOXELS, FIELD_MAX_WORK = 1 << 19, 255, 256, 1 << 24, 1 << 28
 
 
+class _ReachRequest(C.Structure):
+    """se_hip_reach_request of include/se_hip.h (seeds: a host address)."""
+    _fields_ = [("lo", C.c_int32 * 3), ("side", C.c_int32 * 3), ("robot", C.c_int32 * 3), ("stop_at", C.c_int32), ("n_seeds", C.c_int32),
+                ("seeds", C.c_void_p)]
+
+
+class _ReachOut(C.Structure):
+    """se_hip_reach_out of include/se_hip.h: output addresses, 0 = not wanted (steps is required; counts is a host address)."""
+    _fields_ = [("steps", C.c_void_p), ("seed", C.c_void_p), ("next", C.c_void_p), ("counts", C.c_void_p)]
+
+
+# steps / next of se_hip_reach_field for an unreached position and at a seed; the most seeds a request may hold
+REACH_NONE, REACH_AT_SEED, REACH_MAX_SEEDS = -1, 6, 255
+# the moves that next's codes 0 .. 5 name (x, y, z)
+REACH_MOVES = ((-1, 0, 0), (1, 0, 0), (0, -1, 0), (0, 1, 0), (0, 0, -1), (0, 0, 1))
+
+
+def reach_path(next, lo, start) -> np.ndarray:
+    """The path that DenseSLAMPipeline.reach_field's `next` [side z, side y, side x] describes from the position `start` (x, y, z; absolute
+    voxel coordinates, `lo` the region's) to its seed: int64 [steps + 1, 3], `start` first, the seed last.  Empty [0, 3] where next is 255
+    (not free, or cut off from every seed) or `start` lies outside the region.  Pure numpy; bounded by the array's size, so an array that
+    is no navigation function raises ValueError instead of looping."""
+    nx = np.asarray(next)
+    if nx.ndim != 3 or nx.dtype != np.uint8:
+        raise ValueError(f"reach_path: next must be a uint8 array [side z, side y, side x], got {nx.dtype} {list(nx.shape)}")
+    lo = [int(v) for v in np.asarray(lo).reshape(3)]
+    pos = [int(v) for v in np.asarray(start).reshape(3)]
+    side = (nx.shape[2], nx.shape[1], nx.shape[0])
+    path = []
+    for _ in range(nx.size + 1):
+        rel = [pos[k] - lo[k] for k in range(3)]
+        if not all(0 <= rel[k] < side[k] for k in range(3)):
+            if path:
+                raise ValueError("reach_path: next leads out of the region")
+            break
+        code = int(nx[rel[2], rel[1], rel[0]])
+        if code == 255:
+            if path:
+                raise ValueError("reach_path: next leads to a position without a move")
+            break
+        path.append(tuple(pos))
+        if code == REACH_AT_SEED:
+            return np.array(path, np.int64).reshape(-1, 3)
+        if code > 5:
+            raise ValueError(f"reach_path: unknown code {code}")
+        pos = [pos[k] + REACH_MOVES[code][k] for k in range(3)]
+    if path:
+        raise ValueError("reach_path: next does not arrive at a seed")
+    return np.zeros((0, 3), np.int64)
+
+
 # se_hip_collide_oriented: sub-units per voxel, and the bounds of a valid box (|c_k|, |h_ik|, in sub-units)
 ORIENTED_SUB, ORIENTED_CENTRE_LIMIT, ORIENTED_AXIS_LIMIT = 16, 1 << 20, 1 << 14
 
@@ -268,6 +319,8 @@ EXPORTS = {
     "se_hip_project_columns_host": (C.c_int, [C.c_void_p, C.POINTER(_ProjectRequest), C.POINTER(_CollideTest), C.POINTER(_ProjectOut)]),
     "se_hip_distance_field": (C.c_int, [C.c_void_p, C.POINTER(_FieldRequest), C.POINTER(_CollideTest), C.POINTER(_FieldOut)]),
     "se_hip_distance_field_host": (C.c_int, [C.c_void_p, C.POINTER(_FieldRequest), C.POINTER(_CollideTest), C.POINTER(_FieldOut)]),
+    "se_hip_reach_field": (C.c_int, [C.c_void_p, C.POINTER(_ReachRequest), C.POINTER(_CollideTest), C.POINTER(_ReachOut)]),
+    "se_hip_reach_field_host": (C.c_int, [C.c_void_p, C.POINTER(_ReachRequest), C.POINTER(_CollideTest), C.POINTER(_ReachOut)]),
     "se_hip_collide_oriented": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_void_p]),
     "se_hip_collide_oriented_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_void_p]),
     "se_hip_edit_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
@@ -1098,6 +1151,75 @@ class DenseSLAMPipeline:
         out = _FieldOut(d2.data_ptr(), near.data_ptr() if nearest else None)
         self._device_call(torch, dev, self.lib.se_hip_distance_field, C.byref(rq), C.byref(test), C.byref(out))
         return (d2, near) if nearest else d2
+
+    def reach_field(self, lo, side, seeds, robot=(1, 1, 1), stop_at: str = "occupied", threshold: float = 0.0, occupied_above=None,
+                    seed: bool = False, next: bool = False, counts: bool = False, device: bool = False) -> dict:
+        """The reachability field of a map region (se_hip_reach_field, include/se_hip.h): lo, side three integers each, the region
+        [lo, lo + side) in voxels (x, y, z); seeds integers [n, 3], 1 <= n <= 255, absolute voxel positions (x, y, z); robot the side of the
+        box whose min corner stands at a position.  A position is free iff collides() in strict mode answers a status above stop_at for the
+        box there; moves are 6-connected between free positions of the region; a seed outside the region or at a position that is not free
+        is ignored.  Returns a dict: "steps" [side z, side y, side x] int32, the moves to the nearest usable seed or REACH_NONE (-1); with
+        seed, "seed" uint8, the lowest index among the nearest seeds or 255; with next, "next" uint8, the first move of a shortest path to
+        that seed (0 .. 5: -x +x -y +y -z +z, REACH_AT_SEED at a seed, 255 where steps is REACH_NONE; reach_path follows it); with counts,
+        "counts" numpy int64 [4]: free positions, reached positions, the largest steps (-1: nothing reached), relaxation rounds.
+          - device=False: through the host entry; numpy arrays out.
+          - device=True: through the device entry; torch tensors on this handle's GPU out ("counts" stays numpy).
+        Either way the handle is synchronised when the call returns.  A side or robot < 1, a robot > 256, lo or lo + side + robot beyond
+        +-2^19, more than 2^24 positions, no seed or more than 255, a seed coordinate beyond int32 raise ValueError, wrong types TypeError,
+        before any library call."""
+        def ints(name, v, shape=(3,)):
+            a = np.asarray(v)
+            if isinstance(v, (bool, np.bool_)) or a.dtype.kind not in "iu":
+                raise TypeError(f"reach_field: {name} must hold integers, got {a.dtype}")
+            if shape is not None and a.shape != shape:
+                raise ValueError(f"reach_field: {name} must have shape {list(shape)}, got {list(a.shape)}")
+            return a
+
+        if stop_at not in _MOTION_STOPS:
+            raise ValueError(f"reach_field: stop_at must be one of {sorted(_MOTION_STOPS)}, got {stop_at!r}")
+        if occupied_above is None:
+            occupied_above = self.field == OFUSION
+        if not isinstance(occupied_above, (bool, np.bool_)):
+            raise TypeError(f"reach_field: occupied_above must be a bool, got {type(occupied_above).__name__}")
+        thr = float(threshold)
+        if not np.isfinite(np.float32(thr)):
+            raise ValueError(f"reach_field: threshold must be finite as a float32, got {threshold!r}")
+        lo, side, robot = ([int(x) for x in ints(n, v)] for n, v in (("lo", lo), ("side", side), ("robot", robot)))
+        sd = ints("seeds", seeds, None)
+        if sd.ndim != 2 or sd.shape[1] != 3:
+            raise ValueError(f"reach_field: seeds must have shape [n, 3], got {list(sd.shape)}")
+        if not 1 <= sd.shape[0] <= REACH_MAX_SEEDS:
+            raise ValueError(f"reach_field: 1 .. {REACH_MAX_SEEDS} seeds, got {sd.shape[0]}")
+        if sd.min() < -(2 ** 31) or sd.max() > 2 ** 31 - 1:
+            raise ValueError("reach_field: a seed coordinate beyond int32")
+        sd = np.ascontiguousarray(sd, np.int32)
+        if min(side) < 1 or min(robot) < 1 or max(robot) > FIELD_ROBOT_MAX:
+            raise ValueError(f"reach_field: side must be >= 1 and robot in 1 .. {FIELD_ROBOT_MAX}, got {side}, {robot}")
+        if any(abs(v) > FIELD_LIMIT for k in range(3) for v in (lo[k], lo[k] + side[k] + robot[k])):
+            raise ValueError("reach_field: lo and lo + side + robot must lie within +-2^19")
+        if side[0] * side[1] * side[2] > FIELD_MAX_VOXELS:
+            raise ValueError(f"reach_field: {side[0] * side[1] * side[2]} positions, more than 2^24")
+        rq = _ReachRequest()
+        rq.stop_at, rq.n_seeds, rq.seeds = _MOTION_STOPS[stop_at], sd.shape[0], sd.ctypes.data
+        for k in range(3):
+            rq.lo[k], rq.side[k], rq.robot[k] = lo[k], side[k], robot[k]
+        test = _CollideTest(thr, int(bool(occupied_above)))
+        shape = (side[2], side[1], side[0])
+        want = (("steps", True, np.int32), ("seed", seed, np.uint8), ("next", next, np.uint8))
+        cnt = np.zeros(4, np.int64) if counts else None
+        if not device:
+            res = {k: np.empty(shape, dt) for k, w, dt in want if w}
+            out = _ReachOut(*(res[k].ctypes.data if k in res else None for k, _, _ in want), cnt.ctypes.data if counts else None)
+            self._check(self.lib.se_hip_reach_field_host(self._h, C.byref(rq), C.byref(test), C.byref(out)))
+        else:
+            import torch
+            dev = torch.device("cuda", self._device if self._device is not None else torch.cuda.current_device())
+            res = {k: torch.empty(shape, dtype=getattr(torch, np.dtype(dt).name), device=dev) for k, w, dt in want if w}
+            out = _ReachOut(*(res[k].data_ptr() if k in res else None for k, _, _ in want), cnt.ctypes.data if counts else None)
+            self._device_call(torch, dev, self.lib.se_hip_reach_field, C.byref(rq), C.byref(test), C.byref(out))
+        if counts:
+            res["counts"] = cnt
+        return res
 
     @staticmethod
     def _edit_only(only) -> int:
