@@ -51,18 +51,18 @@ struct field_result {
   std::vector<int32_t> nearest;  /* [side z][side y][side x][3]; INT32_MIN three times for none */
 };
 
-inline bool field_valid(const field_request& q) {
-  if (q.r_max < 0 || q.r_max > field_r_max) return false;
+inline bool region_valid(const int3& lo, const int3& side, const int3& robot) {   /* what every request over a region must satisfy */
   int64_t voxels = 1;
   for (int k = 0; k < 3; ++k) {
-    if (q.side(k) < 1 || q.robot(k) < 1 || q.robot(k) > field_robot_max) return false;
-    const int64_t a = q.lo(k), b = (int64_t)q.lo(k) + q.side(k) + q.robot(k);
-    if (a < -clearance_limit || a > clearance_limit || b < -clearance_limit || b > clearance_limit) return false;
-    voxels *= q.side(k);
+    const int64_t a = lo(k), b = (int64_t)lo(k) + side(k) + robot(k);
+    if (side(k) < 1 || robot(k) < 1 || robot(k) > field_robot_max || a < -clearance_limit || b > clearance_limit) return false;   /* (a < b by then) */
+    voxels *= side(k);
   }
-  if (voxels > field_max_voxels) return false;
-  const int64_t d1 = (int64_t)q.side(1) + q.robot(1) + 2 * q.r_max + 1, d2 = (int64_t)q.side(2) + q.robot(2) + 2 * q.r_max + 1;
-  return (int64_t)q.side(0) * d1 * d2 <= field_max_work;
+  return voxels <= field_max_voxels;
+}
+inline bool field_valid(const field_request& q) {
+  const int64_t w = 2 * (int64_t)q.r_max + 1, d1 = w + q.side(1) + q.robot(1), d2 = w + q.side(2) + q.robot(2);
+  return q.r_max >= 0 && q.r_max <= field_r_max && region_valid(q.lo, q.side, q.robot) && q.side(0) * d1 * d2 <= field_max_work;
 }
 
 namespace field_detail {

@@ -53,7 +53,6 @@ namespace geometry {
 constexpr int reach_none = -1;               /* steps of a position that is not free or not connected to a usable seed */
 constexpr int reach_at_seed = 6;             /* next where steps == 0 */
 constexpr int reach_max_seeds = 255;
-constexpr int64_t reach_max_positions = 1 << 24;
 constexpr uint32_t reach_nokey = 0xFFFFFFFFu;
 constexpr int reach_moves[6][3] = {{-1, 0, 0}, {1, 0, 0}, {0, -1, 0}, {0, 1, 0}, {0, 0, -1}, {0, 0, 1}};
 
@@ -78,15 +77,7 @@ struct reach_schedule {
 };
 
 inline bool reach_valid(const reach_request& q) {
-  if (q.seeds.empty() || q.seeds.size() > (size_t)reach_max_seeds) return false;
-  int64_t positions = 1;
-  for (int k = 0; k < 3; ++k) {
-    if (q.side(k) < 1 || q.robot(k) < 1 || q.robot(k) > field_robot_max) return false;
-    const int64_t a = q.lo(k), b = (int64_t)q.lo(k) + q.side(k) + q.robot(k);
-    if (a < -clearance_limit || a > clearance_limit || b < -clearance_limit || b > clearance_limit) return false;
-    positions *= q.side(k);
-  }
-  return positions <= reach_max_positions;
+  return !q.seeds.empty() && q.seeds.size() <= (size_t)reach_max_seeds && region_valid(q.lo, q.side, q.robot);
 }
 
 namespace reach_detail {

@@ -167,6 +167,28 @@ __device__ __forceinline__ uint32_t leaf_index(const DevMap& m, int bx, int by, 
   const int l = m.leaf_level;
   return m.leaf_off + (((((uint32_t)bz << l) | (uint32_t)by) << l) | (uint32_t)bx);
 }
+// Octree::get (octree.hpp:335-355) for a block of the volume that is absent: down from the root while the octant on the block's path exists; the
+// answer is the first missing octant's value_[child] in its parent.  Every allocated octant has all its ancestors, so the walk stops at the first
+// level whose octant is absent (SE_PENDING counts as absent).  Returns the value slot nid * 8 + child of m.nx / m.ny, and in `sh` the missing
+// octant's side: 8 << sh voxels.  Unrolled over the constant bound so that m.off[] is indexed by constants only.
+__device__ __forceinline__ size_t absent_value_slot(const DevMap& m, int bx, int by, int bz, int& sh) {
+  const int leaf = m.leaf_level;
+  uint32_t nid = 0u;   // node 0 = the root
+  int lmiss = leaf;
+  bool down = true;
+#pragma unroll
+  for (int l = 1; l < SE_MAX_LEVELS; ++l) {
+    if (down && l < leaf) {
+      const int s = leaf - l;
+      const uint32_t t = m.tab[tab_index(m, l, bx >> s, by >> s, bz >> s)];
+      if (t != 0u && t != SE_PENDING) nid = t - 1u;
+      else { lmiss = l; down = false; }
+    }
+  }
+  sh = leaf - lmiss;
+  const uint32_t child = ((uint32_t)(bx >> sh) & 1u) | (((uint32_t)(by >> sh) & 1u) << 1) | (((uint32_t)(bz >> sh) & 1u) << 2);
+  return (size_t)nid * 8 + child;
+}
 // Morton code of an octant position (<= 10 bits per axis), x lowest
 __device__ __forceinline__ uint32_t morton30(int x, int y, int z) {
   return (uint32_t)(se_expand21_d((unsigned long long)x) | (se_expand21_d((unsigned long long)y) << 1) | (se_expand21_d((unsigned long long)z) << 2));

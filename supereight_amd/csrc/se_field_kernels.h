@@ -47,30 +47,34 @@
 #define SE_FIELD_NO32 0x80008000u
 #define SE_WG_FIELD 256
 
+// What k_field_classify reads and writes: the block-aligned hull of a domain and the occupancy test.
+struct HullArgs {
+  int b0[3], nb[3];              // the hull in blocks: first block and block count per axis
+  int words;                     // 64-bit words per bit row: ceil(nb[0] / 8)
+  unsigned long long* bits;      // [8 nb[2]][8 nb[1]][words]
+  float thr; int above; uint32_t stop_at;
+};
 struct FieldArgs {
   int lo[3], side[3], robot[3];
   int r_max;
-  int b0[3], nb[3];              // the hull in blocks: first block and block count per axis
-  int words;                     // 64-bit words per bit row: ceil(nb[0] / 8)
   int D[3];                      // the domain's cells per axis
-  unsigned long long* bits;      // [8 nb[2]][8 nb[1]][words]
+  HullArgs hull;
   int16_t* ax;                   // [D[2]][D[1]][side[0]]
   uint32_t* ay;                  // [D[2]][side[1]][side[0]]
   int32_t* d2; int32_t* nearest; // [side[2]][side[1]][side[0]] (nearest: [3] more)
-  float thr; int above; uint32_t stop_at;
 };
 
 // the gap of a candidate at offset o = c - v from a box of side `robot` at v
 __device__ __forceinline__ int se_field_gap(int o, int robot) { return max(max(o - robot, -o - 1), 0); }
 
 template <bool DENSE>
-__global__ __launch_bounds__(SE_WG_COLLIDE) void k_field_classify(DevMap m, FieldArgs a) {
+__global__ __launch_bounds__(SE_WG_COLLIDE) void k_field_classify(DevMap m, HullArgs a) {
   const FieldConst fc = se_field_const(m);
   const uint32_t lane = threadIdx.x & 63u;
   const float thr = a.thr;
   const int above = a.above;
   const uint32_t stop_at = a.stop_at;
-  const int leaf = m.leaf_level, nb = m.size >> 3;
+  const int nb = m.size >> 3;
   const size_t n0 = (size_t)a.nb[0], n1 = (size_t)a.nb[1], cells = n0 * n1 * (size_t)a.nb[2];
   const size_t row_bytes = (size_t)a.words * 8u;
   uint8_t* out = (uint8_t*)a.bits;
@@ -99,22 +103,9 @@ __global__ __launch_bounds__(SE_WG_COLLIDE) void k_field_classify(DevMap m, Fiel
 #pragma unroll
         for (int k = 0; k < 8; ++k) byte |= (se_collide_class(vx[k], vy[k], fc, thr, above) <= stop_at ? 1u : 0u) << k;
       } else {
-        // Octree::get: down from the root while the octant on the path exists (as k_project_columns does)
-        uint32_t nid = 0u;
-        int lmiss = leaf;
-        bool down = true;
-#pragma unroll
-        for (int l = 1; l < SE_MAX_LEVELS; ++l) {
-          if (down && l < leaf) {
-            const int sh = leaf - l;
-            const uint32_t t = m.tab[tab_index(m, l, bx >> sh, by >> sh, bz >> sh)];
-            if (t != 0u && t != SE_PENDING) nid = t - 1u;
-            else { lmiss = l; down = false; }
-          }
-        }
-        const int sh = leaf - lmiss;
-        const uint32_t child = ((uint32_t)(bx >> sh) & 1u) | (((uint32_t)(by >> sh) & 1u) << 1) | (((uint32_t)(bz >> sh) & 1u) << 2);
-        const uint32_t cls = se_collide_class(m.nx[(size_t)nid * 8 + child], m.ny[(size_t)nid * 8 + child], fc, thr, above);
+        int sh;   // Octree::get: the value of the first missing octant on the block's path (absent_value_slot, se_device.h)
+        const size_t vs = absent_value_slot(m, bx, by, bz, sh);
+        const uint32_t cls = se_collide_class(m.nx[vs], m.ny[vs], fc, thr, above);
         byte = cls <= stop_at ? 0xFFu : 0u;
       }
     }
@@ -148,11 +139,11 @@ __global__ __launch_bounds__(SE_WG_FIELD) void k_field_x(FieldArgs a) {
   const size_t s0 = (size_t)a.side[0], d1 = (size_t)a.D[1], total = s0 * d1 * (size_t)a.D[2];
   const int r = a.r_max, robot = a.robot[0];
   // the domain's origin inside the hull, per axis: (lo - 1 - r_max) - 8 b0, in [0, 8)
-  const int hx = a.lo[0] - 1 - r - 8 * a.b0[0], hy = a.lo[1] - 1 - r - 8 * a.b0[1], hz = a.lo[2] - 1 - r - 8 * a.b0[2];
-  const size_t rows_y = (size_t)a.nb[1] * 8u;
+  const int hx = a.lo[0] - 1 - r - 8 * a.hull.b0[0], hy = a.lo[1] - 1 - r - 8 * a.hull.b0[1], hz = a.lo[2] - 1 - r - 8 * a.hull.b0[2];
+  const size_t rows_y = (size_t)a.hull.nb[1] * 8u;
   for (size_t idx = (size_t)blockIdx.x * SE_WG_FIELD + threadIdx.x; idx < total; idx += (size_t)gridDim.x * SE_WG_FIELD) {
     const size_t i = idx % s0, y = (idx / s0) % d1, z = idx / (s0 * d1);
-    const unsigned long long* row = a.bits + ((z + (size_t)hz) * rows_y + (y + (size_t)hy)) * (size_t)a.words;
+    const unsigned long long* row = a.hull.bits + ((z + (size_t)hz) * rows_y + (y + (size_t)hy)) * (size_t)a.hull.words;
     const int pv = hx + 1 + r + (int)i;   // the bit of v_x = lo_x + i
     int c = se_field_lowest(row, pv - 1, pv + robot);
     if (c < 0 && r > 0) {

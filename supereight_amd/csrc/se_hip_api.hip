@@ -551,6 +551,13 @@ template <typename Check> int query_prologue(se_hip_pipeline* p, Check args_ok) 
   if (int r = args_ok()) return r;
   return join_scan(p);
 }
+// What every host form does last: the staged parts asked for (bytes[i] != 0) copied from dev[i] to the caller's host[i], then the counters
+// (synchronises; a sticky overflow is reported as the other read-back calls report it).
+int read_back(se_hip_pipeline* p, int k, void* const* host, void* const* dev, const size_t* bytes) {
+  for (int i = 0; i < k; ++i)
+    if (bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], dev[i], bytes[i], hipMemcpyDeviceToHost, p->stream));
+  return fetch_counters(p);
+}
 // The outputs of an array-in / array-out family (points, boxes, rays, edits): per output the caller's array (null: not asked for) and its bytes per item
 // -- or, per_call, its bytes whatever n is (the edits' counts; the allocations' counts and key list).
 struct BatchOut { void* ptr; size_t item_bytes; bool per_call = false; };
@@ -580,14 +587,11 @@ int batch_host(se_hip_pipeline* p, const void* in, size_t in_item_bytes, int64_t
   if (int r = reserve_staging(p, staging_layout(bytes, out.count + 1, off))) return r;
   unsigned char* b = p->staging;
   HIP_TRY(hipMemcpyAsync(b, in, bytes[0], hipMemcpyHostToDevice, p->stream));
-  void* dev[5];
-  for (int k = 0; k < out.count; ++k) dev[k] = bytes[k + 1] ? b + off[k + 1] : nullptr;
+  void *dev[5], *host[5];
+  for (int k = 0; k < out.count; ++k) { dev[k] = bytes[k + 1] ? b + off[k + 1] : nullptr; host[k] = out.o[k].ptr; }
   launch(b, dev);
   HIP_TRY(hipGetLastError());
-  for (int k = 0; k < out.count; ++k)
-    if (bytes[k + 1]) HIP_TRY(hipMemcpyAsync(out.o[k].ptr, dev[k], bytes[k + 1], hipMemcpyDeviceToHost, p->stream));
-  // (synchronises; a sticky overflow is reported as the other read-back calls report it)
-  return fetch_counters(p);
+  return read_back(p, out.count, host, dev, bytes + 1);
 }
 // The launch of the wave-per-item query kernels (boxes, motions, clearance, oriented boxes): grid-stride beyond 2^20 workgroups, one instantiation per brick layout.
 template <class Args>
@@ -2328,30 +2332,48 @@ int se_hip_project_columns_host(se_hip_pipeline* p, const se_hip_project_request
   for (int k = 0; k < 4; ++k) dev[k] = bytes[k] ? b + off[k] : nullptr;
   launch_project(p, request, test, (uint8_t*)dev[3], (int32_t*)dev[0], (int32_t*)dev[1], (int32_t*)dev[2]);
   HIP_TRY(hipGetLastError());
-  for (int k = 0; k < 4; ++k)
-    if (bytes[k]) HIP_TRY(hipMemcpyAsync(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost, p->stream));
-  // (synchronises; a sticky overflow is reported as the other read-back calls report it)
-  return fetch_counters(p);
+  return read_back(p, 4, host, dev, bytes);
 }
 
 
 // ------------------------------------------------------------------------------------ distance field of a region
 static_assert(SE_HIP_CLEARANCE_NONE == SE_FIELD_NONE, "d2 code of se_hip_distance_field");
 namespace {
+// The region rule of se_hip_distance_field and se_hip_reach_field (se::geometry::region_valid); `noun`: what the region's items are called.
+int region_args(const std::string& who, const int32_t* lo, const int32_t* side, const int32_t* robot, const char* noun) {
+  int64_t items = 1;
+  for (int k = 0; k < 3; ++k) {
+    if (side[k] < 1 || robot[k] < 1 || robot[k] > SE_FIELD_ROBOT) return fail(SE_HIP_E_INVALID, who + "side < 1, or robot outside 1 .. 256");
+    const int64_t a = lo[k], b = (int64_t)lo[k] + side[k] + robot[k];
+    if (a < -SE_FIELD_LIMIT || a > SE_FIELD_LIMIT || b < -SE_FIELD_LIMIT || b > SE_FIELD_LIMIT) return fail(SE_HIP_E_INVALID, who + "lo or lo + side + robot beyond +-2^19");
+    items *= side[k];   // (each side <= 2^20: the product of three stays inside int64)
+  }
+  if (items > SE_FIELD_MAX_VOXELS) return fail(SE_HIP_E_INVALID, who + "more than 2^24 " + noun);
+  return SE_HIP_OK;
+}
+// The block-aligned hull of the domain of D cells per axis from the voxel `first` on, with the occupancy test, but its buffer; returns the bytes
+// of the bit rows.
+size_t hull_plan(HullArgs& h, const int first[3], const int D[3], const se_hip_collide_test* test, int32_t stop_at) {
+  for (int k = 0; k < 3; ++k) {
+    h.b0[k] = first[k] >> 3;   // (>> 3 floors for negative coordinates too)
+    h.nb[k] = ((first[k] + D[k] - 1) >> 3) - h.b0[k] + 1;
+  }
+  h.words = (h.nb[0] + 7) / 8;
+  h.thr = test->threshold; h.above = test->occupied_above; h.stop_at = (uint32_t)stop_at;
+  return (size_t)h.nb[2] * 8u * (size_t)h.nb[1] * 8u * (size_t)h.words * sizeof(unsigned long long);
+}
+// One wave per 8^3 cell of the hull; like every grid below, bounded, and the kernel strides over the rest.
+void launch_classify(se_hip_pipeline* p, const HullArgs& h) {
+  const size_t cells = (size_t)h.nb[0] * (size_t)h.nb[1] * (size_t)h.nb[2];
+  hipLaunchKernelGGL(p->map.dense ? k_field_classify<true> : k_field_classify<false>, dim3(grid_for(cells, 1, 1 << 20)), dim3(SE_WG_COLLIDE), 0, p->stream, p->map, h);
+}
 int field_args(const se_hip_field_request* rq, const se_hip_collide_test* test, const se_hip_field_out* out) {
   const std::string who = "se_hip_distance_field: ";
   if (!rq) return fail(SE_HIP_E_INVALID, who + "null request");
   if (!out || !out->d2) return fail(SE_HIP_E_INVALID, who + "null out or d2");
   if (int r = collide_test_args("se_hip_distance_field", test, &rq->stop_at)) return r;
   if (rq->r_max < 0 || rq->r_max > SE_FIELD_RMAX) return fail(SE_HIP_E_INVALID, who + "r_max must lie in 0 .. 255");
-  int64_t voxels = 1;
-  for (int k = 0; k < 3; ++k) {
-    if (rq->side[k] < 1 || rq->robot[k] < 1 || rq->robot[k] > SE_FIELD_ROBOT) return fail(SE_HIP_E_INVALID, who + "side < 1, or robot outside 1 .. 256");
-    const int64_t a = rq->lo[k], b = (int64_t)rq->lo[k] + rq->side[k] + rq->robot[k];
-    if (a < -SE_FIELD_LIMIT || a > SE_FIELD_LIMIT || b < -SE_FIELD_LIMIT || b > SE_FIELD_LIMIT) return fail(SE_HIP_E_INVALID, who + "lo or lo + side + robot beyond +-2^19");
-    voxels *= rq->side[k];   // (each side <= 2^20: the product of three stays inside int64)
-  }
-  if (voxels > SE_FIELD_MAX_VOXELS) return fail(SE_HIP_E_INVALID, who + "more than 2^24 voxels");
+  if (int r = region_args(who, rq->lo, rq->side, rq->robot, "voxels")) return r;
   const int64_t d1 = (int64_t)rq->side[1] + rq->robot[1] + 2 * rq->r_max + 1, d2 = (int64_t)rq->side[2] + rq->robot[2] + 2 * rq->r_max + 1;
   if ((int64_t)rq->side[0] * d1 * d2 > SE_FIELD_MAX_WORK) return fail(SE_HIP_E_INVALID, who + "side[0] * D1 * D2 beyond 2^28");
   return SE_HIP_OK;
@@ -2361,28 +2383,24 @@ int field_args(const se_hip_field_request* rq, const se_hip_collide_test* test, 
 FieldArgs field_plan(const se_hip_field_request* rq, const se_hip_collide_test* test, size_t bytes[3]) {
   FieldArgs a{};
   a.r_max = rq->r_max;
+  int first[3];
   for (int k = 0; k < 3; ++k) {
     a.lo[k] = rq->lo[k]; a.side[k] = rq->side[k]; a.robot[k] = rq->robot[k];
     a.D[k] = rq->side[k] + rq->robot[k] + 2 * rq->r_max + 1;
-    const int first = rq->lo[k] - 1 - rq->r_max;
-    a.b0[k] = first >> 3;   // (>> 3 floors for negative coordinates too)
-    a.nb[k] = ((first + a.D[k] - 1) >> 3) - a.b0[k] + 1;
+    first[k] = rq->lo[k] - 1 - rq->r_max;
   }
-  a.words = (a.nb[0] + 7) / 8;
-  a.thr = test->threshold; a.above = test->occupied_above; a.stop_at = (uint32_t)rq->stop_at;
-  bytes[0] = (size_t)a.nb[2] * 8u * (size_t)a.nb[1] * 8u * (size_t)a.words * sizeof(unsigned long long);
+  bytes[0] = hull_plan(a.hull, first, a.D, test, rq->stop_at);
   bytes[1] = (size_t)a.D[2] * (size_t)a.side[1] * (size_t)a.side[0] * sizeof(uint32_t);
   bytes[2] = (size_t)a.D[2] * (size_t)a.D[1] * (size_t)a.side[0] * sizeof(int16_t);
   return a;
 }
-// Four plain launches; every grid is bounded and its kernel strides over the rest.
+// Four plain launches.
 void launch_field(se_hip_pipeline* p, const FieldArgs& a) {
-  auto grid = [](size_t lanes, size_t wg) { return dim3((unsigned)std::min<size_t>((lanes + wg - 1) / wg, (size_t)1 << 20)); };
-  const size_t cells = (size_t)a.nb[0] * (size_t)a.nb[1] * (size_t)a.nb[2], s0 = (size_t)a.side[0], s1 = (size_t)a.side[1];
-  hipLaunchKernelGGL(p->map.dense ? k_field_classify<true> : k_field_classify<false>, grid(cells, 1), dim3(SE_WG_COLLIDE), 0, p->stream, p->map, a);
-  hipLaunchKernelGGL(k_field_x, grid(s0 * (size_t)a.D[1] * (size_t)a.D[2], SE_WG_FIELD), dim3(SE_WG_FIELD), 0, p->stream, a);
-  hipLaunchKernelGGL(k_field_y, grid(s0 * s1 * (size_t)a.D[2], SE_WG_FIELD), dim3(SE_WG_FIELD), 0, p->stream, a);
-  hipLaunchKernelGGL(k_field_z, grid(s0 * s1 * (size_t)a.side[2], SE_WG_FIELD), dim3(SE_WG_FIELD), 0, p->stream, a);
+  const size_t s0 = (size_t)a.side[0], s1 = (size_t)a.side[1];
+  launch_classify(p, a.hull);
+  hipLaunchKernelGGL(k_field_x, dim3(grid_for(s0 * (size_t)a.D[1] * (size_t)a.D[2], SE_WG_FIELD, 1 << 20)), dim3(SE_WG_FIELD), 0, p->stream, a);
+  hipLaunchKernelGGL(k_field_y, dim3(grid_for(s0 * s1 * (size_t)a.D[2], SE_WG_FIELD, 1 << 20)), dim3(SE_WG_FIELD), 0, p->stream, a);
+  hipLaunchKernelGGL(k_field_z, dim3(grid_for(s0 * s1 * (size_t)a.side[2], SE_WG_FIELD, 1 << 20)), dim3(SE_WG_FIELD), 0, p->stream, a);
 }
 }  // namespace
 
@@ -2394,7 +2412,7 @@ int se_hip_distance_field(se_hip_pipeline* p, const se_hip_field_request* reques
   FieldArgs a = field_plan(request, test, bytes);
   if (int r = reserve_staging(p, staging_layout(bytes, 3, off))) return r;
   unsigned char* b = p->staging;
-  a.bits = (unsigned long long*)(b + off[0]); a.ay = (uint32_t*)(b + off[1]); a.ax = (int16_t*)(b + off[2]);
+  a.hull.bits = (unsigned long long*)(b + off[0]); a.ay = (uint32_t*)(b + off[1]); a.ax = (int16_t*)(b + off[2]);
   a.d2 = device_out->d2; a.nearest = device_out->nearest;
   launch_field(p, a);
   HIP_TRY(hipGetLastError());
@@ -2410,14 +2428,12 @@ int se_hip_distance_field_host(se_hip_pipeline* p, const se_hip_field_request* r
   bytes[0] = work[0]; bytes[1] = work[1]; bytes[2] = voxels * sizeof(int32_t); bytes[3] = host_out->nearest ? 3 * voxels * sizeof(int32_t) : 0; bytes[4] = work[2];
   if (int r = reserve_staging(p, staging_layout(bytes, 5, off))) return r;
   unsigned char* b = p->staging;
-  a.bits = (unsigned long long*)(b + off[0]); a.ay = (uint32_t*)(b + off[1]); a.ax = (int16_t*)(b + off[4]);
+  a.hull.bits = (unsigned long long*)(b + off[0]); a.ay = (uint32_t*)(b + off[1]); a.ax = (int16_t*)(b + off[4]);
   a.d2 = (int32_t*)(b + off[2]); a.nearest = bytes[3] ? (int32_t*)(b + off[3]) : nullptr;
   launch_field(p, a);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(host_out->d2, a.d2, bytes[2], hipMemcpyDeviceToHost, p->stream));
-  if (bytes[3]) HIP_TRY(hipMemcpyAsync(host_out->nearest, a.nearest, bytes[3], hipMemcpyDeviceToHost, p->stream));
-  // (synchronises; a sticky overflow is reported as the other read-back calls report it)
-  return fetch_counters(p);
+  void* const host[2] = {host_out->d2, host_out->nearest}, * const dev[2] = {a.d2, a.nearest};
+  return read_back(p, 2, host, dev, bytes + 2);
 }
 
 
@@ -2431,33 +2447,22 @@ int reach_args(const se_hip_reach_request* rq, const se_hip_collide_test* test, 
   if (!rq->seeds) return fail(SE_HIP_E_INVALID, who + "null seeds");
   if (int r = collide_test_args("se_hip_reach_field", test, &rq->stop_at)) return r;
   if (rq->n_seeds < 1 || rq->n_seeds > SE_REACH_MAX_SEEDS) return fail(SE_HIP_E_INVALID, who + "n_seeds must lie in 1 .. 255");
-  int64_t positions = 1;
-  for (int k = 0; k < 3; ++k) {
-    if (rq->side[k] < 1 || rq->robot[k] < 1 || rq->robot[k] > SE_FIELD_ROBOT) return fail(SE_HIP_E_INVALID, who + "side < 1, or robot outside 1 .. 256");
-    const int64_t a = rq->lo[k], b = (int64_t)rq->lo[k] + rq->side[k] + rq->robot[k];
-    if (a < -SE_FIELD_LIMIT || a > SE_FIELD_LIMIT || b < -SE_FIELD_LIMIT || b > SE_FIELD_LIMIT) return fail(SE_HIP_E_INVALID, who + "lo or lo + side + robot beyond +-2^19");
-    positions *= rq->side[k];   // (each side <= 2^20: the product of three stays inside int64)
-  }
-  if (positions > SE_FIELD_MAX_VOXELS) return fail(SE_HIP_E_INVALID, who + "more than 2^24 positions");
-  return SE_HIP_OK;
+  return region_args(who, rq->lo, rq->side, rq->robot, "positions");
 }
 // The launch arguments of a checked request but the buffers, and the bytes of the work buffers in the order staging_layout wants them:
 // 8-byte items (blocking bits, x pass, y pass, free bits, counts), then 4-byte items (keys, marks + the changed word, seeds).
 enum { REACH_BITS, REACH_WX, REACH_WY, REACH_FREE, REACH_COUNTS, REACH_KEY, REACH_DIRTY, REACH_SEEDS, REACH_WORK };
-ReachArgs reach_plan(const se_hip_reach_request* rq, size_t bytes[REACH_WORK]) {
+ReachArgs reach_plan(const se_hip_reach_request* rq, const se_hip_collide_test* test, size_t bytes[REACH_WORK]) {
   ReachArgs a{};
   for (int k = 0; k < 3; ++k) {
     a.lo[k] = rq->lo[k]; a.side[k] = rq->side[k]; a.robot[k] = rq->robot[k];
     a.D[k] = rq->side[k] + rq->robot[k] - 1;
-    a.b0[k] = rq->lo[k] >> 3;   // (>> 3 floors for negative coordinates too)
-    a.nb[k] = ((rq->lo[k] + a.D[k] - 1) >> 3) - a.b0[k] + 1;
   }
-  a.words = (a.nb[0] + 7) / 8;
   a.wr = (a.side[0] + 63) / 64;
   a.nt[0] = (a.side[0] + SE_REACH_TX - 1) / SE_REACH_TX; a.nt[1] = (a.side[1] + SE_REACH_TY - 1) / SE_REACH_TY; a.nt[2] = (a.side[2] + SE_REACH_TZ - 1) / SE_REACH_TZ;
   a.n_seeds = rq->n_seeds;
   const size_t wr = (size_t)a.wr, tiles = (size_t)a.nt[0] * (size_t)a.nt[1] * (size_t)a.nt[2];
-  bytes[REACH_BITS] = (size_t)a.nb[2] * 8u * (size_t)a.nb[1] * 8u * (size_t)a.words * sizeof(unsigned long long);
+  bytes[REACH_BITS] = hull_plan(a.hull, a.lo, a.D, test, rq->stop_at);
   bytes[REACH_WX] = (size_t)a.D[2] * (size_t)a.D[1] * wr * sizeof(unsigned long long);
   bytes[REACH_WY] = (size_t)a.D[2] * (size_t)a.side[1] * wr * sizeof(unsigned long long);
   bytes[REACH_FREE] = (size_t)a.side[2] * (size_t)a.side[1] * wr * sizeof(unsigned long long);
@@ -2470,29 +2475,23 @@ ReachArgs reach_plan(const se_hip_reach_request* rq, size_t bytes[REACH_WORK]) {
 // The whole call but the read-back of the arrays: bits, free bits, seeds, the rounds (one launch each; the host reads the `changed` word behind
 // every launch, as fetch_counters reads the counters, and stops at the first round that made no mark), the finish.  a.steps / seed / next and
 // every work buffer are set; `b` is the staging buffer, `off` its layout.  Synchronises.
-int run_reach(se_hip_pipeline* p, const se_hip_reach_request* rq, const se_hip_collide_test* test, ReachArgs& a, const size_t* bytes, const size_t* off, int64_t* counts) {
+int run_reach(se_hip_pipeline* p, const se_hip_reach_request* rq, ReachArgs& a, const size_t* bytes, const size_t* off, int64_t* counts) {
   if (!p->reach_host) { if (int r = p->reach_host.alloc(4, "reach_host")) return r; }
   unsigned char* b = p->staging;
-  a.bits = (const unsigned long long*)(b + off[REACH_BITS]); a.wx = (unsigned long long*)(b + off[REACH_WX]); a.wy = (unsigned long long*)(b + off[REACH_WY]);
+  a.hull.bits = (unsigned long long*)(b + off[REACH_BITS]); a.wx = (unsigned long long*)(b + off[REACH_WX]); a.wy = (unsigned long long*)(b + off[REACH_WY]);
   a.free = (unsigned long long*)(b + off[REACH_FREE]); a.counts = (unsigned long long*)(b + off[REACH_COUNTS]);
   a.key = (uint32_t*)(b + off[REACH_KEY]); a.dirty = (uint32_t*)(b + off[REACH_DIRTY]); a.seeds = (const int32_t*)(b + off[REACH_SEEDS]);
   const size_t tiles = (size_t)a.nt[0] * (size_t)a.nt[1] * (size_t)a.nt[2], positions = (size_t)a.side[0] * (size_t)a.side[1] * (size_t)a.side[2];
   a.changed = a.dirty + 2 * tiles;
-  auto grid = [](size_t lanes, size_t wg) { return dim3((unsigned)std::min<size_t>((lanes + wg - 1) / wg, (size_t)1 << 20)); };
-  // k_field_classify reads b0, nb, words, bits, thr, above, stop_at only
-  FieldArgs f{};
-  for (int k = 0; k < 3; ++k) { f.b0[k] = a.b0[k]; f.nb[k] = a.nb[k]; }
-  f.words = a.words; f.bits = (unsigned long long*)(b + off[REACH_BITS]);
-  f.thr = test->threshold; f.above = test->occupied_above; f.stop_at = (uint32_t)rq->stop_at;
   HIP_TRY(hipMemcpyAsync(b + off[REACH_SEEDS], rq->seeds, bytes[REACH_SEEDS], hipMemcpyHostToDevice, p->stream));
   HIP_TRY(hipMemsetAsync(a.counts, 0, bytes[REACH_COUNTS], p->stream));
   HIP_TRY(hipMemsetAsync(a.key, 0xFF, bytes[REACH_KEY], p->stream));
   HIP_TRY(hipMemsetAsync(a.dirty, 0, bytes[REACH_DIRTY], p->stream));
-  const size_t cells = (size_t)a.nb[0] * (size_t)a.nb[1] * (size_t)a.nb[2], wr = (size_t)a.wr;
-  hipLaunchKernelGGL(p->map.dense ? k_field_classify<true> : k_field_classify<false>, grid(cells, 1), dim3(SE_WG_COLLIDE), 0, p->stream, p->map, f);
-  hipLaunchKernelGGL(k_reach_free<0>, grid(wr * (size_t)a.D[1] * (size_t)a.D[2], SE_WG_REACH), dim3(SE_WG_REACH), 0, p->stream, a);
-  hipLaunchKernelGGL(k_reach_free<1>, grid(wr * (size_t)a.side[1] * (size_t)a.D[2], SE_WG_REACH), dim3(SE_WG_REACH), 0, p->stream, a);
-  hipLaunchKernelGGL(k_reach_free<2>, grid(wr * (size_t)a.side[1] * (size_t)a.side[2], SE_WG_REACH), dim3(SE_WG_REACH), 0, p->stream, a);
+  const size_t wr = (size_t)a.wr;
+  launch_classify(p, a.hull);   // (k_field_classify over the hull of the C-space domain)
+  hipLaunchKernelGGL(k_reach_free<0>, dim3(grid_for(wr * (size_t)a.D[1] * (size_t)a.D[2], SE_WG_REACH, 1 << 20)), dim3(SE_WG_REACH), 0, p->stream, a);
+  hipLaunchKernelGGL(k_reach_free<1>, dim3(grid_for(wr * (size_t)a.side[1] * (size_t)a.D[2], SE_WG_REACH, 1 << 20)), dim3(SE_WG_REACH), 0, p->stream, a);
+  hipLaunchKernelGGL(k_reach_free<2>, dim3(grid_for(wr * (size_t)a.side[1] * (size_t)a.side[2], SE_WG_REACH, 1 << 20)), dim3(SE_WG_REACH), 0, p->stream, a);
   hipLaunchKernelGGL(k_reach_seed, dim3(1), dim3(SE_WG_REACH), 0, p->stream, a);
   HIP_TRY(hipGetLastError());
   uint32_t* changed_host = (uint32_t*)(p->reach_host.get() + 3);
@@ -2509,7 +2508,7 @@ int run_reach(se_hip_pipeline* p, const se_hip_reach_request* rq, const se_hip_c
     if (*changed_host == seen) break;   // (the word counts the marks since the call began: a round makes fewer than 2^24, so a wrap cannot hide one)
     seen = *changed_host;
   }
-  hipLaunchKernelGGL(k_reach_finish, grid(positions, SE_WG_REACH), dim3(SE_WG_REACH), 0, p->stream, a);
+  hipLaunchKernelGGL(k_reach_finish, dim3(grid_for(positions, SE_WG_REACH, 1 << 20)), dim3(SE_WG_REACH), 0, p->stream, a);
   HIP_TRY(hipGetLastError());
   if (counts) {
     HIP_TRY(hipMemcpyAsync(p->reach_host.get(), a.counts, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, p->stream));
@@ -2524,10 +2523,10 @@ int se_hip_reach_field(se_hip_pipeline* p, const se_hip_reach_request* request, 
   if (int r = query_prologue(p, [&] { return reach_args(request, test, device_out); })) return r;
   if (int r = check_overflow(p)) return r;
   size_t bytes[REACH_WORK], off[REACH_WORK];
-  ReachArgs a = reach_plan(request, bytes);
+  ReachArgs a = reach_plan(request, test, bytes);
   if (int r = reserve_staging(p, staging_layout(bytes, REACH_WORK, off))) return r;
   a.steps = device_out->steps; a.seed = device_out->seed; a.next = device_out->next;
-  if (int r = run_reach(p, request, test, a, bytes, off, device_out->counts)) return r;
+  if (int r = run_reach(p, request, a, bytes, off, device_out->counts)) return r;
   // (synchronises; a sticky overflow is reported as the other read-back calls report it)
   return fetch_counters(p);
 }
@@ -2536,18 +2535,15 @@ int se_hip_reach_field_host(se_hip_pipeline* p, const se_hip_reach_request* requ
   if (int r = query_prologue(p, [&] { return reach_args(request, test, host_out); })) return r;
   // staging = [the work buffers][steps][seed, if asked for][next, if asked for]: 8-byte, then 4-byte items, then bytes
   size_t bytes[REACH_WORK + 3], off[REACH_WORK + 3];
-  ReachArgs a = reach_plan(request, bytes);
+  ReachArgs a = reach_plan(request, test, bytes);
   const size_t positions = (size_t)a.side[0] * (size_t)a.side[1] * (size_t)a.side[2];
   bytes[REACH_WORK] = positions * sizeof(int32_t); bytes[REACH_WORK + 1] = host_out->seed ? positions : 0; bytes[REACH_WORK + 2] = host_out->next ? positions : 0;
   if (int r = reserve_staging(p, staging_layout(bytes, REACH_WORK + 3, off))) return r;
   unsigned char* b = p->staging;
   a.steps = (int32_t*)(b + off[REACH_WORK]); a.seed = bytes[REACH_WORK + 1] ? b + off[REACH_WORK + 1] : nullptr; a.next = bytes[REACH_WORK + 2] ? b + off[REACH_WORK + 2] : nullptr;
-  if (int r = run_reach(p, request, test, a, bytes, off, host_out->counts)) return r;
-  HIP_TRY(hipMemcpyAsync(host_out->steps, a.steps, bytes[REACH_WORK], hipMemcpyDeviceToHost, p->stream));
-  if (a.seed) HIP_TRY(hipMemcpyAsync(host_out->seed, a.seed, positions, hipMemcpyDeviceToHost, p->stream));
-  if (a.next) HIP_TRY(hipMemcpyAsync(host_out->next, a.next, positions, hipMemcpyDeviceToHost, p->stream));
-  // (synchronises; a sticky overflow is reported as the other read-back calls report it)
-  return fetch_counters(p);
+  if (int r = run_reach(p, request, a, bytes, off, host_out->counts)) return r;
+  void* const host[3] = {host_out->steps, host_out->seed, host_out->next}, * const dev[3] = {a.steps, a.seed, a.next};
+  return read_back(p, 3, host, dev, bytes + REACH_WORK);
 }
 
 

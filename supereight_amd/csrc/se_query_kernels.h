@@ -43,26 +43,10 @@ __global__ __launch_bounds__(SE_WG_QUERY) void k_query_points(DevMap m, const fl
           fine_x = coarse_x = m.vx[vi];
           fine_y = coarse_y = se_ld_y(m, vi);
         } else if (o.coarse) {
-          // Octree::get (octree.hpp:335-355): descend from the root while the child on the path exists; the first missing child's
-          // value_[childid] in its parent is the answer.  Every allocated octant has all its ancestors, so the walk stops at the first
-          // level l whose octant is absent.  Unrolled over the constant bound so that m.off[] is indexed by constants only.
-          uint32_t nid = 0u;   // node 0 = the root
-          int lmiss = m.leaf_level;
-          bool down = true;
-#pragma unroll
-          for (int l = 1; l < SE_MAX_LEVELS; ++l) {
-            if (down && l < m.leaf_level) {
-              const int sh = m.max_level - l;
-              uint32_t c = m.tab[tab_index(m, l, x >> sh, y >> sh, z >> sh)];
-              c = c == SE_PENDING ? 0u : c;
-              if (c) nid = c - 1u;
-              else { lmiss = l; down = false; }
-            }
-          }
-          const int sh = m.max_level - lmiss;
-          const uint32_t child = ((uint32_t)(x >> sh) & 1u) | (((uint32_t)(y >> sh) & 1u) << 1) | (((uint32_t)(z >> sh) & 1u) << 2);
-          coarse_x = m.nx[(size_t)nid * 8 + child];
-          coarse_y = m.ny[(size_t)nid * 8 + child];
+          int sh;   // Octree::get: the value of the first missing octant on the block's path (absent_value_slot, se_device.h)
+          const size_t vs = absent_value_slot(m, x >> 3, y >> 3, z >> 3, sh);
+          coarse_x = m.nx[vs];
+          coarse_y = m.ny[vs];
         }
       }
       if (o.status) {

@@ -45,11 +45,10 @@
 struct ReachArgs {
   int lo[3], side[3], robot[3];
   int D[3];                        // the C-space domain's cells per axis: side + robot - 1
-  int b0[3], nb[3], words;         // the hull of k_field_classify (FieldArgs)
+  HullArgs hull;                   // the hull of k_field_classify: blocking bits [8 nb[2]][8 nb[1]][words]
   int wr;                          // 64-bit words per row of the region: ceil(side[0] / 64)
   int nt[3];                       // tiles per axis
   int n_seeds;
-  const unsigned long long* bits;  // [8 nb[2]][8 nb[1]][words]   blocking bits
   unsigned long long* wx;          // [D[2]][D[1]][wr]
   unsigned long long* wy;          // [D[2]][side[1]][wr]
   unsigned long long* free;        // [side[2]][side[1]][wr]
@@ -79,9 +78,9 @@ __global__ __launch_bounds__(SE_WG_REACH) void k_reach_free(ReachArgs a) {
     unsigned long long acc = 0ull;
     if (PASS == 0) {
       // the domain's origin inside the hull, per axis: lo - 8 b0, in [0, 8)
-      const int hx = a.lo[0] - 8 * a.b0[0], hy = a.lo[1] - 8 * a.b0[1], hz = a.lo[2] - 8 * a.b0[2];
-      const unsigned long long* row = a.bits + ((z + (size_t)hz) * ((size_t)a.nb[1] * 8u) + (y + (size_t)hy)) * (size_t)a.words;
-      for (int s = 0; s < window; ++s) acc |= se_reach_extract(row, a.words, hx + 64 * (int)w + s);
+      const int hx = a.lo[0] - 8 * a.hull.b0[0], hy = a.lo[1] - 8 * a.hull.b0[1], hz = a.lo[2] - 8 * a.hull.b0[2];
+      const unsigned long long* row = a.hull.bits + ((z + (size_t)hz) * ((size_t)a.hull.nb[1] * 8u) + (y + (size_t)hy)) * (size_t)a.hull.words;
+      for (int s = 0; s < window; ++s) acc |= se_reach_extract(row, a.hull.words, hx + 64 * (int)w + s);
       a.wx[idx] = acc;
     } else if (PASS == 1) {
       const unsigned long long* col = a.wx + (z * (size_t)a.D[1] + y) * wr + w;

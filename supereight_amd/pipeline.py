@@ -826,22 +826,84 @@ class DenseSLAMPipeline:
             raise ValueError(f"{who}: {name} must be on this handle's GPU (cuda:{self._device}), got {a.device}")
         return torch, a, int(a.shape[0])
 
-    @staticmethod
-    def _batch_outputs(torch, like, n, table, want, struct):
-        """The outputs asked for (`want`) of a (name, shape per item, numpy dtype) table as numpy arrays, or as torch tensors on the device
-        of `like`, and the ctypes `struct` of their addresses (NULL where not asked for)."""
-        if torch is None:
-            res = {k: np.empty((n,) + shp, dt) for k, shp, dt in table if want[k]}
-            return res, struct(*(res[k].ctypes.data if k in res else None for k, _, _ in table))
-        res = {k: torch.empty((n,) + shp, dtype=getattr(torch, np.dtype(dt).name), device=like.device) for k, shp, dt in table if want[k]}
-        return res, struct(*(res[k].data_ptr() if k in res else None for k, _, _ in table))
+    def _own_device(self, device: bool):
+        """(torch, this handle's GPU as a torch device) for the entries that take `device=True` instead of a tensor; (None, None) for the host."""
+        if not device:
+            return None, None
+        import torch
+        return torch, torch.device("cuda", self._device if self._device is not None else torch.cuda.current_device())
 
-    def _device_call(self, torch, device, fn, *args):
-        """A device entry on torch tensors: the caller's current torch stream is synchronised first (the inputs must be complete when the
+    @staticmethod
+    def _batch_outputs(torch, device, lead, table, want, struct, *tail):
+        """The outputs asked for (`want`) of a (name, shape per item, numpy dtype) table, each of shape `lead` + its shape per item, as numpy
+        arrays or as torch tensors on `device`, and the ctypes `struct` of their addresses (NULL where not asked for; `tail`: what the struct
+        holds behind them)."""
+        if torch is None:
+            res = {k: np.empty(lead + shp, dt) for k, shp, dt in table if want[k]}
+            return res, struct(*(res[k].ctypes.data if k in res else None for k, _, _ in table), *tail)
+        res = {k: torch.empty(lead + shp, dtype=getattr(torch, np.dtype(dt).name), device=device) for k, shp, dt in table if want[k]}
+        return res, struct(*(res[k].data_ptr() if k in res else None for k, _, _ in table), *tail)
+
+    @staticmethod
+    def _ptr(torch, a, n=1):
+        """The address of a numpy array or a torch tensor for the C ABI; NULL for an empty batch (n == 0) and for None."""
+        if a is None or not n:
+            return None
+        return a.ctypes.data if torch is None else a.data_ptr()
+
+    def _call(self, torch, device, entry, *args):
+        """The host / device fork of every batched entry.  Without torch: `entry`_host on numpy arrays (it synchronises itself).  With torch:
+        `entry` on tensors -- the caller's current torch stream on `device` is synchronised first (the inputs must be complete when the
         handle's stream reads them), and the handle before the outputs are handed back."""
+        if torch is None:
+            self._check(getattr(self.lib, entry + "_host")(self._h, *args))
+            return
         torch.cuda.current_stream(device).synchronize()
-        self._check(fn(self._h, *args))
+        self._check(getattr(self.lib, entry)(self._h, *args))
         self.sync()
+
+    def _occupancy_test(self, who, threshold, occupied_above, records=False) -> _CollideTest:
+        """se_hip_collide_test from threshold / occupied_above: occupied_above None defaults by field (False for SDF, True for OFusion), else
+        it has to be a bool (TypeError); the threshold has to be finite as a float32 (ValueError).  records: the ready-made test of
+        edit_records -- no default, and the threshold is left to the library."""
+        if occupied_above is None and not records:
+            occupied_above = self.field == OFUSION
+        if not isinstance(occupied_above, (bool, np.bool_)):
+            raise TypeError(f"{who}: occupied_above must be a bool, got {type(occupied_above).__name__}")
+        thr = float(threshold)
+        if not records and not np.isfinite(np.float32(thr)):
+            raise ValueError(f"{who}: threshold must be finite as a float32, got {threshold!r}")
+        return _CollideTest(thr, int(bool(occupied_above)))
+
+    @staticmethod
+    def _stop_at(who, stop_at) -> int:
+        """The status code that stop_at names ("occupied" / "unseen"), ValueError for anything else."""
+        if stop_at not in _MOTION_STOPS:
+            raise ValueError(f"{who}: stop_at must be one of {sorted(_MOTION_STOPS)}, got {stop_at!r}")
+        return _MOTION_STOPS[stop_at]
+
+    @staticmethod
+    def _ints(who, name, v, shape=None) -> np.ndarray:
+        """`v` as an array that must hold integers (a bool is refused: TypeError) and, where given, have `shape` (ValueError)."""
+        a = np.asarray(v)
+        if isinstance(v, (bool, np.bool_)) or a.dtype.kind not in "iu":
+            raise TypeError(f"{who}: {name} must hold integers, got {a.dtype}")
+        if shape is not None and a.shape != tuple(shape):
+            raise ValueError(f"{who}: {name} must have shape {list(shape)}, got {list(a.shape)}")
+        return a
+
+    @staticmethod
+    def _region(who, lo, side, robot, noun, r_max=None):
+        """The region rule of distance_field and reach_field on three Python ints each: side >= 1, robot in 1 .. 256, r_max (where the entry
+        has one) in 0 .. 255, lo and lo + side + robot within +-2^19, at most 2^24 `noun`; ValueError otherwise."""
+        if min(side) < 1 or min(robot) < 1 or max(robot) > FIELD_ROBOT_MAX:
+            raise ValueError(f"{who}: side must be >= 1 and robot in 1 .. {FIELD_ROBOT_MAX}, got {side}, {robot}")
+        if r_max is not None and not 0 <= r_max <= FIELD_R_MAX:
+            raise ValueError(f"{who}: r_max must lie in 0 .. {FIELD_R_MAX}, got {r_max}")
+        if any(abs(v) > FIELD_LIMIT for k in range(3) for v in (lo[k], lo[k] + side[k] + robot[k])):
+            raise ValueError(f"{who}: lo and lo + side + robot must lie within +-2^19")
+        if side[0] * side[1] * side[2] > FIELD_MAX_VOXELS:
+            raise ValueError(f"{who}: {side[0] * side[1] * side[2]} {noun}, more than 2^24")
 
     # (shape of each output per point, dtype)
     _QUERY_OUTPUTS = (("fine", (2,), np.float32), ("coarse", (2,), np.float32), ("interp", (), np.float32), ("grad", (3,), np.float32),
@@ -861,11 +923,9 @@ class DenseSLAMPipeline:
         if not any(want.values()):
             raise ValueError("query: no output requested")
         torch, pts, n = self._batch_input("query", "points", points, np.float32, 3)
-        res, out = self._batch_outputs(torch, pts, n, self._QUERY_OUTPUTS, want, _QueryOut)
-        if torch is None:
-            self._check(self.lib.se_hip_query_points_host(self._h, pts.ctypes.data if n else None, n, C.byref(out)))
-        else:
-            self._device_call(torch, pts.device, self.lib.se_hip_query_points, pts.data_ptr() if n else None, n, C.byref(out))
+        dev = pts.device if torch else None
+        res, out = self._batch_outputs(torch, dev, (n,), self._QUERY_OUTPUTS, want, _QueryOut)
+        self._call(torch, dev, "se_hip_query_points", self._ptr(torch, pts, n), n, C.byref(out))
         return res
 
     def collides(self, boxes, threshold: float = 0.0, occupied_above=None, mode: str = "strict"):
@@ -880,23 +940,11 @@ class DenseSLAMPipeline:
         Anything else raises TypeError / ValueError before any library call."""
         if mode not in _COLLIDE_MODES:
             raise ValueError(f"collides: mode must be one of {sorted(_COLLIDE_MODES)}, got {mode!r}")
-        if occupied_above is None:
-            occupied_above = self.field == OFUSION
-        if not isinstance(occupied_above, (bool, np.bool_)):
-            raise TypeError(f"collides: occupied_above must be a bool, got {type(occupied_above).__name__}")
-        thr = float(threshold)
-        if not np.isfinite(np.float32(thr)):
-            raise ValueError(f"collides: threshold must be finite as a float32, got {threshold!r}")
-        test = _CollideTest(thr, int(bool(occupied_above)))
-        m = _COLLIDE_MODES[mode]
+        test = self._occupancy_test("collides", threshold, occupied_above)
         torch, b, n = self._batch_input("collides", "boxes", boxes, np.int32, 6)
-        out = np.empty(n, np.uint8) if torch is None else torch.empty(n, dtype=torch.uint8, device=b.device)
-        if torch is None:
-            self._check(self.lib.se_hip_collide_boxes_host(self._h, b.ctypes.data if n else None, n, C.byref(test), m,
-                                                           out.ctypes.data if n else None))
-        else:
-            self._device_call(torch, b.device, self.lib.se_hip_collide_boxes, b.data_ptr() if n else None, n, C.byref(test), m,
-                              out.data_ptr() if n else None)
+        dev = b.device if torch else None
+        out = np.empty(n, np.uint8) if torch is None else torch.empty(n, dtype=torch.uint8, device=dev)
+        self._call(torch, dev, "se_hip_collide_boxes", self._ptr(torch, b, n), n, C.byref(test), _COLLIDE_MODES[mode], self._ptr(torch, out, n))
         return out
 
     _MOTION_OUTPUTS = (("status", (), np.uint8), ("t_first", (), np.float32))
@@ -913,23 +961,12 @@ class DenseSLAMPipeline:
           - a torch int32 tensor on this handle's GPU (contiguous, [N, 9]): through the device entry; torch tensors on the same device out.
             The caller's current torch stream is synchronised first, and the handle before the tensors are returned.
         Anything else raises TypeError / ValueError before any library call."""
-        if stop_at not in _MOTION_STOPS:
-            raise ValueError(f"collides_moving: stop_at must be one of {sorted(_MOTION_STOPS)}, got {stop_at!r}")
-        if occupied_above is None:
-            occupied_above = self.field == OFUSION
-        if not isinstance(occupied_above, (bool, np.bool_)):
-            raise TypeError(f"collides_moving: occupied_above must be a bool, got {type(occupied_above).__name__}")
-        thr = float(threshold)
-        if not np.isfinite(np.float32(thr)):
-            raise ValueError(f"collides_moving: threshold must be finite as a float32, got {threshold!r}")
-        test = _CollideTest(thr, int(bool(occupied_above)))
+        stop = self._stop_at("collides_moving", stop_at)
+        test = self._occupancy_test("collides_moving", threshold, occupied_above)
         torch, mo, n = self._batch_input("collides_moving", "motions", motions, np.int32, 9)
-        res, out = self._batch_outputs(torch, mo, n, self._MOTION_OUTPUTS, {"status": True, "t_first": bool(t_first)}, _MotionOut)
-        if torch is None:
-            self._check(self.lib.se_hip_collide_motions_host(self._h, mo.ctypes.data if n else None, n, C.byref(test), _MOTION_STOPS[stop_at], C.byref(out)))
-        else:
-            self._device_call(torch, mo.device, self.lib.se_hip_collide_motions, mo.data_ptr() if n else None, n, C.byref(test), _MOTION_STOPS[stop_at],
-                              C.byref(out))
+        dev = mo.device if torch else None
+        res, out = self._batch_outputs(torch, dev, (n,), self._MOTION_OUTPUTS, {"status": True, "t_first": bool(t_first)}, _MotionOut)
+        self._call(torch, dev, "se_hip_collide_motions", self._ptr(torch, mo, n), n, C.byref(test), stop, C.byref(out))
         return (res["status"], res["t_first"]) if t_first else res["status"]
 
     def collides_oriented(self, boxes, threshold: float = 0.0, occupied_above=None):
@@ -943,21 +980,11 @@ class DenseSLAMPipeline:
           - a torch int32 tensor on this handle's GPU (contiguous, [N, 12]): through the device entry; a torch uint8 tensor on the same
             device out.  The caller's current torch stream is synchronised first, and the handle before the tensor is returned.
         Anything else raises TypeError / ValueError before any library call."""
-        if occupied_above is None:
-            occupied_above = self.field == OFUSION
-        if not isinstance(occupied_above, (bool, np.bool_)):
-            raise TypeError(f"collides_oriented: occupied_above must be a bool, got {type(occupied_above).__name__}")
-        thr = float(threshold)
-        if not np.isfinite(np.float32(thr)):
-            raise ValueError(f"collides_oriented: threshold must be finite as a float32, got {threshold!r}")
-        test = _CollideTest(thr, int(bool(occupied_above)))
+        test = self._occupancy_test("collides_oriented", threshold, occupied_above)
         torch, b, n = self._batch_input("collides_oriented", "boxes", boxes, np.int32, 12)
-        out = np.empty(n, np.uint8) if torch is None else torch.empty(n, dtype=torch.uint8, device=b.device)
-        if torch is None:
-            self._check(self.lib.se_hip_collide_oriented_host(self._h, b.ctypes.data if n else None, n, C.byref(test), out.ctypes.data if n else None))
-        else:
-            self._device_call(torch, b.device, self.lib.se_hip_collide_oriented, b.data_ptr() if n else None, n, C.byref(test),
-                              out.data_ptr() if n else None)
+        dev = b.device if torch else None
+        out = np.empty(n, np.uint8) if torch is None else torch.empty(n, dtype=torch.uint8, device=dev)
+        self._call(torch, dev, "se_hip_collide_oriented", self._ptr(torch, b, n), n, C.byref(test), self._ptr(torch, out, n))
         return out
 
     _CLEARANCE_OUTPUTS = (("d2", (), np.int32), ("nearest", (3,), np.int32))
@@ -974,18 +1001,9 @@ class DenseSLAMPipeline:
           - a torch int32 tensor on this handle's GPU (contiguous, [N, 6]): through the device entry; torch tensors on the same device out.
             The caller's current torch stream is synchronised first, and the handle before the tensors are returned.
         Anything else raises TypeError / ValueError before any library call."""
-        if stop_at not in _MOTION_STOPS:
-            raise ValueError(f"clearance: stop_at must be one of {sorted(_MOTION_STOPS)}, got {stop_at!r}")
-        if occupied_above is None:
-            occupied_above = self.field == OFUSION
-        if not isinstance(occupied_above, (bool, np.bool_)):
-            raise TypeError(f"clearance: occupied_above must be a bool, got {type(occupied_above).__name__}")
-        thr = float(threshold)
-        if not np.isfinite(np.float32(thr)):
-            raise ValueError(f"clearance: threshold must be finite as a float32, got {threshold!r}")
-        test = _CollideTest(thr, int(bool(occupied_above)))
+        stop = self._stop_at("clearance", stop_at)
+        test = self._occupancy_test("clearance", threshold, occupied_above)
         torch, b, n = self._batch_input("clearance", "boxes", boxes, np.int32, 6)
-        i32 = np.iinfo(np.int32)
         if torch is not None and _torch_module(r_max) is not None:
             if r_max.dtype not in (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64):
                 raise TypeError(f"clearance: r_max must be an integer or an integer array, got {r_max.dtype}")
@@ -1005,15 +1023,12 @@ class DenseSLAMPipeline:
                 q = np.ascontiguousarray(np.concatenate([b, r.reshape(n, 1)], 1))
             else:
                 q = torch.cat([b, torch.from_numpy(r.copy()).to(b.device).reshape(n, 1)], 1).contiguous()
-        res, out = self._batch_outputs(torch, q, n, self._CLEARANCE_OUTPUTS, {"d2": True, "nearest": bool(nearest)}, _ClearanceOut)
-        if torch is None:
-            self._check(self.lib.se_hip_clearance_boxes_host(self._h, q.ctypes.data if n else None, n, C.byref(test), _MOTION_STOPS[stop_at], C.byref(out)))
-        else:
-            self._device_call(torch, q.device, self.lib.se_hip_clearance_boxes, q.data_ptr() if n else None, n, C.byref(test), _MOTION_STOPS[stop_at],
-                              C.byref(out))
+        dev = q.device if torch else None
+        res, out = self._batch_outputs(torch, dev, (n,), self._CLEARANCE_OUTPUTS, {"d2": True, "nearest": bool(nearest)}, _ClearanceOut)
+        self._call(torch, dev, "se_hip_clearance_boxes", self._ptr(torch, q, n), n, C.byref(test), stop, C.byref(out))
         return (res["d2"], res["nearest"]) if nearest else res["d2"]
 
-    _PROJECT_OUTPUTS = (("status", np.uint8), ("first", np.int32), ("last", np.int32), ("count", np.int32))
+    _PROJECT_OUTPUTS = (("status", (), np.uint8), ("first", (), np.int32), ("last", (), np.int32), ("count", (), np.int32))
 
     def project(self, axis, lo, side, layers, stop_at: str = "occupied", threshold: float = 0.0, occupied_above=None, first: bool = True,
                 last: bool = True, count: bool = True, device: bool = False) -> dict:
@@ -1030,34 +1045,19 @@ class DenseSLAMPipeline:
           - device=True: through the device entry; torch tensors on this handle's GPU out, the handle synchronised before they are returned.
         A side < 1, an empty layer, a coordinate beyond +-2^20, more than 16 layers or more than 2^28 cells raise ValueError, wrong types
         TypeError, before any library call."""
-        def ints(name, v, k):
-            a = np.asarray(v)
-            if isinstance(v, (bool, np.bool_)) or a.dtype.kind not in "iu":
-                raise TypeError(f"project: {name} must hold integers, got {a.dtype}")
-            if a.shape != k:
-                raise ValueError(f"project: {name} must have shape {list(k)}, got {list(a.shape)}")
-            return a.astype(np.int64)
-
         if isinstance(axis, (bool, np.bool_)) or not isinstance(axis, (int, np.integer)):
             raise TypeError(f"project: axis must be an int, got {type(axis).__name__}")
         if axis not in (0, 1, 2):
             raise ValueError(f"project: axis must be 0, 1 or 2, got {axis}")
-        if stop_at not in _MOTION_STOPS:
-            raise ValueError(f"project: stop_at must be one of {sorted(_MOTION_STOPS)}, got {stop_at!r}")
-        if occupied_above is None:
-            occupied_above = self.field == OFUSION
-        if not isinstance(occupied_above, (bool, np.bool_)):
-            raise TypeError(f"project: occupied_above must be a bool, got {type(occupied_above).__name__}")
-        thr = float(threshold)
-        if not np.isfinite(np.float32(thr)):
-            raise ValueError(f"project: threshold must be finite as a float32, got {threshold!r}")
-        lo, side = ints("lo", lo, (2,)), ints("side", side, (2,))
+        stop = self._stop_at("project", stop_at)
+        test = self._occupancy_test("project", threshold, occupied_above)
+        lo, side = (self._ints("project", nm, v, (2,)).astype(np.int64) for nm, v in (("lo", lo), ("side", side)))
         if isinstance(layers, (bool, np.bool_)) or layers is None:
             raise TypeError(f"project: layers must be pairs of integers, got {type(layers).__name__}")
         lay = np.asarray(layers)
         if lay.ndim != 2 or lay.shape[1] != 2 or not 1 <= lay.shape[0] <= PROJECT_MAX_LAYERS:
             raise ValueError(f"project: layers must have shape [L, 2] with L in 1 .. {PROJECT_MAX_LAYERS}, got {list(lay.shape)}")
-        lay = ints("layers", lay, lay.shape)
+        lay = self._ints("project", "layers", lay).astype(np.int64)
         if (side < 1).any():
             raise ValueError(f"project: side must be >= 1, got {side.tolist()}")
         if (lay[:, 0] >= lay[:, 1]).any():
@@ -1068,25 +1068,18 @@ class DenseSLAMPipeline:
         if cells > PROJECT_MAX_CELLS:
             raise ValueError(f"project: {cells} cells, more than 2^28")
         rq = _ProjectRequest()
-        rq.axis, rq.n_layers, rq.stop_at = int(axis), n_l, _MOTION_STOPS[stop_at]
+        rq.axis, rq.n_layers, rq.stop_at = int(axis), n_l, stop
         for k in range(2):
             rq.lo[k], rq.side[k] = int(lo[k]), int(side[k])
         for l in range(n_l):
             rq.layers[l][0], rq.layers[l][1] = int(lay[l, 0]), int(lay[l, 1])
-        test = _CollideTest(thr, int(bool(occupied_above)))
         want = {"status": True, "first": bool(first), "last": bool(last), "count": bool(count)}
-        shape = (n_l, int(side[1]), int(side[0]))
-        if not device:
-            res = {k: np.empty(shape, dt) for k, dt in self._PROJECT_OUTPUTS if want[k]}
-            out = _ProjectOut(*(res[k].ctypes.data if k in res else None for k, _ in self._PROJECT_OUTPUTS))
-            self._check(self.lib.se_hip_project_columns_host(self._h, C.byref(rq), C.byref(test), C.byref(out)))
-            return res
-        import torch
-        dev = torch.device("cuda", self._device if self._device is not None else torch.cuda.current_device())
-        res = {k: torch.empty(shape, dtype=getattr(torch, np.dtype(dt).name), device=dev) for k, dt in self._PROJECT_OUTPUTS if want[k]}
-        out = _ProjectOut(*(res[k].data_ptr() if k in res else None for k, _ in self._PROJECT_OUTPUTS))
-        self._device_call(torch, dev, self.lib.se_hip_project_columns, C.byref(rq), C.byref(test), C.byref(out))
+        torch, dev = self._own_device(device)
+        res, out = self._batch_outputs(torch, dev, (n_l, int(side[1]), int(side[0])), self._PROJECT_OUTPUTS, want, _ProjectOut)
+        self._call(torch, dev, "se_hip_project_columns", C.byref(rq), C.byref(test), C.byref(out))
         return res
+
+    _FIELD_OUTPUTS = _CLEARANCE_OUTPUTS     # (the same two arrays, per voxel of the region)
 
     def distance_field(self, lo, side, r_max, robot=(1, 1, 1), stop_at: str = "occupied", threshold: float = 0.0, occupied_above=None,
                        nearest: bool = False, device: bool = False):
@@ -1101,56 +1094,26 @@ class DenseSLAMPipeline:
           - device=True: through the device entry; torch tensors on this handle's GPU out, the handle synchronised before they are returned.
         A side or robot < 1, a robot > 256, r_max outside 0 .. 255, lo or lo + side + robot beyond +-2^19, more than 2^24 voxels or
         side[0] * D1 * D2 > 2^28 (D_k = side[k] + robot[k] + 2 r_max + 1) raise ValueError, wrong types TypeError, before any library call."""
-        def ints(name, v):
-            a = np.asarray(v)
-            if isinstance(v, (bool, np.bool_)) or a.dtype.kind not in "iu":
-                raise TypeError(f"distance_field: {name} must hold integers, got {a.dtype}")
-            if a.shape != (3,):
-                raise ValueError(f"distance_field: {name} must have shape [3], got {list(a.shape)}")
-            return [int(x) for x in a]
-
-        if stop_at not in _MOTION_STOPS:
-            raise ValueError(f"distance_field: stop_at must be one of {sorted(_MOTION_STOPS)}, got {stop_at!r}")
-        if occupied_above is None:
-            occupied_above = self.field == OFUSION
-        if not isinstance(occupied_above, (bool, np.bool_)):
-            raise TypeError(f"distance_field: occupied_above must be a bool, got {type(occupied_above).__name__}")
-        thr = float(threshold)
-        if not np.isfinite(np.float32(thr)):
-            raise ValueError(f"distance_field: threshold must be finite as a float32, got {threshold!r}")
+        stop = self._stop_at("distance_field", stop_at)
+        test = self._occupancy_test("distance_field", threshold, occupied_above)
         if isinstance(r_max, (bool, np.bool_)) or not isinstance(r_max, (int, np.integer)):
             raise TypeError(f"distance_field: r_max must be an int, got {type(r_max).__name__}")
-        lo, side, robot, r = ints("lo", lo), ints("side", side), ints("robot", robot), int(r_max)
-        if min(side) < 1 or min(robot) < 1 or max(robot) > FIELD_ROBOT_MAX:
-            raise ValueError(f"distance_field: side must be >= 1 and robot in 1 .. {FIELD_ROBOT_MAX}, got {side}, {robot}")
-        if not 0 <= r <= FIELD_R_MAX:
-            raise ValueError(f"distance_field: r_max must lie in 0 .. {FIELD_R_MAX}, got {r}")
-        if any(abs(v) > FIELD_LIMIT for k in range(3) for v in (lo[k], lo[k] + side[k] + robot[k])):
-            raise ValueError("distance_field: lo and lo + side + robot must lie within +-2^19")
-        if side[0] * side[1] * side[2] > FIELD_MAX_VOXELS:
-            raise ValueError(f"distance_field: {side[0] * side[1] * side[2]} voxels, more than 2^24")
+        lo, side, robot = ([int(x) for x in self._ints("distance_field", nm, v, (3,))] for nm, v in (("lo", lo), ("side", side), ("robot", robot)))
+        r = int(r_max)
+        self._region("distance_field", lo, side, robot, "voxels", r)
         work = side[0] * (side[1] + robot[1] + 2 * r + 1) * (side[2] + robot[2] + 2 * r + 1)
         if work > FIELD_MAX_WORK:
             raise ValueError(f"distance_field: side[0] * D1 * D2 = {work}, more than 2^28")
         rq = _FieldRequest()
-        rq.r_max, rq.stop_at = r, _MOTION_STOPS[stop_at]
+        rq.r_max, rq.stop_at = r, stop
         for k in range(3):
             rq.lo[k], rq.side[k], rq.robot[k] = lo[k], side[k], robot[k]
-        test = _CollideTest(thr, int(bool(occupied_above)))
-        shape = (side[2], side[1], side[0])
-        if not device:
-            d2 = np.empty(shape, np.int32)
-            near = np.empty(shape + (3,), np.int32) if nearest else None
-            out = _FieldOut(d2.ctypes.data, near.ctypes.data if nearest else None)
-            self._check(self.lib.se_hip_distance_field_host(self._h, C.byref(rq), C.byref(test), C.byref(out)))
-            return (d2, near) if nearest else d2
-        import torch
-        dev = torch.device("cuda", self._device if self._device is not None else torch.cuda.current_device())
-        d2 = torch.empty(shape, dtype=torch.int32, device=dev)
-        near = torch.empty(shape + (3,), dtype=torch.int32, device=dev) if nearest else None
-        out = _FieldOut(d2.data_ptr(), near.data_ptr() if nearest else None)
-        self._device_call(torch, dev, self.lib.se_hip_distance_field, C.byref(rq), C.byref(test), C.byref(out))
-        return (d2, near) if nearest else d2
+        torch, dev = self._own_device(device)
+        res, out = self._batch_outputs(torch, dev, (side[2], side[1], side[0]), self._FIELD_OUTPUTS, {"d2": True, "nearest": bool(nearest)}, _FieldOut)
+        self._call(torch, dev, "se_hip_distance_field", C.byref(rq), C.byref(test), C.byref(out))
+        return (res["d2"], res["nearest"]) if nearest else res["d2"]
+
+    _REACH_OUTPUTS = (("steps", (), np.int32), ("seed", (), np.uint8), ("next", (), np.uint8))
 
     def reach_field(self, lo, side, seeds, robot=(1, 1, 1), stop_at: str = "occupied", threshold: float = 0.0, occupied_above=None,
                     seed: bool = False, next: bool = False, counts: bool = False, device: bool = False) -> dict:
@@ -1167,25 +1130,10 @@ class DenseSLAMPipeline:
         Either way the handle is synchronised when the call returns.  A side or robot < 1, a robot > 256, lo or lo + side + robot beyond
         +-2^19, more than 2^24 positions, no seed or more than 255, a seed coordinate beyond int32 raise ValueError, wrong types TypeError,
         before any library call."""
-        def ints(name, v, shape=(3,)):
-            a = np.asarray(v)
-            if isinstance(v, (bool, np.bool_)) or a.dtype.kind not in "iu":
-                raise TypeError(f"reach_field: {name} must hold integers, got {a.dtype}")
-            if shape is not None and a.shape != shape:
-                raise ValueError(f"reach_field: {name} must have shape {list(shape)}, got {list(a.shape)}")
-            return a
-
-        if stop_at not in _MOTION_STOPS:
-            raise ValueError(f"reach_field: stop_at must be one of {sorted(_MOTION_STOPS)}, got {stop_at!r}")
-        if occupied_above is None:
-            occupied_above = self.field == OFUSION
-        if not isinstance(occupied_above, (bool, np.bool_)):
-            raise TypeError(f"reach_field: occupied_above must be a bool, got {type(occupied_above).__name__}")
-        thr = float(threshold)
-        if not np.isfinite(np.float32(thr)):
-            raise ValueError(f"reach_field: threshold must be finite as a float32, got {threshold!r}")
-        lo, side, robot = ([int(x) for x in ints(n, v)] for n, v in (("lo", lo), ("side", side), ("robot", robot)))
-        sd = ints("seeds", seeds, None)
+        stop = self._stop_at("reach_field", stop_at)
+        test = self._occupancy_test("reach_field", threshold, occupied_above)
+        lo, side, robot = ([int(x) for x in self._ints("reach_field", nm, v, (3,))] for nm, v in (("lo", lo), ("side", side), ("robot", robot)))
+        sd = self._ints("reach_field", "seeds", seeds)
         if sd.ndim != 2 or sd.shape[1] != 3:
             raise ValueError(f"reach_field: seeds must have shape [n, 3], got {list(sd.shape)}")
         if not 1 <= sd.shape[0] <= REACH_MAX_SEEDS:
@@ -1193,30 +1141,16 @@ class DenseSLAMPipeline:
         if sd.min() < -(2 ** 31) or sd.max() > 2 ** 31 - 1:
             raise ValueError("reach_field: a seed coordinate beyond int32")
         sd = np.ascontiguousarray(sd, np.int32)
-        if min(side) < 1 or min(robot) < 1 or max(robot) > FIELD_ROBOT_MAX:
-            raise ValueError(f"reach_field: side must be >= 1 and robot in 1 .. {FIELD_ROBOT_MAX}, got {side}, {robot}")
-        if any(abs(v) > FIELD_LIMIT for k in range(3) for v in (lo[k], lo[k] + side[k] + robot[k])):
-            raise ValueError("reach_field: lo and lo + side + robot must lie within +-2^19")
-        if side[0] * side[1] * side[2] > FIELD_MAX_VOXELS:
-            raise ValueError(f"reach_field: {side[0] * side[1] * side[2]} positions, more than 2^24")
+        self._region("reach_field", lo, side, robot, "positions")
         rq = _ReachRequest()
-        rq.stop_at, rq.n_seeds, rq.seeds = _MOTION_STOPS[stop_at], sd.shape[0], sd.ctypes.data
+        rq.stop_at, rq.n_seeds, rq.seeds = stop, sd.shape[0], sd.ctypes.data
         for k in range(3):
             rq.lo[k], rq.side[k], rq.robot[k] = lo[k], side[k], robot[k]
-        test = _CollideTest(thr, int(bool(occupied_above)))
-        shape = (side[2], side[1], side[0])
-        want = (("steps", True, np.int32), ("seed", seed, np.uint8), ("next", next, np.uint8))
         cnt = np.zeros(4, np.int64) if counts else None
-        if not device:
-            res = {k: np.empty(shape, dt) for k, w, dt in want if w}
-            out = _ReachOut(*(res[k].ctypes.data if k in res else None for k, _, _ in want), cnt.ctypes.data if counts else None)
-            self._check(self.lib.se_hip_reach_field_host(self._h, C.byref(rq), C.byref(test), C.byref(out)))
-        else:
-            import torch
-            dev = torch.device("cuda", self._device if self._device is not None else torch.cuda.current_device())
-            res = {k: torch.empty(shape, dtype=getattr(torch, np.dtype(dt).name), device=dev) for k, w, dt in want if w}
-            out = _ReachOut(*(res[k].data_ptr() if k in res else None for k, _, _ in want), cnt.ctypes.data if counts else None)
-            self._device_call(torch, dev, self.lib.se_hip_reach_field, C.byref(rq), C.byref(test), C.byref(out))
+        torch, dev = self._own_device(device)
+        res, out = self._batch_outputs(torch, dev, (side[2], side[1], side[0]), self._REACH_OUTPUTS, {"steps": True, "seed": seed, "next": next}, _ReachOut,
+                                       self._ptr(None, cnt))
+        self._call(torch, dev, "se_hip_reach_field", C.byref(rq), C.byref(test), C.byref(out))
         if counts:
             res["counts"] = cnt
         return res
@@ -1251,22 +1185,18 @@ class DenseSLAMPipeline:
         ctest = None
         if test is not None:
             thr, above = test
-            if not isinstance(above, (bool, np.bool_)):
-                raise TypeError(f"edit: occupied_above must be a bool, got {type(above).__name__}")
-            ctest = C.byref(_CollideTest(float(thr), int(bool(above))))
-        m = _EDIT_MODES[mode]
+            ctest = C.byref(self._occupancy_test("edit", thr, above, records=True))
         if type(records) is np.ndarray and records.dtype == EDIT_DTYPE:
             if records.ndim != 1:
                 raise ValueError(f"edit: records must have shape [N], got {list(records.shape)}")
-            rec, n = np.ascontiguousarray(records), records.shape[0]
+            torch, rec, n = None, np.ascontiguousarray(records), records.shape[0]
             out = np.zeros(4, np.int64) if counts else None
-            self._check(self.lib.se_hip_edit_boxes_host(self._h, rec.ctypes.data if n else None, n, ctest, m, out.ctypes.data if counts else None))
-            return out
-        torch, rec, n = self._batch_input("edit", "records", records, np.int32, 10)
-        if torch is None:
-            raise TypeError("edit: records must be a numpy array of EDIT_DTYPE or a torch int32 [N, 10] tensor on the GPU")
-        out = torch.zeros(4, dtype=torch.int64, device=rec.device) if counts else None
-        self._device_call(torch, rec.device, self.lib.se_hip_edit_boxes, rec.data_ptr() if n else None, n, ctest, m, out.data_ptr() if counts else None)
+        else:
+            torch, rec, n = self._batch_input("edit", "records", records, np.int32, 10)
+            if torch is None:
+                raise TypeError("edit: records must be a numpy array of EDIT_DTYPE or a torch int32 [N, 10] tensor on the GPU")
+            out = torch.zeros(4, dtype=torch.int64, device=rec.device) if counts else None
+        self._call(torch, rec.device if torch else None, "se_hip_edit_boxes", self._ptr(torch, rec, n), n, ctest, _EDIT_MODES[mode], self._ptr(torch, out))
         return out
 
     def edit(self, boxes, x=None, y=None, *, only="any", threshold: float = 0.0, occupied_above=None, mode: str = "strict", blocks: bool = True,
@@ -1287,13 +1217,7 @@ class DenseSLAMPipeline:
         if mode not in _EDIT_MODES:
             raise ValueError(f"edit: mode must be one of {sorted(_EDIT_MODES)}, got {mode!r}")
         bits = self._edit_only(only)
-        if occupied_above is None:
-            occupied_above = self.field == OFUSION
-        if not isinstance(occupied_above, (bool, np.bool_)):
-            raise TypeError(f"edit: occupied_above must be a bool, got {type(occupied_above).__name__}")
-        thr = float(threshold)
-        if not np.isfinite(np.float32(thr)):
-            raise ValueError(f"edit: threshold must be finite as a float32, got {threshold!r}")
+        test = self._occupancy_test("edit", threshold, occupied_above)
         for nm, v in (("blocks", blocks), ("nodes", nodes)):
             if not isinstance(v, (bool, np.bool_)):
                 raise TypeError(f"edit: {nm} must be a bool, got {type(v).__name__}")
@@ -1322,7 +1246,7 @@ class DenseSLAMPipeline:
             for j, v in enumerate(vals):
                 fl[:, j] = v if _torch_module(v) is not None else torch.as_tensor(v).to(b.device)
             rec[:, 8], rec[:, 9] = flags, bits
-        return self.edit_records(rec, test=(thr, bool(occupied_above)), mode=mode, counts=counts)
+        return self.edit_records(rec, test=(test.threshold, bool(test.occupied_above)), mode=mode, counts=counts)
 
     def init_value(self):
         """initValue() of the handle's field type as (x, y): what a voxel holds before anything is fused into it."""
@@ -1347,19 +1271,17 @@ class DenseSLAMPipeline:
         if type(records) is np.ndarray and records.dtype == ALLOC_DTYPE:
             if records.ndim != 1:
                 raise ValueError(f"allocate: records must have shape [N], got {list(records.shape)}")
-            rec, n = np.ascontiguousarray(records), records.shape[0]
+            torch, rec, n = None, np.ascontiguousarray(records), records.shape[0]
             out = np.zeros(4, np.int64) if counts else None
             keys = np.zeros(words, np.uint64) if words else None
-            self._check(self.lib.se_hip_allocate_boxes_host(self._h, rec.ctypes.data if n else None, n, out.ctypes.data if counts else None,
-                                                            keys.ctypes.data if words else None, words))
-            return out, keys
-        torch, rec, n = self._batch_input("allocate", "records", records, np.int32, 8)
-        if torch is None:
-            raise TypeError("allocate: records must be a numpy array of ALLOC_DTYPE or a torch int32 [N, 8] tensor on the GPU")
-        out = torch.zeros(4, dtype=torch.int64, device=rec.device) if counts else None
-        keys = torch.zeros(words, dtype=torch.int64, device=rec.device) if words else None      # (torch has no uint64 arithmetic: the bits)
-        self._device_call(torch, rec.device, self.lib.se_hip_allocate_boxes, rec.data_ptr() if n else None, n, out.data_ptr() if counts else None,
-                          keys.data_ptr() if words else None, words)
+        else:
+            torch, rec, n = self._batch_input("allocate", "records", records, np.int32, 8)
+            if torch is None:
+                raise TypeError("allocate: records must be a numpy array of ALLOC_DTYPE or a torch int32 [N, 8] tensor on the GPU")
+            out = torch.zeros(4, dtype=torch.int64, device=rec.device) if counts else None
+            keys = torch.zeros(words, dtype=torch.int64, device=rec.device) if words else None      # (torch has no uint64 arithmetic: the bits)
+        self._call(torch, rec.device if torch else None, "se_hip_allocate_boxes", self._ptr(torch, rec, n), n, self._ptr(torch, out), self._ptr(torch, keys),
+                   words)
         return out, keys
 
     def allocate(self, boxes, level=0, return_keys: bool = False):
@@ -1452,11 +1374,9 @@ class DenseSLAMPipeline:
             if v.ndim != 0 and tuple(v.shape) != (n,):
                 raise ValueError(f"cast_rays: {name} must be a scalar or have shape [{n}], got {list(v.shape)}")
             rays[:, j] = v.astype(np.float32) if torch is None else v.to(device=origins.device, dtype=torch.float32)
-        res, out = self._batch_outputs(torch, rays, n, self._RAY_OUTPUTS, want, _RayOut)
-        if torch is None:
-            self._check(self.lib.se_hip_cast_rays_host(self._h, rays.ctypes.data if n else None, n, mu, C.byref(out)))
-        else:
-            self._device_call(torch, rays.device, self.lib.se_hip_cast_rays, rays.data_ptr() if n else None, n, mu, C.byref(out))
+        dev = rays.device if torch else None
+        res, out = self._batch_outputs(torch, dev, (n,), self._RAY_OUTPUTS, want, _RayOut)
+        self._call(torch, dev, "se_hip_cast_rays", self._ptr(torch, rays, n), n, mu, C.byref(out))
         return res
 
     def _mesh_select(self, region, views, skip_empty):
