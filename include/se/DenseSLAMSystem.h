@@ -253,6 +253,26 @@ class DenseSLAMSystem {
     for (int i = 0; i < 3; ++i)
       for (int k = 0; k < 3; ++k) out[3 + 3 * i + k] = (int32_t)std::nearbyint((double)box_to_world(k, i) * half_extents_m(i) * scale);
   }
+  /* Not in the reference's class: exact segment traces for n segments (host_segments[n][6]: a xyz, b xyz in sub-units of
+   * 1 / SE_HIP_ORIENTED_SUB voxel) -- the min class on the way to the first blocking voxel, its entry parameter, the voxel, and the unseen /
+   * empty voxels before it -- se_hip_trace_segments_host, definitions in se_hip.h.  host_out.status is required; a null pointer for another
+   * array means "not wanted".  stop_at is SE_HIP_COLLISION_OCCUPIED or SE_HIP_COLLISION_UNSEEN.  The answers are those of
+   * se::geometry::trace_walk (include/se/segment_trace.hpp) on the getMap() snapshot. */
+  bool traceSegments(const int32_t* host_segments, size_t n, const se_hip_collide_test& test, int32_t stop_at, se_hip_trace_out& host_out) {
+    return ok(se_hip_trace_segments_host(h_, host_segments, (int64_t)n, &test, stop_at, &host_out));
+  }
+  /* The six int32 of one such segment from metric endpoints: each coordinate x * 16 * size / dim is rounded to the nearest ODD sub-unit,
+   * 2 rint((x - 1) / 2) + 1, so that an endpoint never lies on a voxel boundary and an axis-parallel segment never in a grid plane (where it
+   * would touch nothing).  The trace is exact for the rounded segment; an endpoint moves by at most sqrt(3) / 16 voxel.  Values beyond int32
+   * are clamped to it (such a segment is invalid anyway). */
+  void segmentOf(const Eigen::Vector3f& a_m, const Eigen::Vector3f& b_m, int32_t out[6]) const {
+    const double scale = (double)SE_HIP_ORIENTED_SUB * volume_resolution_.x() / volume_dimension_.x();
+    for (int k = 0; k < 6; ++k) {
+      const double x = (double)(k < 3 ? a_m(k) : b_m(k - 3)) * scale;
+      const double odd = 2.0 * std::nearbyint((x - 1.0) / 2.0) + 1.0;
+      out[k] = (int32_t)std::min(std::max(odd, -2147483647.0), 2147483647.0);
+    }
+  }
   /* Not in the reference's class (an addition of this mirror): se::functor::axis_aligned_map(map, f, min, max) for a list of n boxes with
    * f = "assign x and / or y where the current value has one of these classes", applied to the device map in list order without save / load --
    * se_hip_edit_boxes_host, definitions in se_hip.h.  The map afterwards is what se::apply_edits (include/se/axis_aligned.hpp) makes of the

@@ -675,6 +675,57 @@ int se_hip_reach_field_host(se_hip_pipeline* p, const se_hip_reach_request* requ
 int se_hip_collide_oriented(se_hip_pipeline* p, const int32_t* device_boxes, int64_t n, const se_hip_collide_test* test, uint8_t* device_status);
 int se_hip_collide_oriented_host(se_hip_pipeline* p, const int32_t* host_boxes, int64_t n, const se_hip_collide_test* test, uint8_t* host_status);
 
+/* ---- exact segment traces: "is there a free line of sight from A to B, and if not, which voxel is in the way?" and "how much unseen space
+ *      would a sensor at this pose look into?" for N segments at once, without getMap().  The motion query for a point, in traversal order,
+ *      with class counts: the occupancy-reader counterpart of se_hip_cast_rays, which marches the float field through allocated blocks only
+ *      and does not know the three classes.  Not in the reference; built on its Octree::get and on the classification above.  The host
+ *      restatement and the literal definition are include/se/segment_trace.hpp.
+ * Units: SE_HIP_ORIENTED_SUB = 16 sub-units per voxel, the same as the oriented boxes.
+ * Segment: six int32, a xyz, b xyz in sub-units (segments [n][6]).  Let d = b - a and P(t) = a + t d for t in [0, 1].
+ * Touched: a cube with integer corner c and side s (a voxel: s = 1) is touched iff some t in [0, 1] has, on every axis k,
+ *     16 c_k < a_k + t d_k < 16 (c_k + s).
+ *   This is se_hip_collide_motions' rule for a box of side 0, in sub-units; the inequalities are open.  An axis with d_k = 0 gives a static
+ *   condition, every other axis an open interval with rational ends over |d_k|; with L the largest lower end and U the smallest upper end the
+ *   cube is touched iff L < U, L < 1 and U > 0, and a touched voxel's entry parameter is t_in = max(0, L).
+ *   - A segment that has d_k = 0 and a_k = 0 (mod 16) on some axis lies in a grid plane: it touches nothing, and that is a valid answer.
+ *   - A segment through a voxel edge or corner passes diagonally: the voxels that share only that edge or corner are not touched.
+ *   - The touched voxels of one segment have pairwise distinct t_in, so the order by t_in is the order of traversal.
+ *   Every comparison is exact (cross-multiplication in int64): nothing depends on a step or a rounding.
+ * Classification: exactly that of se_hip_collide_boxes in strict mode -- `test` applied to Octree::get(v) (the voxel, or value_[child] of the
+ *   deepest existing node; a pending index entry counts as absent); every voxel outside [0, size)^3 is unseen.  With stop_at in
+ *   {SE_HIP_COLLISION_OCCUPIED, SE_HIP_COLLISION_UNSEEN}, a voxel blocks when its class is <= stop_at, as in se_hip_collide_motions.
+ * A segment with any coordinate of a or b outside [-2^22, 2^22] (SE_HIP_SEGMENT_LIMIT) is invalid and reads no map memory.  (The bound keeps
+ *   every numerator and denominator at or below 2^23 -- exactly representable as floats --, every cross product below 2^47 and every position
+ *   numerator a_j den + num d_j below 2^47: everything fits int64.)
+ * Outputs (se_hip_trace_out; status is required, a null pointer for another array means "not wanted"):
+ *   status[n]     (uint8) the min class over the touched voxels up to and including the first blocking voxel -- over all touched voxels when
+ *                 nothing blocks; SE_HIP_COLLISION_EMPTY when nothing is touched; SE_HIP_COLLISION_INVALID for an invalid segment.
+ *   t_first[n]    (float) t_in of the first blocking voxel in traversal order, voxels outside the volume included, returned as
+ *                 (float)num / (float)den of the exact rational, as in se_hip_collide_motions; SE_HIP_MOTION_FREE (2.0f) when nothing blocks,
+ *                 -1.0f for an invalid segment.
+ *   first[n][3]   (int32, x y z) that voxel; three times INT32_MIN when nothing blocks or the segment is invalid.
+ *   counts[n][2]  (int32) the number of unseen voxels and of empty voxels among the touched voxels inside the volume that precede the first
+ *                 blocking voxel -- all touched voxels inside the volume when nothing blocks; (-1, -1) for an invalid segment.  Voxels outside
+ *                 the volume are never counted (there is nothing to learn there); they do block under stop_at unseen.  With stop_at occupied,
+ *                 counts[.][0] is the information gain of the ray; with stop_at unseen it is 0 and counts[.][1] is the free run.
+ * Both entries answer for the map after everything enqueued before them (a scan that ran on the side stream included), refuse n < 0, a null
+ * out, a null segments or status pointer with n > 0, a null test, a non-finite threshold, occupied_above other than 0 / 1 and a stop_at other
+ * than the two above with SE_HIP_E_INVALID (n == 0 is a no-op), report a sticky SE_HIP_E_CAPACITY like the other read-back calls, and leave the
+ * map, the images, the image ring, the launch counters (SE_HIP_K_*) and the timing sums alone.
+ *   se_hip_trace_segments       device arrays; one launch enqueued on the handle's stream, asynchronous like the stage calls.
+ *   se_hip_trace_segments_host  host arrays; staged through a device buffer the handle keeps (and grows); synchronises before it returns. */
+#define SE_HIP_SEGMENT_LIMIT (1 << 22)
+typedef struct se_hip_trace_out {
+  uint8_t* status;  /* [n]    */
+  float* t_first;   /* [n]    */
+  int32_t* first;   /* [n][3] */
+  int32_t* counts;  /* [n][2] */
+} se_hip_trace_out;
+int se_hip_trace_segments(se_hip_pipeline* p, const int32_t* device_segments, int64_t n, const se_hip_collide_test* test, int32_t stop_at,
+                          const se_hip_trace_out* device_out);
+int se_hip_trace_segments_host(se_hip_pipeline* p, const int32_t* host_segments, int64_t n, const se_hip_collide_test* test, int32_t stop_at,
+                               const se_hip_trace_out* host_out);
+
 /* ---- batched ray casts against the resident map: the per-pixel body of the reference's raycastKernel (se_denseslam/src/rendering.cpp:51-90)
  *      for N rays of the caller's at once, without getMap() -- simulated range sensors, line-of-sight checks, views from poses that are not
  *      the tracked camera's.

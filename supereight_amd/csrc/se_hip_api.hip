@@ -26,6 +26,7 @@
 #include "se_query_kernels.h"
 #include "se_collide_kernels.h"
 #include "se_motion_kernels.h"
+#include "se_trace_kernels.h"
 #include "se_oriented_kernels.h"
 #include "se_clearance_kernels.h"
 #include "se_project_kernels.h"
@@ -2238,6 +2239,42 @@ int se_hip_collide_motions_host(se_hip_pipeline* p, const int32_t* host_motions,
                                 const se_hip_motion_out* host_out) {
   return batch_host(p, host_motions, 9 * sizeof(int32_t), n, motion_outs(host_out), [&] { return motion_args(host_motions, n, test, stop_at, host_out); },
                     [&](const void* mo, void* const* o) { launch_motions(p, (const int32_t*)mo, n, test, stop_at, o); });
+}
+
+
+// ------------------------------------------------------------------------------------ segment traces
+static_assert(SE_HIP_SEGMENT_LIMIT == SE_TRACE_LIMIT && SE_HIP_ORIENTED_SUB == (1 << SE_TRACE_SUB_SHIFT), "units and bound of se_hip_trace_segments");
+namespace {
+int trace_args(const int32_t* segments, int64_t n, const se_hip_collide_test* test, int32_t stop_at, const se_hip_trace_out* out) {
+  if (n < 0) return fail(SE_HIP_E_INVALID, "se_hip_trace_segments: n < 0");
+  if (!out) return fail(SE_HIP_E_INVALID, "se_hip_trace_segments: null out");
+  if (n > 0 && (!segments || !out->status)) return fail(SE_HIP_E_INVALID, "se_hip_trace_segments: null segments or status");
+  return collide_test_args("se_hip_trace_segments", test, &stop_at);
+}
+// the 4-byte items before status (bytes): the order the staging layout asks for (static: see query_outs)
+static BatchOuts trace_outs(const se_hip_trace_out* out) {
+  if (!out) return {4, {}};
+  return {4, {{out->t_first, sizeof(float)}, {out->first, 3 * sizeof(int32_t)}, {out->counts, 2 * sizeof(int32_t)}, {out->status, 1}}};
+}
+// One lane per segment, grid-stride beyond 2^20 workgroups; one instantiation per brick layout and per "counts wanted".
+void launch_trace(se_hip_pipeline* p, const int32_t* segments, int64_t n, const se_hip_collide_test* test, int32_t stop_at, void* const* out) {
+  const TraceArgs a{segments, (long long)n, (uint8_t*)out[3], (float*)out[0], (int32_t*)out[1], (int32_t*)out[2], test->threshold, test->occupied_above, (uint32_t)stop_at};
+  typedef void (*Kernel)(DevMap, TraceArgs);
+  static const Kernel k[2][2] = {{k_trace_segments<false, false>, k_trace_segments<false, true>}, {k_trace_segments<true, false>, k_trace_segments<true, true>}};
+  hipLaunchKernelGGL(k[p->map.dense ? 1 : 0][a.counts ? 1 : 0], dim3(grid_for((size_t)n, SE_WG_TRACE, 1 << 20)), dim3(SE_WG_TRACE), 0, p->stream, p->map, a);
+}
+}  // namespace
+
+int se_hip_trace_segments(se_hip_pipeline* p, const int32_t* device_segments, int64_t n, const se_hip_collide_test* test, int32_t stop_at,
+                          const se_hip_trace_out* device_out) {
+  return batch_device(p, device_segments, n, trace_outs(device_out), [&] { return trace_args(device_segments, n, test, stop_at, device_out); },
+                      [&](const void* sg, void* const* o) { launch_trace(p, (const int32_t*)sg, n, test, stop_at, o); });
+}
+
+int se_hip_trace_segments_host(se_hip_pipeline* p, const int32_t* host_segments, int64_t n, const se_hip_collide_test* test, int32_t stop_at,
+                               const se_hip_trace_out* host_out) {
+  return batch_host(p, host_segments, 6 * sizeof(int32_t), n, trace_outs(host_out), [&] { return trace_args(host_segments, n, test, stop_at, host_out); },
+                    [&](const void* sg, void* const* o) { launch_trace(p, (const int32_t*)sg, n, test, stop_at, o); });
 }
 
 

@@ -206,6 +206,80 @@ def oriented_boxes(centres_m, rotations, half_extents_m, dim, size):
     return np.clip(np.rint(out), -(2 ** 31), 2 ** 31 - 1).astype(np.int32)
 
 
+class _TraceOut(C.Structure):
+    """se_hip_trace_out of include/se_hip.h: output addresses, 0 = not wanted (status is required)."""
+    _fields_ = [("status", C.c_void_p), ("t_first", C.c_void_p), ("first", C.c_void_p), ("counts", C.c_void_p)]
+
+
+# se_hip_trace_segments: the bound of a valid segment (|coordinate| of a and b, in sub-units of 1 / ORIENTED_SUB voxel), and `first` where nothing blocks
+SEGMENT_LIMIT, TRACE_NONE = 1 << 22, -(1 << 31)
+
+
+def _odd_sub_units(x):
+    """float64 sub-units -> the nearest odd integer, 2 rint((x - 1) / 2) + 1, clamped to int32 (an odd value at either end)."""
+    return np.clip(2.0 * np.rint((x - 1.0) / 2.0) + 1.0, -(2.0 ** 31 - 1), 2.0 ** 31 - 1).astype(np.int32)
+
+
+def segments_from_points(a_m, b_m, dim, size):
+    """The int32 [N, 6] segments of DenseSLAMPipeline.trace from metric endpoints: a_m, b_m [N, 3] in metres, for a volume of `size` voxels over
+    `dim` metres.  Each coordinate x * ORIENTED_SUB * size / dim is rounded to the nearest *odd* sub-unit, 2 rint((x - 1) / 2) + 1: an endpoint
+    therefore never lies on a voxel boundary (a multiple of 16), and an axis-parallel segment never lies in a grid plane, where it would touch
+    nothing.  The query's answer is exact for the rounded segment: each coordinate moves by at most one sub-unit, an endpoint by at most
+    sqrt(3) / 16 voxel.  Values beyond int32 are clamped to it (such a segment is invalid anyway)."""
+    a = np.asarray(a_m, np.float64)
+    b = np.asarray(b_m, np.float64)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError(f"segments_from_points: a_m must have shape [N, 3], got {list(a.shape)}")
+    if b.shape != a.shape:
+        raise ValueError(f"segments_from_points: b_m must have shape {list(a.shape)}, got {list(b.shape)}")
+    if not (np.isfinite(a).all() and np.isfinite(b).all()):
+        raise ValueError("segments_from_points: non-finite input")
+    if not (dim > 0 and size > 0):
+        raise ValueError("segments_from_points: dim and size must be positive")
+    scale = ORIENTED_SUB * float(size) / float(dim)
+    return np.ascontiguousarray(np.concatenate([_odd_sub_units(a * scale), _odd_sub_units(b * scale)], 1))
+
+
+def view_segments(pose, k, width, height, stride, near, far, dim, size):
+    """The segments of a camera view for DenseSLAMPipeline.trace: pose (4 x 4, camera to world, metres), k = (fx, fy, cx, cy), the rays
+    through the pixels (u, v), u = 0, stride, 2 stride, ... < width and v likewise (pixel centres are the integer coordinates, as in the
+    raycast), row by row.  A ray runs from its origin + near * e to + far * e with e = R normalised((u - cx) / fx, (v - cy) / fy, 1), is
+    clipped in float64 to the cube [0, dim]^3 and snapped as segments_from_points snaps (then kept within 1 .. 16 size - 1, so that it stays
+    inside the cube).  Returns (segments int32 [M, 6] of the rays that meet the cube, in ray order; missed int64: the indices of the rays
+    that do not)."""
+    T = np.asarray(pose, np.float64)
+    kk = np.asarray(k, np.float64).reshape(-1)
+    if T.shape != (4, 4) or not np.isfinite(T).all():
+        raise ValueError("view_segments: pose must be a finite 4x4 matrix")
+    if kk.shape != (4,) or not np.isfinite(kk).all() or kk[0] == 0 or kk[1] == 0:
+        raise ValueError("view_segments: k must be four finite numbers (fx, fy, cx, cy) with fx, fy != 0")
+    for name, v in (("width", width), ("height", height), ("stride", stride)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f"view_segments: {name} must be a positive integer, got {v!r}")
+    if not (np.isfinite(near) and np.isfinite(far) and 0 <= near < far):
+        raise ValueError(f"view_segments: 0 <= near < far must hold, got {near!r}, {far!r}")
+    if not (dim > 0 and size > 0):
+        raise ValueError("view_segments: dim and size must be positive")
+    u, v = np.meshgrid(np.arange(0, width, stride, dtype=np.float64), np.arange(0, height, stride, dtype=np.float64))
+    e = np.stack([(u.reshape(-1) - kk[2]) / kk[0], (v.reshape(-1) - kk[3]) / kk[1], np.ones(u.size)], 1)
+    e = (e / np.linalg.norm(e, axis=1, keepdims=True)) @ T[:3, :3].T
+    a, b = T[:3, 3] + near * e, T[:3, 3] + far * e
+    # the part of a + s (b - a), s in [0, 1], inside the cube: the slab test per axis
+    d = b - a
+    s0, s1 = np.zeros(len(a)), np.ones(len(a))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for j in range(3):
+            lo, hi = (0.0 - a[:, j]) / d[:, j], (float(dim) - a[:, j]) / d[:, j]
+            still = d[:, j] == 0
+            inside = (a[:, j] >= 0) & (a[:, j] <= dim)
+            lo, hi = np.where(still, np.where(inside, -np.inf, np.inf), np.minimum(lo, hi)), np.where(still, np.where(inside, np.inf, -np.inf), np.maximum(lo, hi))
+            s0, s1 = np.maximum(s0, lo), np.minimum(s1, hi)
+    hit = s0 < s1
+    a, b = (a + s0[:, None] * d)[hit], (a + s1[:, None] * d)[hit]
+    seg = segments_from_points(np.clip(a, 0.0, dim), np.clip(b, 0.0, dim), dim, size)
+    return np.ascontiguousarray(np.clip(seg, 1, ORIENTED_SUB * int(size) - 1)), np.nonzero(~hit)[0].astype(np.int64)
+
+
 class _Edit(C.Structure):
     """se_hip_edit of include/se_hip.h (40 bytes)."""
     _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("x", C.c_float), ("y", C.c_float), ("flags", C.c_uint32), ("only", C.c_uint32)]
@@ -313,6 +387,8 @@ EXPORTS = {
     "se_hip_collide_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
     "se_hip_collide_motions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_MotionOut)]),
     "se_hip_collide_motions_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_MotionOut)]),
+    "se_hip_trace_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_TraceOut)]),
+    "se_hip_trace_segments_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_TraceOut)]),
     "se_hip_clearance_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_ClearanceOut)]),
     "se_hip_clearance_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_ClearanceOut)]),
     "se_hip_project_columns": (C.c_int, [C.c_void_p, C.POINTER(_ProjectRequest), C.POINTER(_CollideTest), C.POINTER(_ProjectOut)]),
@@ -968,6 +1044,63 @@ class DenseSLAMPipeline:
         res, out = self._batch_outputs(torch, dev, (n,), self._MOTION_OUTPUTS, {"status": True, "t_first": bool(t_first)}, _MotionOut)
         self._call(torch, dev, "se_hip_collide_motions", self._ptr(torch, mo, n), n, C.byref(test), stop, C.byref(out))
         return (res["status"], res["t_first"]) if t_first else res["status"]
+
+    _TRACE_OUTPUTS = (("status", (), np.uint8), ("t_first", (), np.float32), ("first", (3,), np.int32), ("counts", (2,), np.int32))
+
+    def trace(self, segments, threshold: float = 0.0, occupied_above=None, stop_at: str = "occupied", t_first: bool = True, first: bool = True,
+              counts: bool = True) -> dict:
+        """Exact segment traces (se_hip_trace_segments, include/se_hip.h): segments [N, 6] int32 = a xyz, b xyz in sub-units of
+        1 / ORIENTED_SUB voxel (segments_from_points() and view_segments() make them from metric ones).  The voxels a segment touches (open
+        inequalities, exact) are visited in the order it touches them and classified as collides() classifies them in strict mode (threshold /
+        occupied_above as there; outside the volume is unseen), up to the first that blocks (stop_at "occupied": occupied voxels; "unseen":
+        unseen ones too).  Returns a dict of the outputs asked for:
+          status   uint8 [N]: the min class up to and including the blocking voxel, COLLISION_EMPTY where nothing is touched,
+                   COLLISION_INVALID for a coordinate beyond +-2^22;
+          t_first  float32 [N]: the parameter at which the blocking voxel is entered, MOTION_FREE (2.0) when nothing blocks, -1 when invalid;
+          first    int32 [N, 3]: that voxel (x y z), TRACE_NONE where there is none;
+          counts   int32 [N, 2]: the unseen and the empty voxels inside the volume before it, (-1, -1) when invalid.  With stop_at "occupied"
+                   counts[:, 0] is the information gain of the ray; without counts the call skips absent octants in one jump each.
+          - numpy int32 [N, 6]: through the host entry; numpy arrays out.
+          - a torch int32 tensor on this handle's GPU (contiguous, [N, 6]): through the device entry; torch tensors on the same device out.
+            The caller's current torch stream is synchronised first, and the handle before the tensors are returned.
+        Anything else raises TypeError / ValueError before any library call."""
+        stop = self._stop_at("trace", stop_at)
+        test = self._occupancy_test("trace", threshold, occupied_above)
+        torch, sg, n = self._batch_input("trace", "segments", segments, np.int32, 6)
+        dev = sg.device if torch else None
+        want = {"status": True, "t_first": bool(t_first), "first": bool(first), "counts": bool(counts)}
+        res, out = self._batch_outputs(torch, dev, (n,), self._TRACE_OUTPUTS, want, _TraceOut)
+        self._call(torch, dev, "se_hip_trace_segments", self._ptr(torch, sg, n), n, C.byref(test), stop, C.byref(out))
+        return res
+
+    def view_gain(self, poses, k, width, height, stride: int = 8, near: float = 0.4, far: float = 4.0, threshold: float = 0.0, occupied_above=None,
+                  device: bool = False):
+        """Next-best-view scores of candidate camera poses [V, 4, 4] (camera to world, metres) with intrinsics k = (fx, fy, cx, cy): the fan of
+        view_segments() per pose, traced with stop_at "occupied" in ONE trace() call for all views.  Returns int64 [V, 4] per view: the unseen
+        voxels its rays look into before anything occupied (the information gain), the empty voxels they cross, the rays that ended on an
+        occupied voxel, and the rays traced (those that meet the volume).  device: upload the segments and take the sums on this handle's GPU
+        (a torch tensor out), else through the host entry (a numpy array out)."""
+        T = np.asarray(poses, np.float64)
+        if T.ndim != 3 or T.shape[1:] != (4, 4):
+            raise ValueError(f"view_gain: poses must have shape [V, 4, 4], got {list(T.shape)}")
+        if not isinstance(device, (bool, np.bool_)):
+            raise TypeError(f"view_gain: device must be a bool, got {type(device).__name__}")
+        self._occupancy_test("view_gain", threshold, occupied_above)
+        fans = [view_segments(t, k, width, height, stride, near, far, self.dim, self.size)[0] for t in T]
+        nv = len(fans)
+        seg = np.ascontiguousarray(np.concatenate(fans)) if nv else np.zeros((0, 6), np.int32)
+        view = np.repeat(np.arange(nv), [len(f) for f in fans])
+        torch, dev = self._own_device(bool(device))
+        if torch is None:
+            r = self.trace(seg, threshold, occupied_above, "occupied", t_first=False, first=False)
+            cols = np.stack([r["counts"][:, 0], r["counts"][:, 1], r["status"] == COLLISION_OCCUPIED, np.ones(len(seg), np.int64)], 1).astype(np.int64)
+            out = np.zeros((nv, 4), np.int64)
+            np.add.at(out, view, cols)
+            return out
+        r = self.trace(torch.from_numpy(seg).to(dev), threshold, occupied_above, "occupied", t_first=False, first=False)
+        cols = torch.stack([r["counts"][:, 0].long(), r["counts"][:, 1].long(), (r["status"] == COLLISION_OCCUPIED).long(),
+                            torch.ones(len(seg), dtype=torch.int64, device=dev)], 1)
+        return torch.zeros((nv, 4), dtype=torch.int64, device=dev).index_add_(0, torch.from_numpy(view).to(dev), cols)
 
     def collides_oriented(self, boxes, threshold: float = 0.0, occupied_above=None):
         """Batched collision queries for oriented boxes (se_hip_collide_oriented, include/se_hip.h): boxes [N, 12] int32 = centre xyz, then the

@@ -23,7 +23,7 @@ def main():
     dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.splitlines()
     for (name, v, a, s, sc, occ, lds), d in zip(rows, dem):
         d = re.sub(r"\(.*", "", d).replace("void ", "")
-        if any(k in d for k in ("k_alloc_scan", "k_raycast", "k_integrate", "k_icp", "k_alloc_commit", "k_occ_commit", "k_cast_rays", "k_render_volume", "k_query_points", "k_mesh", "k_edit", "k_alloc_boxes", "k_collide_boxes", "k_collide_motions", "k_clearance_boxes", "k_project_columns", "k_field_", "k_reach_", "k_collide_oriented", "k_shift", "k_merge_select", "k_merge_bricks", "k_rigid_", "k_release")):
+        if any(k in d for k in ("k_alloc_scan", "k_raycast", "k_integrate", "k_icp", "k_alloc_commit", "k_occ_commit", "k_cast_rays", "k_render_volume", "k_query_points", "k_mesh", "k_edit", "k_alloc_boxes", "k_collide_boxes", "k_collide_motions", "k_trace_segments", "k_clearance_boxes", "k_project_columns", "k_field_", "k_reach_", "k_collide_oriented", "k_shift", "k_merge_select", "k_merge_bricks", "k_rigid_", "k_release")):
             print(f"{d:<60} VGPR {v:>3} AGPR {a:>3} SGPR {s:>3} scratch {sc:>4} occ {occ} lds {lds}")
 
 
