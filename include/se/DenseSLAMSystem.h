@@ -253,6 +253,22 @@ class DenseSLAMSystem {
     for (int i = 0; i < 3; ++i)
       for (int k = 0; k < 3; ++k) out[3 + 3 * i + k] = (int32_t)std::nearbyint((double)box_to_world(k, i) * half_extents_m(i) * scale);
   }
+  /* Not in the reference's class: collision queries for n oriented boxes moved along straight segments (host_motions[n][15]: the box as for
+   * collidesOriented, then the displacement d xyz in sub-units; the attitude does not change) -- the min class over the voxels the moving box
+   * touches and the exact parameter at which it first touches a blocking one -- se_hip_collide_oriented_motions_host, definitions in
+   * se_hip.h.  host_out.status is required; a null t_first or t_exact means "not wanted".  stop_at is SE_HIP_COLLISION_OCCUPIED or
+   * SE_HIP_COLLISION_UNSEEN.  The answers are those of se::geometry::oriented_motion_status (include/se/oriented_motion.hpp) on the
+   * getMap() snapshot. */
+  bool collidesOrientedMoving(const int32_t* host_motions, size_t n, const se_hip_collide_test& test, int32_t stop_at, se_hip_oriented_motion_out& host_out) {
+    return ok(se_hip_collide_oriented_motions_host(h_, host_motions, (int64_t)n, &test, stop_at, &host_out));
+  }
+  /* The fifteen int32 of one such motion from a metric one: the box as orientedBox rounds it, then displacement_m (metres) rounded to the
+   * nearest sub-unit like the centre (se::geometry::oriented_motion_round of include/se/oriented_motion.hpp does the same on plain arrays). */
+  void orientedMotion(const Eigen::Matrix4f& box_to_world, const Eigen::Vector3f& half_extents_m, const Eigen::Vector3f& displacement_m, int32_t out[15]) const {
+    const double scale = (double)SE_HIP_ORIENTED_SUB * volume_resolution_.x() / volume_dimension_.x();
+    orientedBox(box_to_world, half_extents_m, out);
+    for (int k = 0; k < 3; ++k) out[12 + k] = (int32_t)std::nearbyint(displacement_m(k) * scale);
+  }
   /* Not in the reference's class: exact segment traces for n segments (host_segments[n][6]: a xyz, b xyz in sub-units of
    * 1 / SE_HIP_ORIENTED_SUB voxel) -- the min class on the way to the first blocking voxel, its entry parameter, the voxel, and the unseen /
    * empty voxels before it -- se_hip_trace_segments_host, definitions in se_hip.h.  host_out.status is required; a null pointer for another

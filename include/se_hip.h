@@ -675,6 +675,66 @@ int se_hip_reach_field_host(se_hip_pipeline* p, const se_hip_reach_request* requ
 int se_hip_collide_oriented(se_hip_pipeline* p, const int32_t* device_boxes, int64_t n, const se_hip_collide_test* test, uint8_t* device_status);
 int se_hip_collide_oriented_host(se_hip_pipeline* p, const int32_t* host_boxes, int64_t n, const se_hip_collide_test* test, uint8_t* host_status);
 
+/* ---- batched collision queries for oriented boxes moved along straight segments: "may this robot, at this attitude, move from A to B, and
+ *      if not, how far?" for N motions at once, without getMap().  se_hip_collide_motions for the box of se_hip_collide_oriented.  Not in the
+ *      reference; built on its Octree::get and on the classification above.  The host restatement and the literal definition are
+ *      include/se/oriented_motion.hpp.
+ * Units: SE_HIP_ORIENTED_SUB = 16 sub-units per voxel.
+ * Motion: fifteen int32, centre c xyz, half-axes h0, h1, h2 xyz, displacement d xyz (motions [n][15]).  At parameter t in [0, 1] the box is the
+ *   open set   B(t) = { c + t d + s0 h0 + s1 h1 + s2 h2 : |s_i| < 1 }.   The half-axes need not be orthogonal, as for the static query; the
+ *   attitude does not change during the motion.
+ * Touched: a cube with integer corner v and side s in voxels (a voxel: s = 1) is touched iff some t in [0, 1] has B(t) touching it in the
+ *   sense of se_hip_collide_oriented.  Written out, with the fifteen axes of that query (e_k, h_i x h_j, h_i x e_k; a zero axis takes no
+ *   part), per axis a:
+ *     m = 32 v + 16 s - 2 c,   p = a . m,   q = 2 (a . d),   R = 2 sum_i |a . h_i| + 16 s sum_k |a_k|.
+ *   The box at t is not separated by a iff |p - t q| < R.  An axis with q = 0 gives the static condition |p| < R; every other axis the open
+ *   interval ((p' - R) / |q|, (p' + R) / |q|) with p' = p sign(q).  With L the largest lower end and U the smallest upper end over those axes
+ *   (L = 0, U = 1 when there is none) the cube is touched iff every static condition holds and L < U, L < 1, U > 0, and its entry parameter
+ *   is t_in = max(0, L).  All inequalities are open.  t_in is an infimum: a box whose vertex only meets a voxel's corner at t = 0 and then
+ *   slides into the voxel has t_in = 0, although the static query at t = 0 says "not touched".
+ * Equivalent form (used for pruning and for the touched test on the device; the host tests hold the two together): the swept set is the open
+ *   zonotope with generators h0, h1, h2, d / 2 about c + d / 2, and a cube is touched iff none of the 21 axes e_k, g_i x g_j, g_i x e_k with
+ *   g = (h0, h1, h2, d) separates; an axis a != 0 separates iff
+ *     |a . (32 v + 16 s - 2 c - d)| >= 2 sum_i |a . h_i| + |a . d| + 16 s sum_k |a_k|.
+ * A motion is invalid if its box is invalid for se_hip_collide_oriented (det(h0, h1, h2) == 0, |c_k| > 2^20, |h_ik| > 2^14), if any
+ *   |d_k| > SE_HIP_ORIENTED_MOVE_LIMIT = 2^18 (16 384 voxels, twice the largest volume) or if any |c_k + d_k| > 2^20.  An invalid motion gets
+ *   status SE_HIP_COLLISION_INVALID, t_first = -1, t_exact = (-1, 1), and reads no map memory.
+ * Exactness: nothing is rounded before the final conversion.  With those bounds and sizes up to 8192, for the fifteen axes |a_k| <= 2^29 as
+ *   in the static query, |m_k| < 2^22 and |p| <= 3 * 2^29 * 2^22 < 2^53; |q| <= 2 * 3 * 2^29 * 2^18 < 2^50; R < 2^49 as there: the numerators
+ *   p' +- R stay below 2^54.  A component of h_i x d or d x e_k is at most 2 * 2^14 * 2^18 = 2^33; |32 v + 16 s - 2 c - d| < 2^22 + 2^18, so
+ *   the left side of the 21-axis form is below 3 * 2^33 * 2^22.1 < 2^57, and on its right 2 sum_i |a . h_i| <= 2 * 3 * 3 * 2^33 * 2^14 < 2^52
+ *   and 16 s sum_k |a_k| <= 2^17 * 3 * 2^33 < 2^52: both sides stay below 2^59.  Everything is int64 except the comparison of two rationals,
+ *   which is a cross-multiplication in 128 bits (products below 2^104); there is no 128-bit division.
+ * Classification: exactly that of se_hip_collide_oriented and of SE_HIP_COLLIDE_STRICT -- `test` applied to Octree::get(v), a pending index
+ *   entry counts as absent, voxels outside [0, size)^3 are unseen.  The box touches a voxel outside the volume at t iff, for some k,
+ *   c_k + t d_k - ext_k < 0 or c_k + t d_k + ext_k > 16 size with ext_k = sum_i |h_ik|: the outside's contribution to status, and to the
+ *   entry parameter when stop_at is unseen, is closed form per face.  An absent touched octant folds classify(value_[child]), and the octant's
+ *   own t_in when that class blocks; both are exact by the open-set argument of the static query.
+ * Outputs (se_hip_oriented_motion_out; status is required, a null t_first or t_exact means "not wanted"):
+ *   status[n]      (uint8) the min class over the touched voxels, as for se_hip_collide_motions.
+ *   t_exact[n][2]  (int64) with stop_at in {SE_HIP_COLLISION_OCCUPIED, SE_HIP_COLLISION_UNSEEN}, a voxel blocks when its class is <= stop_at;
+ *                  the smallest t_in over the touched blocking voxels (those outside the volume included) as a reduced fraction num / den,
+ *                  den > 0, gcd = 1: (0, 1) when blocked from the start, (2, 1) when nothing blocks, (-1, 1) for an invalid motion.
+ *   t_first[n]     (float) (float)((double)num / (double)den) of that reduced pair -- reduced first, so that the float depends on the value
+ *                  only; SE_HIP_MOTION_FREE (2.0f) when nothing blocks, -1.0f for an invalid motion.
+ * Both entries answer for the map after everything enqueued before them (a scan that ran on the side stream included), refuse n < 0, a null
+ * out, a null motions or status pointer with n > 0, a null test, a non-finite threshold, occupied_above other than 0 / 1 and a stop_at other
+ * than the two above with SE_HIP_E_INVALID (n == 0 is a no-op), report a sticky SE_HIP_E_CAPACITY like the other read-back calls, and leave the
+ * map, the images and the launch counters (SE_HIP_K_*) alone.
+ *   se_hip_collide_oriented_motions       device arrays; enqueued on the handle's stream, asynchronous like the stage calls.
+ *   se_hip_collide_oriented_motions_host  host arrays; staged through a device buffer the handle keeps (and grows); synchronises before it
+ *                                         returns. */
+#define SE_HIP_ORIENTED_MOVE_LIMIT (1 << 18)
+typedef struct se_hip_oriented_motion_out {
+  uint8_t* status;   /* [n] */
+  float* t_first;    /* [n] */
+  int64_t* t_exact;  /* [n][2] */
+} se_hip_oriented_motion_out;
+int se_hip_collide_oriented_motions(se_hip_pipeline* p, const int32_t* device_motions, int64_t n, const se_hip_collide_test* test, int32_t stop_at,
+                                    const se_hip_oriented_motion_out* device_out);
+int se_hip_collide_oriented_motions_host(se_hip_pipeline* p, const int32_t* host_motions, int64_t n, const se_hip_collide_test* test, int32_t stop_at,
+                                         const se_hip_oriented_motion_out* host_out);
+
 /* ---- exact segment traces: "is there a free line of sight from A to B, and if not, which voxel is in the way?" and "how much unseen space
  *      would a sensor at this pose look into?" for N segments at once, without getMap().  The motion query for a point, in traversal order,
  *      with class counts: the occupancy-reader counterpart of se_hip_cast_rays, which marches the float field through allocated blocks only

@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC_DIR = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libse_hip.so")
 SOURCES = ["se_hip_api.hip"]
-HEADERS = ["se_device.h", "se_sample.h", "se_kernels.h", "se_track_kernels.h", "se_mesh_kernels.h", "se_query_kernels.h", "se_frontier.h", "se_collide_kernels.h", "se_motion_kernels.h", "se_trace_kernels.h", "se_clearance_kernels.h", "se_project_kernels.h", "se_field_kernels.h", "se_reach_kernels.h", "se_oriented_kernels.h", "se_edit_kernels.h", "se_alloc_kernels.h", "se_ray_kernels.h", "se_shift_kernels.h", "se_merge_kernels.h", "se_resample_kernels.h", "se_release_kernels.h", "se_host_resources.h", os.path.join("..", "..", "include", "se_hip.h"),
+HEADERS = ["se_device.h", "se_sample.h", "se_kernels.h", "se_track_kernels.h", "se_mesh_kernels.h", "se_query_kernels.h", "se_frontier.h", "se_collide_kernels.h", "se_motion_kernels.h", "se_trace_kernels.h", "se_clearance_kernels.h", "se_project_kernels.h", "se_field_kernels.h", "se_reach_kernels.h", "se_oriented_kernels.h", "se_oriented_motion_kernels.h", "se_edit_kernels.h", "se_alloc_kernels.h", "se_ray_kernels.h", "se_shift_kernels.h", "se_merge_kernels.h", "se_resample_kernels.h", "se_release_kernels.h", "se_host_resources.h", os.path.join("..", "..", "include", "se_hip.h"),
            os.path.join("..", "..", "include", "se_mc_table.h")]
 # -ffp-contract=off is part of the numeric contract (no FMA contraction in device or host code)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unused-value"]

@@ -28,6 +28,7 @@
 #include "se_motion_kernels.h"
 #include "se_trace_kernels.h"
 #include "se_oriented_kernels.h"
+#include "se_oriented_motion_kernels.h"
 #include "se_clearance_kernels.h"
 #include "se_project_kernels.h"
 #include "se_field_kernels.h"
@@ -576,18 +577,18 @@ int batch_device(se_hip_pipeline* p, const void* in, int64_t n, const BatchOuts&
   return SE_HIP_OK;
 }
 // Host form: staging = [input n x in_item_bytes][the outputs asked for, in the order given]; upload, launch on the staged arrays, download.
-// (An input item that is not a multiple of 8 bytes must not be followed by an 8-byte output: the edits' 40-byte records are.)
+// (The input part is padded to a multiple of 8 bytes, so that an 8-byte output may follow an input whose items are not: the oriented motions' 60-byte rows.)
 template <typename Check, typename Launch>
 int batch_host(se_hip_pipeline* p, const void* in, size_t in_item_bytes, int64_t n, const BatchOuts& out, Check args_ok, Launch launch) {
   if (int r = query_prologue(p, args_ok)) return r;
   if (n == 0) return fetch_counters(p);
   const size_t un = (size_t)n;
   size_t bytes[6], off[6];
-  bytes[0] = un * in_item_bytes;
+  bytes[0] = (un * in_item_bytes + 7) & ~(size_t)7;
   for (int k = 0; k < out.count; ++k) bytes[k + 1] = out.o[k].ptr ? (out.o[k].per_call ? 1 : un) * out.o[k].item_bytes : 0;
   if (int r = reserve_staging(p, staging_layout(bytes, out.count + 1, off))) return r;
   unsigned char* b = p->staging;
-  HIP_TRY(hipMemcpyAsync(b, in, bytes[0], hipMemcpyHostToDevice, p->stream));
+  HIP_TRY(hipMemcpyAsync(b, in, un * in_item_bytes, hipMemcpyHostToDevice, p->stream));
   void *dev[5], *host[5];
   for (int k = 0; k < out.count; ++k) { dev[k] = bytes[k + 1] ? b + off[k + 1] : nullptr; host[k] = out.o[k].ptr; }
   launch(b, dev);
@@ -2608,6 +2609,39 @@ int se_hip_collide_oriented_host(se_hip_pipeline* p, const int32_t* host_boxes, 
   const BatchOuts out{1, {{host_status, 1}}};
   return batch_host(p, host_boxes, 12 * sizeof(int32_t), n, out, [&] { return oriented_args(host_boxes, n, test, host_status); },
                     [&](const void* boxes, void* const* o) { launch_oriented(p, (const int32_t*)boxes, n, test, (uint8_t*)o[0]); });
+}
+
+
+// ------------------------------------------------------------------------------------ oriented motion collision queries
+static_assert(SE_HIP_ORIENTED_MOVE_LIMIT == SE_ORIENTED_MOVE_LIMIT && sizeof(long long) == sizeof(int64_t), "bound and t_exact of se_hip_collide_oriented_motions");
+namespace {
+int oriented_motion_args(const int32_t* motions, int64_t n, const se_hip_collide_test* test, int32_t stop_at, const se_hip_oriented_motion_out* out) {
+  if (n < 0) return fail(SE_HIP_E_INVALID, "se_hip_collide_oriented_motions: n < 0");
+  if (!out) return fail(SE_HIP_E_INVALID, "se_hip_collide_oriented_motions: null out");
+  if (n > 0 && (!motions || !out->status)) return fail(SE_HIP_E_INVALID, "se_hip_collide_oriented_motions: null motions or status");
+  return collide_test_args("se_hip_collide_oriented_motions", test, &stop_at);
+}
+// t_exact (8-byte items) before t_first (4-byte items) before status (bytes): the order the staging layout asks for (static: see query_outs)
+static BatchOuts oriented_motion_outs(const se_hip_oriented_motion_out* out) {
+  if (!out) return {3, {}};
+  return {3, {{out->t_exact, 2 * sizeof(int64_t)}, {out->t_first, sizeof(float)}, {out->status, 1}}};
+}
+void launch_oriented_motions(se_hip_pipeline* p, const int32_t* motions, int64_t n, const se_hip_collide_test* test, int32_t stop_at, void* const* out) {
+  const OrientedMotionArgs a{motions, (long long)n, (uint8_t*)out[2], (float*)out[1], (long long*)out[0], test->threshold, test->occupied_above, (uint32_t)stop_at};
+  launch_wave_per_item(p, n, k_collide_oriented_motions<true>, k_collide_oriented_motions<false>, a);
+}
+}  // namespace
+
+int se_hip_collide_oriented_motions(se_hip_pipeline* p, const int32_t* device_motions, int64_t n, const se_hip_collide_test* test, int32_t stop_at,
+                                    const se_hip_oriented_motion_out* device_out) {
+  return batch_device(p, device_motions, n, oriented_motion_outs(device_out), [&] { return oriented_motion_args(device_motions, n, test, stop_at, device_out); },
+                      [&](const void* mo, void* const* o) { launch_oriented_motions(p, (const int32_t*)mo, n, test, stop_at, o); });
+}
+
+int se_hip_collide_oriented_motions_host(se_hip_pipeline* p, const int32_t* host_motions, int64_t n, const se_hip_collide_test* test, int32_t stop_at,
+                                         const se_hip_oriented_motion_out* host_out) {
+  return batch_host(p, host_motions, 15 * sizeof(int32_t), n, oriented_motion_outs(host_out), [&] { return oriented_motion_args(host_motions, n, test, stop_at, host_out); },
+                    [&](const void* mo, void* const* o) { launch_oriented_motions(p, (const int32_t*)mo, n, test, stop_at, o); });
 }
 
 

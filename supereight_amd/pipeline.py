@@ -82,6 +82,13 @@ class _MotionOut(C.Structure):
 
 # t_first of se_hip_collide_motions when nothing blocks the motion; what stop_at may name
 MOTION_FREE = 2.0
+
+
+class _OrientedMotionOut(C.Structure):
+    """se_hip_oriented_motion_out of include/se_hip.h: output addresses, t_first / t_exact 0 = not wanted."""
+    _fields_ = [("status", C.c_void_p), ("t_first", C.c_void_p), ("t_exact", C.c_void_p)]
+
+
 _MOTION_STOPS = {"occupied": COLLISION_OCCUPIED, "unseen": COLLISION_UNSEEN}
 
 
@@ -204,6 +211,25 @@ def oriented_boxes(centres_m, rotations, half_extents_m, dim, size):
     for i in range(3):
         out[:, 3 + 3 * i:6 + 3 * i] = r[:, :, i] * e[:, i:i + 1] * scale
     return np.clip(np.rint(out), -(2 ** 31), 2 ** 31 - 1).astype(np.int32)
+
+
+# se_hip_collide_oriented_motions: the bound of a valid displacement (|d_k|, in sub-units)
+ORIENTED_MOVE_LIMIT = 1 << 18
+
+
+def oriented_motions(centres_m, rotations, half_extents_m, displacements_m, dim, size):
+    """The int32 [N, 15] motions of DenseSLAMPipeline.collides_oriented_moving from metric ones: the box as oriented_boxes() rounds it (centres_m
+    [N, 3], rotations [N, 3, 3], half_extents_m [N, 3]), then displacements_m [N, 3] in metres rounded to the nearest sub-unit like the centre.
+    The query's answer is exact for the rounded motion.  Values beyond int32 are clamped to it (such a motion is invalid anyway)."""
+    boxes = oriented_boxes(centres_m, rotations, half_extents_m, dim, size)
+    d = np.asarray(displacements_m, np.float64)
+    if d.shape != (boxes.shape[0], 3):
+        raise ValueError(f"oriented_motions: displacements_m must have shape [{boxes.shape[0]}, 3], got {list(d.shape)}")
+    if not np.isfinite(d).all():
+        raise ValueError("oriented_motions: non-finite input")
+    scale = ORIENTED_SUB * float(size) / float(dim)
+    dd = np.clip(np.rint(d * scale), -(2 ** 31), 2 ** 31 - 1).astype(np.int32)
+    return np.ascontiguousarray(np.concatenate([boxes, dd], 1))
 
 
 class _TraceOut(C.Structure):
@@ -399,6 +425,8 @@ EXPORTS = {
     "se_hip_reach_field_host": (C.c_int, [C.c_void_p, C.POINTER(_ReachRequest), C.POINTER(_CollideTest), C.POINTER(_ReachOut)]),
     "se_hip_collide_oriented": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_void_p]),
     "se_hip_collide_oriented_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_void_p]),
+    "se_hip_collide_oriented_motions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_OrientedMotionOut)]),
+    "se_hip_collide_oriented_motions_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.POINTER(_OrientedMotionOut)]),
     "se_hip_edit_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
     "se_hip_edit_boxes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_CollideTest), C.c_int32, C.c_void_p]),
     "se_hip_allocate_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
@@ -1119,6 +1147,33 @@ class DenseSLAMPipeline:
         out = np.empty(n, np.uint8) if torch is None else torch.empty(n, dtype=torch.uint8, device=dev)
         self._call(torch, dev, "se_hip_collide_oriented", self._ptr(torch, b, n), n, C.byref(test), self._ptr(torch, out, n))
         return out
+
+    _ORIENTED_MOTION_OUTPUTS = (("status", (), np.uint8), ("t_first", (), np.float32), ("t_exact", (2,), np.int64))
+
+    def collides_oriented_moving(self, motions, threshold: float = 0.0, occupied_above=None, stop_at: str = "occupied", t_first: bool = True,
+                                 exact: bool = False):
+        """Batched collision queries for oriented boxes moved along straight segments (se_hip_collide_oriented_motions, include/se_hip.h):
+        motions [N, 15] int32 = centre xyz, the half-axes h0, h1, h2 xyz, the displacement d xyz, in sub-units of 1 / ORIENTED_SUB voxel
+        (oriented_motions() makes them from metric ones).  The box of collides_oriented() is translated by t * d, t in [0, 1], without turning.
+        Exact for the continuous motion: a voxel counts iff the moving box touches it (open inequalities, integer arithmetic), and is classified
+        as collides() classifies it in strict mode (threshold / occupied_above as there; outside the volume is unseen).  Returns the status per
+        motion -- the min class over the touched voxels, COLLISION_INVALID for an invalid box, |d_k| > 2^18 or |c_k + d_k| > 2^20 -- or, with
+        t_first, (status, t_first): the parameter at which the motion first touches a voxel that blocks (stop_at "occupied": occupied voxels;
+        "unseen": unseen ones too), 0 when it is blocked at its start, MOTION_FREE (2.0) when nothing blocks, -1 for an invalid motion; with
+        exact, the int64 [N, 2] reduced fractions num / den of that parameter come last ((2, 1) free, (-1, 1) invalid).
+          - numpy int32 [N, 15]: through the host entry; numpy arrays out.
+          - a torch int32 tensor on this handle's GPU (contiguous, [N, 15]): through the device entry; torch tensors on the same device out.
+            The caller's current torch stream is synchronised first, and the handle before the tensors are returned.
+        Anything else raises TypeError / ValueError before any library call."""
+        stop = self._stop_at("collides_oriented_moving", stop_at)
+        test = self._occupancy_test("collides_oriented_moving", threshold, occupied_above)
+        torch, mo, n = self._batch_input("collides_oriented_moving", "motions", motions, np.int32, 15)
+        dev = mo.device if torch else None
+        want = {"status": True, "t_first": bool(t_first), "t_exact": bool(exact)}
+        res, out = self._batch_outputs(torch, dev, (n,), self._ORIENTED_MOTION_OUTPUTS, want, _OrientedMotionOut)
+        self._call(torch, dev, "se_hip_collide_oriented_motions", self._ptr(torch, mo, n), n, C.byref(test), stop, C.byref(out))
+        got = [res["status"]] + ([res["t_first"]] if t_first else []) + ([res["t_exact"]] if exact else [])
+        return got[0] if len(got) == 1 else tuple(got)
 
     _CLEARANCE_OUTPUTS = (("d2", (), np.int32), ("nearest", (3,), np.int32))
 
